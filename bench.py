@@ -1,6 +1,6 @@
 """bench.py -- generator+discriminator training frames/sec at 512x1024 (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 A step = one window of the vid2vid inner loop on one GPU: two-scale generator
@@ -10,7 +10,17 @@ Adam steps, RCCL all-reduce of all gradients when N > 1 (frame-parallel: every r
 synthetic sequence; weak scaling).  Synthetic inputs and seeded random-init weights (no datasets or
 checkpoints offline), resident in HBM before the timed region.
 
-Prints ONE JSON line (rank 0).  Besides the contract keys it carries
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times K steps and prints the headline keys
+(metric, value, unit, higher_is_better, dtype, ms_per_step, ...).
+
+--dump-outputs DIR (rank 0) writes, after the timed steps, what the last timed window computed, as float32 .npy files:
+  loss_<name>  -- every loss term train_window returns (scalars);
+  fake_B, fake_B_raw, flow, weight -- the generated frame, raw frame, flow and blend weight (trainer.last_outputs);
+  params_G_sample, params_D_sample, params_D_T_sample -- a fixed, seeded sample of about 1 M of each network's
+                  parameters after the window's Adam step (flat in parameters() order, sorted sample indices).
+Inputs and weights are seeded, so the same arguments give the same inputs in every run.
+
+--full additionally measures, outside the timed steps or with per-launch events inside them:
   roofline     -- the dominant kernel (MFMA implicit-GEMM 3x3 convolution), HIP-event timed per launch
                   inside the timed region on the launch stream: algorithmic flops / mean duration
                   against the 2.5 PFLOP/s dense bf16 peak (MI355X_MICROARCH.md);
@@ -37,6 +47,8 @@ H, W = 512, 1024
 PREROLL = 12          # windows until both temporal discriminator scales are active AND every lazy step is behind us:
                       # the skipped pairs' flows are reused from window 9 on, which changes FlowNet2's batch, and its
                       # HIP graph at the new shape is captured on the third call (window 11)
+DUMP_LIMIT_BYTES = 64 * 2 ** 20   # --dump-outputs: all files together
+PARAM_SAMPLE = 1 << 20            # --dump-outputs: sample indices drawn per network (duplicates dropped)
 
 
 def usable_cpus():
@@ -205,13 +217,49 @@ def config3_operators(dev):
     return out
 
 
+def param_sample(params, n, seed):
+    """float32 values of a fixed, seeded sample of the parameters taken as one flat vector in the given order: ``n``
+    indices drawn with numpy's default_rng(seed), duplicates dropped, ascending."""
+    import numpy as np
+    flat = [p.detach().reshape(-1) for p in params]
+    offs = np.concatenate([[0], np.cumsum([t.numel() for t in flat])])
+    idx = np.unique(np.random.default_rng(seed).integers(0, offs[-1], n))
+    owner = np.searchsorted(offs, idx, side="right") - 1
+    parts = []
+    for k in np.unique(owner):
+        sel = torch.from_numpy(idx[owner == k] - offs[k]).to(flat[k].device)
+        parts.append(flat[k][sel].float().cpu())
+    return torch.cat(parts).numpy()
+
+
+def dump_outputs(out_dir, losses, trainer):
+    """--dump-outputs: what the last timed window computed (see the module docstring), float32 .npy files."""
+    import re
+    import numpy as np
+    torch.cuda.synchronize()
+    arrays = {"loss_" + re.sub(r"[^A-Za-z0-9_.-]", "_", k): v.float().cpu().numpy() for k, v in losses.items()}
+    arrays.update({k: t.float().cpu().numpy() for k, t in zip(("fake_B", "fake_B_raw", "flow", "weight"), trainer.last_outputs)})
+    nets = {"G": [p for g in trainer.netG for p in g.parameters()], "D": list(trainer.netD.parameters()),
+            "D_T": [p for d in trainer.netD_T for p in d.parameters()]}
+    for seed, (name, params) in enumerate(nets.items()):
+        arrays[f"params_{name}_sample"] = param_sample(params, PARAM_SAMPLE, seed)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {total} bytes > {DUMP_LIMIT_BYTES}"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a, dtype=np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f16"])
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed window's outputs to DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure roofline, the generator forwards, BASELINE configs 5 and 3 and cpu_baseline")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -253,35 +301,65 @@ def main():
 
     i = 0
     for k in range(PREROLL + args.warmup):   # untimed: steady-state sequence state + W warm-up steps
-        if k == PREROLL + args.warmup - 1:
+        if args.full and k == PREROLL + args.warmup - 1:
             torch.cuda.synchronize()
             C.PROFILE = {}                   # last untimed window: every convolution shape bracketed
             t_w = time.perf_counter()
         window(i)
         i += 1
     torch.cuda.synchronize()
-    survey_s = time.perf_counter() - t_w
-    survey, C.PROFILE = shape_totals(C.PROFILE), None
-    # dominant kernel = the convolution shape with the largest total time in that window
-    dominant = max(survey, key=lambda kk: survey[kk][0])
+    if args.full:
+        survey_s = time.perf_counter() - t_w
+        survey, C.PROFILE = shape_totals(C.PROFILE), None
+        # dominant kernel = the convolution shape with the largest total time in that window
+        dominant = max(survey, key=lambda kk: survey[kk][0])
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
-    C.PROFILE = {"only": dominant}           # timed region: events around the dominant shape only
+    if args.full:
+        C.PROFILE = {"only": dominant}       # timed region: events around the dominant shape only
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        window(i)
+        losses = window(i)
         i += 1
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
-    prof, C.PROFILE = shape_totals(C.PROFILE), None
+    if args.full:
+        prof, C.PROFILE = shape_totals(C.PROFILE), None
     t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, losses, trainer)
+
+    frames = world * args.steps * 1  # n_frames_load = 1 frame per window per rank
+    line = {
+        "metric": "generator+discriminator frames/sec at 512x1024", "value": round(frames / elapsed, 3), "unit": "frames/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 2),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
+        "config": {"workload": "vid2vid training window 512x1024: 2-scale generator (composite ngf128 @256x512 + "
+                               "composite-local ngf64 @512x1024, tG=3) + FlowNet2 reference flow + image D (num_D=2) + "
+                               "2 temporal D, 3 backward passes + Adam; batch 1 frame per GPU",
+                   "parallelism": f"dp{world} (frame-parallel sequences, RCCL gradient all-reduce)"},
+    }
+    if args.full:
+        del trainer      # (also out of the window closure) the forward-only measurements want its memory
+        line.update(full_measurements(args, dev, rank, world, survey, survey_s, dominant, prof))
+    if rank == 0:
+        print(json.dumps(line), flush=True)
+    if world > 1:
+        dist.barrier()   # rank 0 ran the extra forward-only measurement: leave the job together
+        dist.destroy_process_group()
+
+
+def full_measurements(args, dev, rank, world, survey, survey_s, dominant, prof):
+    """--full: roofline of the dominant convolution (from the bracketed survey window and timed region), the generator-
+    forward timings and BASELINE configs 5 / 3 (rank 0), cpu_baseline (rank 0 at N = 1) -> keys of the JSON line."""
+    dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float16
 
     def traffic_of(key):
         """(HBM-side bytes per launch, where they were measured) from the committed PMC passes
@@ -318,7 +396,6 @@ def main():
     if rank == 0:
         from ir2rgb_amd import networks as N
         opt = dict(gen_blocks=9, n_blocks_local=3, fg=False, no_flow=False, n_local_enhancers=1, feat_num=3)
-        del trainer
         torch.cuda.empty_cache()
         torch.manual_seed(0)
         g = N.build_generator_module(9, 3, 6, 128, "composite", 3, "batch", 0, **opt).to(dev).train()
@@ -363,24 +440,10 @@ def main():
                 extra[name] = {"error": f"{type(e).__name__}: {e}"}
             torch.cuda.empty_cache()
 
-    frames = world * args.steps * 1  # n_frames_load = 1 frame per window per rank
-    line = {
-        "metric": "generator+discriminator frames/sec at 512x1024", "value": round(frames / elapsed, 3), "unit": "frames/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 2),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
-        "config": {"workload": "vid2vid training window 512x1024: 2-scale generator (composite ngf128 @256x512 + "
-                               "composite-local ngf64 @512x1024, tG=3) + FlowNet2 reference flow + image D (num_D=2) + "
-                               "2 temporal D, 3 backward passes + Adam; batch 1 frame per GPU",
-                   "parallelism": f"dp{world} (frame-parallel sequences, RCCL gradient all-reduce)"},
-        "roofline": roofline, "extra": extra,
-    }
-    if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
-            line["cpu_baseline"] = cpu_baseline(usable_cpus())
-        print(json.dumps(line), flush=True)
-    if world > 1:
-        dist.barrier()   # rank 0 ran the extra forward-only measurement: leave the job together
-        dist.destroy_process_group()
+    line = {"roofline": roofline, "extra": extra}
+    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+        line["cpu_baseline"] = cpu_baseline(usable_cpus())
+    return line
 
 
 if __name__ == "__main__":
