@@ -1,0 +1,97 @@
+"""Per-element error bounds of the half-precision MFMA kernels against an fp64 reference (test-only).
+
+A kernel result ``got`` of an exact value ``ref`` is accepted when, element by element,
+
+    |got - ref| <= u_out * |ref| + (1 + u_out) * b * S + eta
+
+* ``u_out``: unit roundoff of the stored output (2^-8 bf16, 2^-11 f16, 0 when the kernel writes fp32);
+* ``S``: the same linear operation on absolute values (sum of |a*b| over the element's products, + |bias|);
+* ``b``: the fp32 accumulation term of the element's summation chain (below);
+* ``eta``: the smallest normal number of the output format -- covers rounding (or flushing) at the underflow edge.
+
+Operands are bf16 values inside f16's normal range, so every product of two of them is exact in fp32 (8 + 8 or 11 + 11
+significand bits <= 24) and only the additions round.
+
+The accumulation term ``b``
+---------------------------
+The worst-case form gamma_L = L * 2^-24 is rigorous for any summation order but grows with the chain length L: for the
+weight gradients at 512 x 1024 (L = 524288 pixels) it is 0.031 * S, about 14 times a typical |ref| of random operands
+(|ref| ~ sqrt(L) * rms(ab), S = L * E|ab|), which no fault could exceed.  Even the random-walk bound below is ~16 % of a
+typical |ref| there: at that size it catches gross faults only; the fault tests (test_kernel_bounds_cpu.py) show what
+it rejects at a 99k-pixel weight gradient.  The bf16 / f16 MFMA's
+own accumulation has not been measured here (the f32-input MFMA is a round-to-nearest fma chain with error
+~3.5e-7 * S at K = 4096, i.e. 0.09 * sqrt(K) * 2^-24 * S).  We therefore use the random-walk form
+
+    b = C_RW * sqrt(L) * 2^-24,   C_RW = 8,
+
+with L the longest chain the kernel's tiling gives (``chain_*`` below).  C_RW is fixed before any comparison: a
+round-to-nearest chain over random operands stays near 0.1 * sqrt(L) * 2^-24 * S (the f32 MFMA figure), and even a
+chain that truncated at every addition (errors of one sign, 2^-23 each, on partial sums that grow like sqrt(k))
+accumulates ~2 * sqrt(L) * 2^-24 * S, four times inside the bound.  The form is for random operands (what these tests
+draw); it is not a worst case over adversarial data.
+"""
+import math
+
+import numpy as np
+
+U32 = 2.0 ** -24
+C_RW = 8.0
+U_OUT = {"bf16": 2.0 ** -8, "f16": 2.0 ** -11, "f32": 0.0}
+ETA = {"bf16": 2.0 ** -126, "f16": 2.0 ** -14, "f32": 2.0 ** -126}
+MAX_SPLIT = 256                # weight gradients: at most 256 pixel splits added in the finish pass (wgrad_mfma.hip)
+MAX_TILE_PIXELS = 256          # statistics rows: one per pixel tile of at most 256 pixels (conv_mfma.hip tile_pixels)
+
+
+def b_rw(chain):
+    return C_RW * math.sqrt(chain) * U32
+
+
+def chain_fwd(desc):
+    """Forward-type launches: K = Cin * taps products (the split-K form adds its two partials: + 1), + bias (+ 1)."""
+    taps = desc["kh"] * desc["kw"]
+    return desc["Cin"] * taps + 2
+
+
+def chain_wgrad(desc):
+    """Weight gradients: one product per output pixel of the batch, split over at most MAX_SPLIT segments whose fp32
+    partial sums the finish pass adds (+ the base of the accumulating form)."""
+    return desc["N"] * desc["Hout"] * desc["Wout"] + MAX_SPLIT + 1
+
+
+def bound(ref, S, fmt, chain):
+    u = U_OUT[fmt]
+    return u * np.abs(ref) + (1.0 + u) * b_rw(chain) * S + ETA[fmt]
+
+
+def check(got, ref, S, fmt, chain):
+    """(ok, worst err/bound ratio, index of the worst element, count over the bound).  Non-finite values fail."""
+    got = np.asarray(got, dtype=np.float64)
+    bnd = bound(ref, S, fmt, chain)
+    if not np.isfinite(got).all():
+        return False, math.inf, int(np.argmin(np.isfinite(got).ravel())), int((~np.isfinite(got)).sum())
+    r = np.abs(got - ref) / bnd
+    i = int(np.argmax(r))
+    over = int((r > 1.0).sum())
+    return over == 0, float(r.ravel()[i]), i, over
+
+
+def stats_terms(ref, S, chain):
+    """Per-pixel terms of the statistics-row check.  ``ref``/``S`` [P, C] fp64.  The kernel sums fp32 outputs v
+    (|v - ref| <= e = b * S) over the at most MAX_TILE_PIXELS pixels of a row, and squares them for the second half:
+      |sum v   - sum ref  | <= sum e + b_t * sum (|ref| + e)
+      |sum v^2 - sum ref^2| <= sum e (2 |ref| + e) + b_t * sum (|ref| + e)^2,   b_t = b_rw(MAX_TILE_PIXELS + 3)
+    (+3: the square's rounding and the four per-wave partials).  Returns (ref, ref^2, bound_sum, bound_sq) [P, C],
+    to be summed over each row's pixels."""
+    e = b_rw(chain) * S
+    bt = b_rw(MAX_TILE_PIXELS + 3)
+    a = np.abs(ref) + e
+    return ref, ref * ref, e + bt * a, e * (2 * np.abs(ref) + e) + bt * a * a
+
+
+def check_stats(got, acc):
+    """got [R, 2, C] statistics rows (fp64), acc = the four stats_terms summed per row.  -> (ok, worst ratio)."""
+    rs, rq, bs, bq = acc
+    if not np.isfinite(got).all():
+        return False, math.inf
+    ratio = max((np.abs(got[:, 0] - rs) / bs).max(), (np.abs(got[:, 1] - rq) / bq).max())
+    return bool(ratio <= 1.0), float(ratio)
