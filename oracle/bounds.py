@@ -95,3 +95,61 @@ def check_stats(got, acc):
         return False, math.inf
     ratio = max((np.abs(got[:, 0] - rs) / bs).max(), (np.abs(got[:, 1] - rq) / bq).max())
     return bool(ratio <= 1.0), float(ratio)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Non-convolution entry points of the window (tests/test_window_ops_gpu.py, oracle/window_ops_ref.py).  Constants fixed
+# before any comparison:
+#
+# * short fp32 sums of L terms (reflect folds, the xexpand adjoint, 3x3 pooling, the 8-MAC flow up-sampler, the KH + 1
+#   terms of head_finish): the worst case gamma_L = L * 2^-24 (rigorous for any order), then the output rounding:
+#       |got - ref| <= u_out |ref| + (1 + u_out) gamma_L S + eta                                   (bound_sum)
+# * activations (head_finish): the pre-activation error propagates through |f'(pre)|, and the device tanhf / expf add
+#   their own error.  That ulp error was NOT measured on gfx950; C_ACT = 4 ulps of fp32 (2^-23 each) is a margin over
+#   the few ulps such implementations promise; the sigmoid's 1/(1 + e) adds two roundings, counted in C_ACT too.
+#       |got - ref| <= |f'(pre)| gamma_{KH+1} S_pre + (C_ACT * 2^-23 + 2^-24) |ref| + eta_f32          (bound_act)
+# * long deterministic reductions (head_finish_bwd / thin_grad_expand bias gradients, loss slots): the random-walk term
+#   above with the kernel's chain, plus c_term roundings (2^-24 each) in forming each summand:
+#       |got - ref| <= u_out |ref| + (1 + u_out) (c_term 2^-24 + b_rw(chain)) S + eta             (bound_rw)
+# * bilinear sampling (warp_blend): the sampling coordinate ix = ((gx + 1) W - 1) / 2 is formed in fp32 from
+#   gx = linspace(-1, 1, W)[x] + flow / ((W - 1) / 2), |gx| <= ~2: about ten roundings of magnitude <= 2 in gx
+#   (the linspace step and product, the division, the sum), scaled by W / 2, and three more of magnitude <= 3 W / 2
+#   in the unnormalisation.  DELTA_COORD = 16 rounds that to  delta = 16 * 2^-24 * (W + 1)  (1.0e-3 at W = 1024).
+#   The value error is |d out / d ix| delta_x + |d out / d iy| delta_y on top of C_AR = 8 roundings of the arithmetic
+#   (products of the four weights, the blend) over S.
+C_ACT = 4.0
+C_AR = 8.0
+DELTA_COORD = 16.0
+
+
+def gamma(L):
+    return L * U32
+
+
+def coord_delta(n):
+    return DELTA_COORD * U32 * (n + 1)
+
+
+def bound_sum(ref, S, fmt, terms):
+    u = U_OUT[fmt]
+    return u * np.abs(ref) + (1.0 + u) * gamma(terms) * S + ETA[fmt]
+
+
+def bound_act(ref, slope, S_pre, terms):
+    return slope * gamma(terms) * S_pre + (C_ACT * 2 * U32 + U32) * np.abs(ref) + ETA["f32"]
+
+
+def bound_rw(ref, S, fmt, chain, c_term):
+    u = U_OUT[fmt]
+    return u * np.abs(ref) + (1.0 + u) * (c_term * U32 + b_rw(chain)) * S + ETA[fmt]
+
+
+def check_bound(got, ref, bnd):
+    """check() against a precomputed per-element bound: (ok, worst ratio, index of the worst, count over)."""
+    got = np.asarray(got, dtype=np.float64)
+    if not np.isfinite(got).all():
+        return False, math.inf, int(np.argmin(np.isfinite(got).ravel())), int((~np.isfinite(got)).sum())
+    r = np.abs(got - ref) / bnd
+    i = int(np.argmax(r))
+    over = int((r > 1.0).sum())
+    return over == 0, float(r.ravel()[i]), i, over
