@@ -25,7 +25,14 @@ FlowNet (pretrained checkpoint = a download) is replaced by tests/golden/window_
 
 Weights are never stored: both trees are built from the same seed and asserted bit-identical here.
 
-    python tests/golden/make_window_goldens.py [flownet] [losses] [window]
+``flownetc`` (a12, unstubbed) imports ``models.flownet2_pytorch.networks.FlowNetC`` and ``models.flownet2_pytorch.models``
+themselves, with empty stand-ins registered for the three CUDA extension modules they import; on the built instances
+``.corr`` / ``.resample`` / ``.channelnorm`` are replaced by oracle/closed_form.py (pinned by tests/test_oracle_ops.py),
+both sides are tamed and FlowNetC's feature tower is scaled (window_stub.gain_flownetc), and everything runs in
+float64.  Those goldens hold no inputs: tests/golden/window_stub.py:moving_pair rebuilds them, and
+a checksum is stored.  Written with a fixed zip timestamp, so a second run reproduces them byte for byte.
+
+    python tests/golden/make_window_goldens.py [flownet] [losses] [window] [flownetc]
 """
 import os
 import sys
@@ -48,7 +55,7 @@ from models.flownet2_pytorch.networks import FlowNetFusion as ref_fusion   # noq
 from models.flownet2_pytorch.networks import FlowNetS as ref_s             # noqa: E402
 from models.flownet2_pytorch.networks import FlowNetSD as ref_sd           # noqa: E402
 
-from window_stub import smooth, stub_flow_and_conf, stub_flownetc          # noqa: E402
+from window_stub import gain_flownetc, moving_pair, pair_checksum, smooth, stub_flow_and_conf, stub_flownetc   # noqa: E402
 
 from ir2rgb_amd import networks as mine                                    # noqa: E402
 from ir2rgb_amd.flownet2_pytorch import models as mine_fn                  # noqa: E402
@@ -674,11 +681,161 @@ def window_case(tag, n_windows, H, W, no_first_img=False, n_scales_spatial=1, ng
                         floor_windows=floor_windows, no_first_img=no_first_img, n_scales_spatial=n_scales_spatial, **out)
 
 
+# ------------------------------------------------------------------------------------------------
+# a12, unstubbed: FlowNetC and FlowNet2.forward with FlowNetC in place, in float64
+# ------------------------------------------------------------------------------------------------
+FLOWNETC_SEED, FLOWNET2_SEED = 35, 36
+FLOWNETC_CASES = {"a": (1, 64, 128), "b": (2, 128, 192), "c": (1, 512, 1024)}             # (N, H, W)
+FLOWNET2_CASES = {"a": (1, 64, 128), "b": (1, 80, 128), "c": (3, 128, 192), "d": (1, 512, 1024)}
+
+
+def savez_fixed(path, **arrays):
+    """np.savez_compressed with a fixed member timestamp (np.savez stamps the current time): reproducible bytes."""
+    import io
+    import zipfile
+    with zipfile.ZipFile(path, "w", compression=zipfile.ZIP_DEFLATED) as z:
+        for k, v in arrays.items():
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asanyarray(v), allow_pickle=False)
+            info = zipfile.ZipInfo(k + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            z.writestr(info, buf.getvalue())
+
+
+class ClosedCorr(nn.Module):
+    """Correlation(pad_size=20, kernel_size=1, max_displacement=20, stride1=1, stride2=2) (FlowNetC.py:31)."""
+
+    def forward(self, a, b):
+        return closed_form.correlation(a, b, 20, 1, 20, 1, 2)
+
+
+class ClosedResample(nn.Module):
+    def forward(self, img, flow):
+        return closed_form.resample2d(img.contiguous(), flow)
+
+
+class ClosedChannelNorm(nn.Module):
+    def forward(self, x):
+        return closed_form.channelnorm(x)
+
+
+def _ref_flownet_modules():
+    """The reference's FlowNetC module and models module, imported with empty stand-ins for the CUDA extensions."""
+    import types
+    for name in ("correlation_cuda", "resample2d_cuda", "channelnorm_cuda"):
+        sys.modules.setdefault(name, types.ModuleType(name))
+    from models.flownet2_pytorch import models as ref_models
+    from models.flownet2_pytorch.networks import FlowNetC as ref_flownetc
+    return ref_flownetc, ref_models
+
+
+def _key_shapes(m):
+    sd = m.state_dict()
+    return np.array(list(sd.keys())), np.array(["x".join(str(d) for d in v.shape) for v in sd.values()])
+
+
+def ref_flownetc(seed):
+    ref_c, _ = _ref_flownet_modules()
+    args = _Args()
+    args.rgb_max, args.fp16, args.grads = 1, False, {}
+    torch.manual_seed(seed)
+    r = ref_c.FlowNetC(args, batchNorm=False)
+    torch.manual_seed(seed)
+    assert_same_init(r, mine_fn.FlowNetC())
+    r.corr = ClosedCorr()
+    return gain_flownetc(_tame(r)).double().train()       # train(): flow2..flow6 (no BatchNorm / dropout: the same values as eval)
+
+
+def ref_flownet2(seed):
+    """Seeded as vid2vid.FlowNet(seed=...) seeds the product: torch.manual_seed(seed) right before the constructor."""
+    _, ref_m = _ref_flownet_modules()
+    torch.manual_seed(seed)
+    r = ref_m.FlowNet2()
+    torch.manual_seed(seed)
+    assert_same_init(r, mine_fn.FlowNet2())
+    r.flownetc.corr, r.resample, r.channelnorm = ClosedCorr(), ClosedResample(), ClosedChannelNorm()
+    gain_flownetc(_tame(r).flownetc)
+    return r.double().eval()
+
+
+def ref_flow_and_conf(f2, im1, im2):
+    """FlowNet.compute_flow_and_conf (flownet.py:38-57) around the reference's own FlowNet2.forward."""
+    old_h, old_w = im1.size()[2], im1.size()[3]
+    new_h, new_w = old_h // 64 * 64, old_w // 64 * 64
+    if old_h != new_h:
+        downsample = torch.nn.Upsample(size=(new_h, new_w), mode="bilinear")
+        upsample = torch.nn.Upsample(size=(old_h, old_w), mode="bilinear")
+        im1, im2 = downsample(im1), downsample(im2)
+    data1 = torch.cat([im1.unsqueeze(2), im2.unsqueeze(2)], dim=2)
+    flow1 = f2(data1)
+    d = im1 - f2.resample(im2, flow1)
+    conf = (torch.sum(d * d, dim=1, keepdim=True) < 0.02).to(flow1.dtype)
+    if old_h != new_h:
+        flow1 = upsample(flow1) * old_h / new_h
+        conf = upsample(conf)
+    return flow1, conf
+
+
+def rounded_flow2(r, x, dt):
+    """The rounding floor: the float64 reference with every conv / ConvTranspose output and the cost volume rounded to
+    ``dt`` (forward hooks), -> flow2."""
+    hooks = [m.register_forward_hook(lambda _m, _i, out: out.to(dt).double())
+             for m in r.modules() if isinstance(m, (nn.Conv2d, nn.ConvTranspose2d, ClosedCorr))]
+    try:
+        return r(x)[0]
+    finally:
+        for h in hooks:
+            h.remove()
+
+
+def flownetc_cases():
+    r = ref_flownetc(FLOWNETC_SEED)
+    keys_c, shapes_c = _key_shapes(r)
+    for tag, (n, h, w) in FLOWNETC_CASES.items():
+        im1, im2 = moving_pair(n, h, w)
+        in_sums, in_samples = pair_checksum(im1, im2)
+        x = torch.cat([im1, im2], 1)
+        with torch.no_grad():
+            flows = r(x)
+            floor = {}
+            for name, dt in (("bf16", torch.bfloat16), ("f16", torch.float16)):
+                rf = rounded_flow2(r, x, dt)
+                floor[name] = ((rf - flows[0]).norm() / flows[0].norm()).item()
+        out = {f"flow{lvl}": f.float().numpy() for lvl, f in zip((2, 3, 4, 5, 6), flows)}
+        savez_fixed(os.path.join(OUT, f"flownetc_{tag}_n{n}_{h}x{w}.npz"), seed=np.int64(FLOWNETC_SEED), n=np.int64(n),
+                    h=np.int64(h), w=np.int64(w), in_sums=in_sums, in_samples=in_samples, floor_bf16=np.float64(floor["bf16"]),
+                    floor_f16=np.float64(floor["f16"]), **out)
+        print("flownetc", tag, (n, h, w), "flow2 |mean|", float(flows[0].abs().mean()), "rounding floor (rel L2 of flow2)",
+              floor, flush=True)
+
+    f2 = ref_flownet2(FLOWNET2_SEED)
+    keys_2, shapes_2 = _key_shapes(f2)
+    savez_fixed(os.path.join(OUT, "flownet2_keys.npz"), flownetc_keys=keys_c, flownetc_shapes=shapes_c,
+                flownet2_keys=keys_2, flownet2_shapes=shapes_2)
+    for tag, (n, h, w) in FLOWNET2_CASES.items():
+        im1, im2 = moving_pair(n, h, w)
+        in_sums, in_samples = pair_checksum(im1, im2)
+        with torch.no_grad():
+            flow, conf = ref_flow_and_conf(f2, im1, im2)
+        rec = dict(seed=np.int64(FLOWNET2_SEED), n=np.int64(n), h=np.int64(h), w=np.int64(w), in_sums=in_sums,
+                   in_samples=in_samples)
+        if h * w > 128 * 192:           # the bench size: flow 4x4 average-pooled, the (binary) mask bit-packed
+            rec["flow_pool4"] = F.avg_pool2d(flow, 4).float().numpy()
+            assert bool(((conf == 0) | (conf == 1)).all())
+            rec["conf_bits"] = np.packbits(conf.numpy().astype(bool).reshape(-1))
+        else:
+            rec["flow"], rec["conf"] = flow.float().numpy(), conf.float().numpy()
+        savez_fixed(os.path.join(OUT, f"flownet2_{tag}_n{n}_{h}x{w}.npz"), **rec)
+        print("flownet2", tag, (n, h, w), "flow |mean|", float(flow.abs().mean()), "conf mean", float(conf.mean()), flush=True)
+
+
 if __name__ == "__main__":
-    what = set(sys.argv[1:]) or {"flownet", "losses", "window"}
+    what = set(sys.argv[1:]) or {"flownet", "losses", "window", "flownetc"}
     torch.set_num_threads(8)
     if "flownet" in what:
         flownet_cases()
+    if "flownetc" in what:
+        flownetc_cases()
     if "losses" in what:
         loss_case(False, 1, "s1")
         loss_case(True, 2, "s2_nofirst")
