@@ -13,7 +13,6 @@ are HIP, as are the backward of the separable head convolutions and of the warp-
 convolution is left on the generator / discriminator path, forward or backward.
 """
 import contextlib
-import ctypes
 import os
 
 import torch
@@ -26,15 +25,8 @@ from . import layers as L
 from . import streamcheck as SC
 from . import stageplan
 
-_DT = {torch.bfloat16: 1, torch.float16: 2}
-_ADJ_DESCS = {}      # adjoint descriptors of strided convolutions (conv_dgrad), one object per geometry
-
-
-def _p(t):
-
-    # (a plain int: accepted by the fastcall bindings and by ctypes' c_void_p parameters alike; a c_void_p object per
-    # argument cost 0.75 us, ten of them per launch)
-    return t.data_ptr() if t is not None else 0
+_DT = C._TORCH2DT
+_ADJ_DESCS = {}      # adjoint descriptors of strided convolutions (dgrad_geometry), one object per geometry
 
 
 def _as_half_nhwc(g, dtype):
@@ -114,11 +106,6 @@ def xexpand_bwd(dxe, cin, w, kw, stride_w, pad_w, pad_mode):
 # ---------------------------------------------------------------------------------------------
 # data gradient = a forward convolution with the adjoint geometry
 # ---------------------------------------------------------------------------------------------
-def _flip_swap(w):
-    """Conv2d weight [Cout,Cin,kh,kw] -> adjoint Conv2d weight [Cin,Cout,kh,kw] (taps reversed)."""
-    return w.permute(1, 0, 2, 3).flip(2, 3)
-
-
 def _compose(f, g):
     if f is None:
         return g
@@ -195,52 +182,53 @@ class _PaddedBN:
             self.bn.running_var.copy_(self.running_var[:c])
 
 
+def dgrad_geometry(spec, x_shape, gy_shape, dtype):
+    """The data gradient of the convolution ``spec`` over an input of ``x_shape`` as a forward launch on the gradient
+    ``gy_shape`` w.r.t. its output: -> (launch descriptor, descriptor the weight is packed for, adjoint packing, fold).
+    ``fold``: the launch writes the gradient of the reflection-PADDED input and fold_reflect follows."""
+    kh, kw = spec["k"]
+    (sh, sw), (ph, pw) = spec["stride"], spec["pad"]
+    n, cin, hin, win = x_shape
+    if spec["transposed"]:
+        # forward was ConvTranspose2d(W[cin][cout]); adjoint = Conv2d with the same memory as [out=cin][in=cout]
+        desc = C.make_desc(gy_shape, cin, (kh, kw), (sh, sw), (ph, pw), C.PAD_ZERO, dtype)
+        return desc, desc, False, False
+    if sh == 1 and sw == 1:
+        if spec["pad_mode"] != C.PAD_REFLECT:
+            desc = C.make_desc(gy_shape, cin, (kh, kw), 1, (kh - 1 - ph, kw - 1 - pw), C.PAD_ZERO, dtype)
+            return desc, desc, True, False
+        if (kh, kw, ph, pw) == (3, 3, 1, 1):
+            # the patch-staged kernel evaluates the adjoint of the reflection in place (border terms):
+            # no padded 2-pixel-larger output grid, no fold pass
+            dadj = C.make_desc(gy_shape, cin, 3, 1, 1, C.PAD_REFLECT_ADJ, dtype)
+            if C.kernel_name(dadj) == "conv3x3_patch_kernel":
+                return dadj, C.make_desc(gy_shape, cin, 3, 1, 1, C.PAD_ZERO, dtype), True, False
+        desc = C.make_desc(gy_shape, cin, (kh, kw), 1, (kh - 1, kw - 1), C.PAD_ZERO, dtype)
+        return desc, desc, True, True
+    # strided zero-padded convolution: adjoint = transposed convolution reading W as [in=cout][out=cin]
+    if spec["pad_mode"] != C.PAD_ZERO:
+        raise NotImplementedError("data gradient of a strided reflect-padded convolution")
+    hfull, wfull = (gy_shape[2] - 1) * sh - 2 * ph + kh, (gy_shape[3] - 1) * sw - 2 * pw + kw
+    assert 0 <= hin - hfull < sh and 0 <= win - wfull < sw, "adjoint geometry mismatch"
+    key = (n, gy_shape[2], gy_shape[3], gy_shape[1], hin, win, cin, kh, kw, sh, sw, ph, pw, C.PAD_ZERO, 1, _DT[dtype], 0, 0, 0, 0, 0, 0)
+    desc = _ADJ_DESCS.get(key)
+    if desc is None:
+        desc = _ADJ_DESCS[key] = C.sealed(C.ConvDesc(*key))
+    return desc, desc, False, False
+
+
 def conv_dgrad(gy, conv, spec, x_shape, weight_fn=None, tag="dgrad", out=None):
     """gy: grad wrt the convolution output (channels_last half, channels % 64 == 0).  ``weight_fn``
     maps conv.weight to the weight tensor the forward convolution actually used (x-expanded / padded
     forms).  Returns grad wrt the convolution input (channels_last half)."""
-    kh, kw = spec["k"]
-    (sh, sw), (ph, pw) = spec["stride"], spec["pad"]
-    n, cin, hin, win = x_shape
-    dt = gy.dtype
-    if spec["transposed"]:
-        # forward was ConvTranspose2d(W[cin][cout]); adjoint = Conv2d with the same memory as [out=cin][in=cout]
-        desc = C.make_desc(tuple(gy.shape), cin, (kh, kw), (sh, sw), (ph, pw), C.PAD_ZERO, dt)
-        wp = L.packed_weight(conv, desc, weight_fn, tag=tag)
-        dx, _ = C.conv2d_fwd(desc, gy, wp, out=out)
-        return dx
-    if sh == 1 and sw == 1:
-        if spec["pad_mode"] == C.PAD_REFLECT:
-            if (kh, kw, ph, pw) == (3, 3, 1, 1):
-                # the patch-staged kernel evaluates the adjoint of the reflection in place (border terms):
-                # no padded 2-pixel-larger output grid, no fold pass
-                dadj = C.make_desc(tuple(gy.shape), cin, 3, 1, 1, C.PAD_REFLECT_ADJ, dt)
-                if C.kernel_name(dadj) == "conv3x3_patch_kernel":
-                    dpack = C.make_desc(tuple(gy.shape), cin, 3, 1, 1, C.PAD_ZERO, dt)
-                    wp = L.packed_weight(conv, dpack, weight_fn, tag=tag, adjoint=True)
-                    dx, _ = C.conv2d_fwd(dadj, gy, wp, out=out)
-                    return dx
-            desc = C.make_desc(tuple(gy.shape), cin, (kh, kw), 1, (kh - 1, kw - 1), C.PAD_ZERO, dt)
-            wp = L.packed_weight(conv, desc, weight_fn, tag=tag, adjoint=True)
-            dxpad, _ = C.conv2d_fwd(desc, gy, wp)
-            dx = fold_reflect(dxpad, ph, pw) if (ph or pw) else dxpad
-            return dx if out is None else out.copy_(dx)
-        desc = C.make_desc(tuple(gy.shape), cin, (kh, kw), 1, (kh - 1 - ph, kw - 1 - pw), C.PAD_ZERO, dt)
-        wp = L.packed_weight(conv, desc, weight_fn, tag=tag, adjoint=True)
-        dx, _ = C.conv2d_fwd(desc, gy, wp, out=out)
-        return dx
-    # strided zero-padded convolution: adjoint = transposed convolution reading W as [in=cout][out=cin]
-    if spec["pad_mode"] != C.PAD_ZERO:
-        raise NotImplementedError("data gradient of a strided reflect-padded convolution")
-    hfull, wfull = (gy.shape[2] - 1) * sh - 2 * ph + kh, (gy.shape[3] - 1) * sw - 2 * pw + kw
-    key = (n, gy.shape[2], gy.shape[3], gy.shape[1], hin, win, cin, kh, kw, sh, sw, ph, pw, C.PAD_ZERO, 1, _DT[dt], 0, 0, 0, 0, 0, 0)
-    desc = _ADJ_DESCS.get(key)
-    if desc is None:
-        desc = _ADJ_DESCS[key] = C.sealed(C.ConvDesc(*key))
-    assert 0 <= hin - hfull < sh and 0 <= win - wfull < sw, "adjoint geometry mismatch"
-    wp = L.packed_weight(conv, desc, weight_fn, tag=tag)
-    dx, _ = C.conv2d_fwd(desc, gy, wp, out=out)
-    return dx
+    desc, dpack, adjoint, fold = dgrad_geometry(spec, x_shape, tuple(gy.shape), gy.dtype)
+    wp = L.packed_weight(conv, dpack, weight_fn, tag=tag, adjoint=adjoint)
+    if not fold:
+        return C.conv2d_fwd(desc, gy, wp, out=out)[0]
+    dxpad, _ = C.conv2d_fwd(desc, gy, wp)
+    ph, pw = spec["pad"]
+    dx = fold_reflect(dxpad, ph, pw) if (ph or pw) else dxpad
+    return dx if out is None else out.copy_(dx)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -252,6 +240,25 @@ def conv_dgrad(gy, conv, spec, x_shape, weight_fn=None, tag="dgrad", out=None):
 # autograd adopts a tensor that already lives in the buffer and no gather copy precedes the all-reduce.  Only sound for
 # a parameter that receives ONE contribution per backward pass (the caller's promise: vid2vid.FlatGrads(direct=True)).
 GRAD_SINKS = {}
+
+
+def wgrad_destination(weight, shape):
+    """Where the gradient of ``weight`` (a layer running at the parameter's own ``shape``) is written and what autograd is
+    handed for it: -> (out, accumulate, grad).  ``out`` None: a fresh tensor, which is then the gradient."""
+    sink = GRAD_SINKS.get(weight) if GRAD_SINKS else None
+    have = weight.grad
+    if (ACCUMULATE_IN_KERNEL and sink is None and have is not None and have.dtype is torch.float32 and have.is_contiguous()
+            and have.shape == weight.shape):
+        # a later use of the same parameter in this pass (the discriminators see two or three inputs per window): dw is
+        # added to .grad by the kernel's own finish pass; autograd gets nothing to add
+        return have, True, None
+    if sink is None:
+        return None, False, None
+    if tuple(sink.shape) != shape or sink.dtype is not torch.float32 or not sink.is_contiguous():
+        raise ValueError("conv2d_wgrad: out must be a contiguous fp32 tensor of the weight's shape on the inputs' device")
+    # (a NEW tensor object over the sink's memory: autograd adopts a gradient without cloning it only when nobody else
+    # holds the object it is handed)
+    return sink, False, sink.view(shape)
 
 
 def conv_wgrad(x, gy, weight_shape, spec, out=None, accumulate=False):
@@ -452,42 +459,8 @@ class ConvStageFn(Function):
                 vec = torch.empty((4, G, cout_p), dtype=torch.float32, device=y.device)
                 scale, shift, mean, invstd = vec[0], vec[1], vec[2], vec[3]
                 reps = L._STAT_UPDATES        # layers.repeated_forward: an int, or one count per group
-                if not ctx.frozen and bnp is bn and not SC.ENABLED and spec["training"]:
-                    # the same per-group launches as the loop below, addressed by offset: no slices, no per-group wrappers
-                    # (3 groups x 12 BatchNorm stages per window: ~7 tensor views and ~10 us of Python per group)
-                    lib, stream = _lib.lib(), _lib.current_stream(y)
-                    _, pw, pb, prm, prv, has_rm, momentum, eps, trs = L._bn_ptrs(bn)
-                    track = trs and has_rm
-                    py, pz, ps, pv = y.data_ptr(), z.data_ptr(), stats.data_ptr(), vec.data_ptr()
-                    npix_g = count // G
-                    per_y, per_s, c4 = npix_g * cout_p * y.element_size(), rg * 2 * cout_p * 4, cout_p * 4
-                    gc4, act_, dtc = G * c4, spec["act"], _DT[y.dtype]
-                    fuse_g = fused and rg <= L.FUSED_BN_MAX_ROWS
-                    for g in (spec.get("group_order") or range(G)):
-                        r = reps[g] if isinstance(reps, tuple) else reps
-                        sc = pv + g * c4
-                        if fuse_g:
-                            rc = lib.ir2rgb_bn_finalize_apply(ps + g * per_s, rg, cout_p, npix_g, pw, pb, bias, prm if track else None,
-                                                              prv if track else None, momentum, eps, sc, sc + gc4, sc + 2 * gc4,
-                                                              sc + 3 * gc4, r, py + g * per_y, None, None, pz + g * per_y, npix_g,
-                                                              act_, dtc, stream)
-                            if rc:
-                                _lib.check(rc, "bn_finalize_apply")
-                        else:
-                            rc = lib.ir2rgb_bn_finalize_ex(ps + g * per_s, rg, cout_p, npix_g, pw, pb, bias, prm if track else None,
-                                                           prv if track else None, momentum, eps, sc, sc + gc4, sc + 2 * gc4,
-                                                           sc + 3 * gc4, r, 0, stream)
-                            if rc:
-                                _lib.check(rc, "bn_finalize")
-                            rc = lib.ir2rgb_bn_apply(py + g * per_y, sc, sc + gc4, None, None, pz + g * per_y, npix_g, cout_p, act_, dtc,
-                                                     stream)
-                            if rc:
-                                _lib.check(rc, "bn_apply")
-                        if track and bn.num_batches_tracked is not None:
-                            L._PENDING_COUNTERS.append((bn.num_batches_tracked, r))
-                    G = 0       # (done: the loop below is empty)
                 try:
-                    for g in ((spec.get("group_order") or range(G)) if G else ()):      # (the order the running statistics advance in)
+                    for g in (spec.get("group_order") or range(G)):      # (the order the running statistics advance in)
                         L._STAT_UPDATES = reps[g] if isinstance(reps, tuple) else reps
                         yg, zg = y[g * ng:(g + 1) * ng], z[g * ng:(g + 1) * ng]
                         sg = None if ctx.frozen else stats[g * rg:(g + 1) * rg]
@@ -514,19 +487,10 @@ class ConvStageFn(Function):
     @staticmethod
     def backward(ctx, gz):
         plan = ctx.plan
-        if plan is not None:
-            conv = ctx.conv
-            if not SC.ENABLED and (plan.groups > 1 or (not getattr(conv, "_ir2rgb_bwd", 0) and
-                                                        getattr(conv, "_ir2rgb_active", None) is None)):
-                return plan.backward(ctx, gz)       # (a grouped plan handles the backward flags itself)
-            # backward flags on a planned stage (a discriminator run without sample groups): the general code below
-            xin, y, vec = ctx.saved_tensors
-            scale, shift, mean, invstd = vec.unbind(0)
-            spec = plan.spec
-            ctx.wfn, ctx.frozen, ctx.x_shape, ctx.has_bn = None, False, plan.x_shape, True
-        else:
-            spec, conv = ctx.spec, ctx.conv
-            xin, y, scale, shift, mean, invstd = ctx.saved_tensors
+        if plan is not None:        # (the plan honours the backward flags and inactive sample groups itself)
+            return plan.backward(ctx, gz)
+        spec, conv = ctx.spec, ctx.conv
+        xin, y, scale, shift, mean, invstd = ctx.saved_tensors
         hdt = xin.dtype
         pad_fn = wfn = ctx.wfn
         cout, cin = conv.out_channels, conv.in_channels
@@ -555,29 +519,6 @@ class ConvStageFn(Function):
             act = spec["act"] | (16 if ctx.frozen else 0)
             if scale.dim() == 1:
                 gy, dgamma, dbeta = bn_bwd(gz, y, scale, shift, mean, invstd, act)
-            elif not ctx.frozen and not SC.ENABLED and gz.is_contiguous(memory_format=torch.channels_last):
-                # sample groups, addressed by offset (the launches of the loop in the next branch, without its slices and
-                # per-group wrappers; one partial-row region serves all groups: same stream, one group after the other)
-                G = scale.shape[0]
-                ng, ch = y.shape[0] // G, y.shape[1]
-                npix_g = ng * y.shape[2] * y.shape[3]
-                lib, stream = _lib.lib(), _lib.current_stream(y)
-                nblk = lib.ir2rgb_bn_bwd_blocks(npix_g, ch)
-                if nblk < 0:
-                    _lib.check(nblk, "bn_bwd_blocks")
-                gy = torch.empty_like(y, memory_format=torch.channels_last)
-                buf = torch.empty((nblk * 2 + 5) * ch, dtype=torch.float32, device=y.device)
-                dgamma, dbeta = buf[:ch], buf[ch:2 * ch]
-                pb_, c4 = buf.data_ptr(), ch * 4
-                per = npix_g * ch * y.element_size()
-                pg, py_, pgy = gz.data_ptr(), y.data_ptr(), gy.data_ptr()
-                psc, psh, pmu, piv = scale.data_ptr(), shift.data_ptr(), mean.data_ptr(), invstd.data_ptr()
-                dtc = _DT[y.dtype]
-                for g in range(G):
-                    rc = lib.ir2rgb_bn_bwd(pg + g * per, py_ + g * per, psc + g * c4, psh + g * c4, pmu + g * c4, piv + g * c4,
-                                           pgy + g * per, pb_, pb_ + c4, pb_ + 2 * c4, npix_g, ch, act | (32 if g else 0), dtc, stream)
-                    if rc:
-                        _lib.check(rc, "bn_bwd")
             else:                       # sample groups: per-group BatchNorm backward into the batch's gradient tensor
                 G = scale.shape[0]
                 ng = y.shape[0] // G
@@ -646,15 +587,13 @@ class ConvStageFn(Function):
                         return (g[:cin, :cout] if spec["transposed"] else g[:cout, :cin]).contiguous()
                     dw = wgrad_overlapped(conv, padded_wgrad, xin, gy)
                 else:
-                    sink = GRAD_SINKS.get(conv.weight) if GRAD_SINKS else None
-                    have = conv.weight.grad
-                    if (ACCUMULATE_IN_KERNEL and sink is None and have is not None and have.dtype == torch.float32
-                            and have.is_contiguous() and have.shape == conv.weight.shape):
-                        # a later use of the same parameter in this pass (the discriminators see two or three inputs per
-                        # window): dw is added to .grad by the kernel's own finish pass; autograd gets nothing to add
-                        conv_wgrad(xin, gy, tuple(conv.weight.shape), spec, out=have, accumulate=True)
+                    wsh = tuple(conv.weight.shape)
+                    out, acc, dw = wgrad_destination(conv.weight, wsh)
+                    if acc:
+                        conv_wgrad(xin, gy, wsh, spec, out=out, accumulate=True)
                     else:
-                        dw = wgrad_overlapped(conv, lambda: conv_wgrad(xin, gy, tuple(conv.weight.shape), spec, out=sink), xin, gy)
+                        # (conv2d_wgrad hands back the fresh tensor, or its own new view of the sink)
+                        dw = wgrad_overlapped(conv, lambda: conv_wgrad(xin, gy, wsh, spec, out=out), xin, gy)
         r1 = gz if ctx.has_res[0] else None
         r2 = gz if ctx.has_res[1] else None
         if wfn is not None:      # reference-shaped parameter gradients

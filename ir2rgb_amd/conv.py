@@ -156,6 +156,16 @@ def stats_rows(desc):
     return r
 
 
+def fwd_workspace_bytes(desc):
+    """Bytes of workspace ir2rgb_conv2d_fwd_ws wants for ``desc`` (0: none), asked once per descriptor."""
+    n = getattr(desc, "_ws_bytes", None)         # (descriptors are built once per layer and shape and never edited)
+    if n is None:
+        n = desc._ws_bytes = int(_lib.lib().ir2rgb_conv2d_fwd_workspace_bytes(desc))
+        if n < 0:
+            _lib.check(n, "conv2d_fwd_workspace_bytes")
+    return n
+
+
 # Optional per-launch timing (bench.py's roofline leg): when PROFILE is a dict, convolutions are
 # bracketed by HIP events on the stream they are launched on and tallied by shape -- every shape, or
 # only PROFILE["only"] when that key is set (an event pair costs a queue marker, so the timed region
@@ -210,11 +220,7 @@ _SPLIT_WS = {}
 
 
 def _fwd_workspace(desc, x):
-    n = getattr(desc, "_ws_bytes", None)         # (descriptors are built once per layer and shape and never edited)
-    if n is None:
-        n = desc._ws_bytes = int(_lib.lib().ir2rgb_conv2d_fwd_workspace_bytes(desc))
-        if n < 0:
-            _lib.check(n, "conv2d_fwd_workspace_bytes")
+    n = fwd_workspace_bytes(desc)
     if n == 0:
         return None, 0
     if torch.cuda.is_current_stream_capturing():

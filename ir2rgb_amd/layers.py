@@ -22,7 +22,7 @@ from . import conv as C
 from . import streamcheck as SC
 
 ACT_NONE, ACT_RELU, ACT_LEAKY = 0, 1, 2
-_DT = {torch.bfloat16: 1, torch.float16: 2}
+_DT = C._TORCH2DT
 
 
 def _p(t):

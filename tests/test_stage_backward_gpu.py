@@ -242,11 +242,13 @@ def test_planned_stage_equals_the_general_stage(dev, dtype, case):
     (64, 33, 65, 128, 4, 2, 2, 3, (2, 0, 1), 2),      # image discriminator layer: three groups, the generator's pass on two
     (128, 17, 33, 256, 4, 1, 2, 2, (1, 0), 1),        # temporal discriminator layer, stride 1: two groups, one active
     (64, 70, 200, 128, 4, 2, 2, 3, None, 2),          # > 128 statistics rows per group: finalize + apply launches
+    (64, 33, 65, 128, 4, 2, 2, 1, None, 1),           # ungrouped (a discriminator run without sample groups) under the flags
 ])
 def test_planned_grouped_stage_equals_the_general_stage(dev, dtype, case):
-    """stageplan.GroupedStagePlan (batched discriminator stages: BatchNorm per sample group, backward flags, passes with
-    inactive groups) against ConvStageFn's general code: forward, a flagged pass (no parameter gradients, leading groups
-    only) and a full pass (parameter gradients, accumulated in the kernel on top of an earlier one), bit for bit."""
+    """stageplan.StagePlan with sample groups (batched discriminator stages: BatchNorm per sample group, backward flags,
+    passes with inactive groups) against ConvStageFn's general code: forward, a flagged pass (no parameter gradients,
+    leading groups only) and a full pass (parameter gradients, accumulated in the kernel on top of an earlier one), bit for
+    bit.  The last case is an ungrouped planned stage under the same flags."""
     import copy
     from ir2rgb_amd import autograd as A, conv as C, layers as L, stageplan
     cin, h, w, cout, k, s, p, G, order, active = case
@@ -266,7 +268,7 @@ def test_planned_grouped_stage_equals_the_general_stage(dev, dtype, case):
             outs = []
             for rep in range(2):
                 x = x0.clone().requires_grad_(True)
-                with L.repeated_forward(tuple(range(1, G + 1))):
+                with L.repeated_forward(tuple(range(1, G + 1)) if G > 1 else 2):
                     z = A.conv_stage(x, conv, bn, L.ACT_LEAKY, C.PAD_ZERO, dtype, groups=G, group_order=order, training=True)
                 L.flush_bn_counters()
                 g = torch.randn(z.shape, generator=torch.Generator().manual_seed(7 + rep)).to(dev).to(dtype).contiguous(
@@ -282,7 +284,8 @@ def test_planned_grouped_stage_equals_the_general_stage(dev, dtype, case):
                 outs += [z.detach().clone(), dx_part, x.grad.clone()]
             outs += [conv.weight.grad.clone(), bn.weight.grad.clone(), bn.bias.grad.clone(), bn.running_mean.clone(),
                      bn.running_var.clone(), bn.num_batches_tracked.clone()]
-            planned = any(isinstance(v, stageplan.GroupedStagePlan) for v in conv.__dict__.get("_ir2rgb_plans", {}).values())
+            plans = [v for v in conv.__dict__.get("_ir2rgb_plans", {}).values() if v]
+            planned = bool(plans) and all(v.groups == G for v in plans)       # (G > 1 in every case but the last)
             assert planned == lean
             results.append(outs)
         finally:

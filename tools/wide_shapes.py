@@ -17,9 +17,7 @@ SHAPES = [  # Cin, Hin, Win, Cout, k, stride, pad, pad_mode, transposed, opad, o
 ]
 for cin, h, w, cout, k, st, pad, pm, tr, opad, f32 in SHAPES:
     x = torch.randn(1, cin, h, w, device=dev).to(dt).contiguous(memory_format=torch.channels_last)
-    d = C.make_desc(tuple(x.shape), cout, k, st, pad, pm, dt, tr, opad)
-    if f32:
-        d.out_f32 = 1
+    d = C.make_desc(tuple(x.shape), cout, k, st, pad, pm, dt, tr, opad, out_f32=f32)
     wt = torch.randn((cin, cout) + k if tr else (cout, cin) + k, device=dev) * 0.02
     wp = C.pack_weight(d, wt)
     for _ in range(3):
