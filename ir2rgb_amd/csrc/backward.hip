@@ -502,6 +502,7 @@ bn_bwd_onepass_kernel(const uint4 *__restrict__ gz, const uint4 *__restrict__ y,
     // Workgroups whose channel groups share 128-byte lines (64 / CPB neighbours) go to ONE XCD (blockIdx % 8 under
     // round-robin placement): each L2 then fetches a line once and merges the 16-byte stores into whole lines, instead
     // of eight L2s fetching and partially writing every line (speed only: any placement gives the same result).
+    // (xcd_remap is always 1; the argument stays because hipcc schedules the kernel differently without it)
     const int G = gridDim.x;
     const int grp = xcd_remap && (G & 7) == 0 ? (int)(blockIdx.x & 7) * (G >> 3) + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
     const int c0 = grp * CPB + oc * 8, C8 = C >> 3;
@@ -584,9 +585,7 @@ template <int CPB>
 static bool bn_bwd_onepass_launch(int K, dim3 grid, hipStream_t s, const uint4 *gz, const uint4 *y, const float *scale,
                                   const float *shift, const float *mean, const float *invstd, uint4 *gy, float *dgamma,
                                   float *dbeta, long npix, int C, int act, int dt, float inv_n, int acc) {
-    static int remap = -1;          // IR2RGB_BN_BWD_XCD=0: channel group = blockIdx (A/B measurements)
-    if (remap < 0) { const char *e = getenv("IR2RGB_BN_BWD_XCD"); remap = e ? atoi(e) : 1; }
-#define IR2RGB_ONEPASS(KK) bn_bwd_onepass_kernel<KK, CPB><<<grid, 512, 0, s>>>(gz, y, scale, shift, mean, invstd, gy, dgamma, dbeta, npix, C, act, dt, inv_n, acc, remap)
+#define IR2RGB_ONEPASS(KK) bn_bwd_onepass_kernel<KK, CPB><<<grid, 512, 0, s>>>(gz, y, scale, shift, mean, invstd, gy, dgamma, dbeta, npix, C, act, dt, inv_n, acc, 1)
     if (K <= 4) IR2RGB_ONEPASS(4);
     else if (K <= 8) IR2RGB_ONEPASS(8);       // (K = 12 would need scratch: 256 registers are gone at K = 9)
     else return false;
@@ -618,18 +617,14 @@ extern "C" int ir2rgb_bn_bwd(const void *gz, const void *y, const float *scale, 
     // 8 channels per workgroup while that gives at most 8 loads per tensor and thread, else not applicable; wider
     // groups (better coalescing, fewer workgroups) when the layer still yields >= 128 workgroups.
     {
-        static int onepass = -1;
-        if (onepass < 0) { const char *e = getenv("IR2RGB_BN_BWD_ONEPASS"); onepass = e ? atoi(e) : 1; }
-        if (onepass && scale && shift && mean && invstd && !frozen && npix <= 8 * 512) {
+        if (scale && shift && mean && invstd && !frozen && npix <= 8 * 512) {
             const float inv_n = 1.0f / (float)npix;
             bool done;
-            static int force_cpb = -1;      // IR2RGB_BN_BWD_ONEPASS_CPB=8|16|32: A/B measurements
-            if (force_cpb < 0) { const char *e = getenv("IR2RGB_BN_BWD_ONEPASS_CPB"); force_cpb = e ? atoi(e) : 0; }
-            const int min_wg = force_cpb ? 1 : 128;
-            if ((!force_cpb || force_cpb == 32) && C / 32 >= min_wg && npix * 4 <= 8 * 512)
+            const int min_wg = 128;
+            if (C / 32 >= min_wg && npix * 4 <= 8 * 512)
                 done = bn_bwd_onepass_launch<32>((int)((npix * 4 + 511) / 512), dim3(C / 32), s, (const uint4 *)gz, (const uint4 *)y, scale, shift,
                                                  mean, invstd, (uint4 *)gy, dgamma, dbeta, npix, C, act, dtype, inv_n, acc);
-            else if ((!force_cpb || force_cpb == 16) && C / 16 >= min_wg && npix * 2 <= 8 * 512)
+            else if (C / 16 >= min_wg && npix * 2 <= 8 * 512)
                 done = bn_bwd_onepass_launch<16>((int)((npix * 2 + 511) / 512), dim3(C / 16), s, (const uint4 *)gz, (const uint4 *)y, scale, shift,
                                                  mean, invstd, (uint4 *)gy, dgamma, dbeta, npix, C, act, dtype, inv_n, acc);
             else
@@ -642,9 +637,7 @@ extern "C" int ir2rgb_bn_bwd(const void *gz, const void *y, const float *scale, 
     float *coef = partial + (long)R * 2 * C;
     bn_bwd_reduce_kernel<<<R * (C / 64), 512, 0, s>>>((const uint4 *)gz, (const uint4 *)y, scale, shift, mean, invstd,
                                                       partial, npix, C, act, dtype, per);
-    static int fused = -1;
-    if (fused < 0) { const char *e = getenv("IR2RGB_FUSED_BN_BWD"); fused = e ? atoi(e) : 1; }
-    if (fused && scale && shift && mean && invstd) {
+    if (scale && shift && mean && invstd) {
         long chunks = 2048 / (C / 64);
         const long cap = (npix + 127) / 128;
         chunks = chunks < 1 ? 1 : (chunks > cap ? cap : chunks);
@@ -684,12 +677,10 @@ extern "C" int ir2rgb_xexpand_bwd(const void *dxe, float *din, int N, int Cin, i
     long total = (long)N * H * W;
     if (total == 0) return IR2RGB_OK;
     {
-        static int tiled = -1;          // IR2RGB_XEXPAND_BWD_TILED=0: the one-thread-per-pixel kernel (A/B measurements)
-        if (tiled < 0) { const char *e = getenv("IR2RGB_XEXPAND_BWD_TILED"); tiled = e ? atoi(e) : 1; }
         const int xtiles = (W + XB_TW - 1) / XB_TW;
         const long blocks = (long)N * H * xtiles;
         const size_t lds = (size_t)((XB_TW + KW + 2 * pad_w) / stride_w + 3) * XB_PITCH * sizeof(uint32_t);
-        if (tiled && pad_w < XB_TW && blocks <= 0x7fffffffL && lds <= 64 * 1024 && !((uintptr_t)dxe & 15)) {
+        if (pad_w < XB_TW && blocks <= 0x7fffffffL && lds <= 64 * 1024 && !((uintptr_t)dxe & 15)) {
             xexpand_bwd_tile_kernel<<<(unsigned)blocks, 256, lds, as_stream(stream)>>>((const uint4 *)dxe, din, Cin, H, W, Wout, KW,
                                                                                     stride_w, pad_w, pad_mode, xtiles, dtype);
             return ir2rgb_launch_status();

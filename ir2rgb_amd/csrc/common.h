@@ -53,4 +53,56 @@ __device__ __forceinline__ float row16_sum(float v) {
     v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, true));  // row_mirror
     return v;
 }
+
+// ---- shared by the MFMA / LDS-DMA kernels (every .hip file is its own translation unit) ----
+typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
+typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
+typedef __attribute__((ext_vector_type(4))) float f32x4;
+typedef __attribute__((ext_vector_type(4))) short s16x4;
+typedef __attribute__((address_space(3))) void *lptr_t;
+typedef __amdgpu_buffer_rsrc_t rsrc_t;
+
+// element type of the half-precision operands: MFMA fragment, the 16x16x32 MFMA, fp32 -> half conversion
+template <int DT> struct Half;
+template <> struct Half<IR2RGB_BF16> {
+    typedef bf16x8 frag;
+    static __device__ __forceinline__ f32x4 mfma(frag a, frag b, f32x4 c) {
+        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+    }
+    static __device__ __forceinline__ uint16_t cvt(float f) {
+        __bf16 h = (__bf16)f;
+        return __builtin_bit_cast(uint16_t, h);
+    }
+};
+template <> struct Half<IR2RGB_F16> {
+    typedef f16x8 frag;
+    static __device__ __forceinline__ f32x4 mfma(frag a, frag b, f32x4 c) {
+        return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
+    }
+    static __device__ __forceinline__ uint16_t cvt(float f) {
+        _Float16 h = (_Float16)f;
+        return __builtin_bit_cast(uint16_t, h);
+    }
+};
+
+// Buffer-addressed LDS-DMA: 16 B per lane from (SGPR base + per-lane 32-bit byte offset + scalar byte
+// offset) to LDS at wave-uniform base + lane * 16.  The per-lane offset is range-checked against the
+// resource extent and out-of-range lanes deliver ZEROS: zero padding costs no instruction, and the
+// scalar K offset rides in an SGPR, so a K-step's staging issues no VALU address arithmetic at all.
+#define IR2RGB_OOB 0x80000000u  // per-lane offset past any extent (extents are < 2^31)
+__device__ __forceinline__ rsrc_t make_rsrc(const void *p, unsigned bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, (int)bytes, 0x00020000);
+}
+__device__ __forceinline__ void lds_dma16(rsrc_t r, unsigned voff, unsigned soff, lptr_t dst_wave_base) {
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, dst_wave_base, 16, voff, soff, 0, 0);
+}
+__device__ __forceinline__ void lds_dma16(rsrc_t r, unsigned voff, unsigned soff, void *dst_wave_base) {
+    lds_dma16(r, voff, soff, (lptr_t)dst_wave_base);
+}
+
+// index of a reflection-padded coordinate (no edge repeat)
+__device__ __forceinline__ int reflect(int v, int n) {
+    v = v < 0 ? -v : v;
+    return v >= n ? 2 * n - 2 - v : v;
+}
 #endif

@@ -20,27 +20,10 @@
 #include "common.h"
 #include "conv1x7_thin.h"
 
-typedef __attribute__((ext_vector_type(8))) __bf16 t7_bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 t7_f16x8;
-typedef __attribute__((ext_vector_type(4))) float t7_f32x4;
-typedef __attribute__((address_space(3))) void *t7_lptr_t;
-typedef __amdgpu_buffer_rsrc_t t7_rsrc_t;
-#define T7_OOB 0x80000000u
-
-template <int DT> struct T7Half;
-template <> struct T7Half<IR2RGB_BF16> {
-    typedef t7_bf16x8 frag;
-    static __device__ __forceinline__ t7_f32x4 mfma(frag a, frag b, t7_f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-};
-template <> struct T7Half<IR2RGB_F16> {
-    typedef t7_f16x8 frag;
-    static __device__ __forceinline__ t7_f32x4 mfma(frag a, frag b, t7_f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-};
-
 template <int DT, int CIN>
 __global__ void __launch_bounds__(256, 1)
 conv1x7_thin_kernel(const uint16_t *__restrict__ X, const uint16_t *__restrict__ Wp, float *__restrict__ Y, const T7Geom g) {
-    typedef T7Half<DT> Hf;
+    typedef Half<DT> Hf;
     typedef typename Hf::frag frag;
     constexpr int TW = 128, KW = 7, PAD = 3, ROWS = TW + KW - 1;          // 134 staged pixels per segment
     constexpr int NC = CIN / 32;                                          // 32-channel K-steps per tap
@@ -54,8 +37,8 @@ conv1x7_thin_kernel(const uint16_t *__restrict__ X, const uint16_t *__restrict__
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l15 = lane & 15, grp = lane >> 4;
-    const t7_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t *>(X), 0, (int)g.x_bytes, 0x00020000);
-    const t7_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t *>(Wp), 0, (int)g.w_bytes, 0x00020000);
+    const rsrc_t rx = make_rsrc(X, g.x_bytes);
+    const rsrc_t rw = make_rsrc(Wp, g.w_bytes);
 
     // ---- this wave's MFMA A-fragments: rows (row responses) mt*16 + l15, K-step j = kx*NC + c: channels c*32 + grp*8 .. +7 of
     // tap kx.  Packed weights Wp[row][CIN/64][7][64]; rows >= Cout lie behind the resource's extent and read zeros.
@@ -68,7 +51,7 @@ conv1x7_thin_kernel(const uint16_t *__restrict__ X, const uint16_t *__restrict__
             const int row = mt * 16 + l15;
             const unsigned off = (unsigned)((((row * (CIN / 64) + (c >> 1)) * KW + kx) * 64 + (c & 1) * 32 + grp * 8) * 2);
             typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-            const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rw, row < g.Cout ? off : T7_OOB, 0, 0);
+            const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rw, row < g.Cout ? off : IR2RGB_OOB, 0, 0);
             A[j][mt] = __builtin_bit_cast(frag, v);
         }
     }
@@ -95,9 +78,9 @@ conv1x7_thin_kernel(const uint16_t *__restrict__ X, const uint16_t *__restrict__
             xs = xs < 0 ? -xs : xs;
             xs = xs >= g.W ? 2 * g.W - 2 - xs : xs;
             const bool ok = row < ROWS && xs >= 0 && xs < g.W && seg < g.nseg;
-            const unsigned v = ok ? ((rowbase + (unsigned)xs) * (unsigned)g.ldx + (unsigned)g.ci_off + (unsigned)chunk * 8u) * 2u : T7_OOB;
+            const unsigned v = ok ? ((rowbase + (unsigned)xs) * (unsigned)g.ldx + (unsigned)g.ci_off + (unsigned)chunk * 8u) * 2u : IR2RGB_OOB;
             if (4 * q + 3 < NDMA || i < NDMA)                             // (only the last round can run past the segment)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (t7_lptr_t)(smem + buf * SEG + i * 1024), 16, v, 0, 0, 0);
+                lds_dma16(rx, v, 0, smem + buf * SEG + i * 1024);
         }
     };
 
@@ -129,11 +112,11 @@ conv1x7_thin_kernel(const uint16_t *__restrict__ X, const uint16_t *__restrict__
         __builtin_amdgcn_s_barrier();                                     // ... for every wave
         issue(seg + gridDim.x, buf ^ 1);                                  // next segment into the other buffer (no-op rows past the end)
         const unsigned boff = (unsigned)(buf * SEG);
-        t7_f32x4 acc[2][2];
+        f32x4 acc[2][2];
 #pragma unroll
         for (int b = 0; b < 2; ++b)
 #pragma unroll
-            for (int mt = 0; mt < 2; ++mt) acc[b][mt] = (t7_f32x4){0.f, 0.f, 0.f, 0.f};
+            for (int mt = 0; mt < 2; ++mt) acc[b][mt] = (f32x4){0.f, 0.f, 0.f, 0.f};
         frag B[R];
         auto fetch = [&]<int T>(std::integral_constant<int, T>) {
             constexpr int j = T / 2, bb = T % 2, kx = j / NC, c = j % NC;
@@ -180,14 +163,8 @@ conv1x7_thin_kernel(const uint16_t *__restrict__ X, const uint16_t *__restrict__
 // ----------------------------------------------------------------------------------------
 // host side (called from conv_mfma.hip)
 // ----------------------------------------------------------------------------------------
-static bool t7_enabled() {
-    static int v = -1;
-    if (v < 0) { const char *e = getenv("IR2RGB_CONV1X7_THIN"); v = e ? atoi(e) : 1; }
-    return v != 0;
-}
-
 bool conv1x7_thin_plan(const ir2rgb_conv_desc *d, T7Geom *g) {
-    if (!t7_enabled() || d->transposed || d->kh != 1 || d->kw != 7 || d->stride_h != 1 || d->stride_w != 1) return false;
+    if (d->transposed || d->kh != 1 || d->kw != 7 || d->stride_h != 1 || d->stride_w != 1) return false;
     if (d->pad_h != 0 || d->pad_w != 3 || d->pad_mode != 1 || !d->out_f32 || d->act != 0 || d->stats_per_sample) return false;
     if (d->Cout < 1 || d->Cout > 32 || (d->Cin != 64 && d->Cin != 128) || d->Win < 4 || d->Hout != d->Hin || d->Wout != d->Win) return false;
     if (d->dtype != IR2RGB_BF16 && d->dtype != IR2RGB_F16) return false;

@@ -25,63 +25,22 @@
 // conv_igemm_kernel), half outputs staged through LDS and written as 16-byte stores.
 #include <utility>
 
-#include "common.h"
+#include "conv3x3_patch.h"
 
-typedef __attribute__((ext_vector_type(8))) __bf16 p3_bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 p3_f16x8;
-typedef __attribute__((ext_vector_type(4))) float p3_f32x4;
-typedef __attribute__((address_space(3))) void *p3_lptr_t;
-typedef __amdgpu_buffer_rsrc_t p3_rsrc_t;
-#define P3_OOB 0x80000000u
-
-template <int DT> struct P3Half;
-template <> struct P3Half<IR2RGB_BF16> {
-    typedef p3_bf16x8 frag;
-    static __device__ __forceinline__ p3_f32x4 mfma(frag a, frag b, p3_f32x4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-    }
-    static __device__ __forceinline__ uint16_t cvt(float f) { __bf16 h = (__bf16)f; return __builtin_bit_cast(uint16_t, h); }
-};
-template <> struct P3Half<IR2RGB_F16> {
-    typedef p3_f16x8 frag;
-    static __device__ __forceinline__ p3_f32x4 mfma(frag a, frag b, p3_f32x4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-    }
-    static __device__ __forceinline__ uint16_t cvt(float f) { _Float16 h = (_Float16)f; return __builtin_bit_cast(uint16_t, h); }
-};
-
-struct P3Geom {
-    int N, H, W, Ho, Wo, Cin, Cout;   // input / output extents
-    int pad, pad_mode, act;
-    int ldx, ci_off, ldy, co_off;
-    int stats_row0, nty, ntx;         // pixel tiles per image: nty x ntx
-    int cout_major, kchunks;
-    unsigned x_bytes, w_bytes;
-    int dbg;   // ablation switches for timing experiments, honoured only by -DIR2RGB_ABLATION builds (results are garbage): 1 = no staging after the prologue, 2 = no fragment reads
-};
-
-__device__ __forceinline__ int p3_reflect(int v, int n) {
-    v = v < 0 ? -v : v;
-    return v >= n ? 2 * n - 2 - v : v;
-}
-
-// SPS = 32-channel slices per K-step (1 or 2): with 2, a step covers a whole 64-channel chunk at one ky --
-// twice the MFMA work between barriers for the small tile, whose steps are otherwise only 24 MFMAs long.
-template <int TW, int TCO, int NCW, int NLW, int ADJ, int SPS, int TR_ = 2> struct P3Cfg {
+template <int TW, int TCO, int NCW, int NLW, int ADJ, int TR_ = 2> struct P3Cfg {
     static constexpr int TR = TR_, NPX = TR * TW;            // pixel tile: TR rows x TW columns
     static constexpr int PWP = ((TW + 2 + 15) / 16) * 16;   // patch row pitch in entries (80 | 144)
     static constexpr int PROWI = PWP / 16;                   // DMA instructions per patch row
-    static constexpr int NW1 = 3 * TCO / 16, NW = SPS * NW1; // DMA instructions for the weights of one K-step
-    static constexpr int WST1 = 3 * TCO * 64, WST = SPS * WST1;   // bytes per weight stage (per slice, per step)
+    static constexpr int NW = 3 * TCO / 16;                  // DMA instructions for the weights of one K-step
+    static constexpr int WST = 3 * TCO * 64;                 // bytes per weight stage
     static constexpr int PBUF = (TR + 2) * PWP * 64;         // bytes per patch buffer (one slice): TR + 2 haloed rows
-    static constexpr int NSTW = (SPS == 2 || TCO == 128 && (TW == 128 || TR > 2)) ? 3 : 4;
+    static constexpr int NSTW = (TCO == 128 && (TW == 128 || TR > 2)) ? 3 : 4;
     static constexpr int AHEAD = NSTW - 1;
     static constexpr int WM = TCO / 64, WN = NCW / WM, PXW = NPX / WN, NI = PXW / 16;
-    static constexpr int LDS = NSTW * WST + 2 * SPS * PBUF + 1024;
+    static constexpr int LDS = NSTW * WST + 2 * PBUF + 1024;
     // patch rows staged with the step of phase ky: rows {0..TR-1} | {TR} | {TR+1}; reflect-adjoint mode needs every row
     // from the first step on (its border terms read row 2 at ky = 0), so it stages all of them with ky = 0
-    static constexpr int np1(int ky) { return ADJ ? (ky == 0 ? (TR + 2) * PROWI : 0) : (ky == 0 ? TR * PROWI : PROWI); }
-    static constexpr int np(int ky) { return SPS * np1(ky); }
+    static constexpr int np(int ky) { return ADJ ? (ky == 0 ? (TR + 2) * PROWI : 0) : (ky == 0 ? TR * PROWI : PROWI); }
     static constexpr int nl(int ky) { return (NW + np(ky) + NLW - 1) / NLW; }     // DMA instructions per loader wave
     static constexpr int NLMAX = nl(0);
     // DMA instructions a loader wave may leave in flight while step (phase ky) is consumed: the steps staged after it
@@ -92,22 +51,21 @@ template <int TW, int TCO, int NCW, int NLW, int ADJ, int SPS, int TR_ = 2> stru
     }
 };
 
-template <int DT, int TW, int TCO, int NCW, int NLW, int PIPE, int ADJ, int SPS, int SPLIT = 1, int TR = 2>
+template <int DT, int TW, int TCO, int NCW, int NLW, int PIPE, int ADJ, int SPLIT = 1, int TR = 2>
 __global__ void __launch_bounds__((NCW + NLW) * 64, 1)
 conv3x3_patch_kernel(const uint16_t *__restrict__ X, const uint16_t *__restrict__ Wp, const float *__restrict__ bias,
                      uint16_t *__restrict__ Y, float *__restrict__ stats_partial, const P3Geom g,
                      unsigned *tickets = nullptr, float *partials = nullptr) {
     static_assert(SPLIT == 1 || SPLIT == 2, "the hand-over adds two partial tiles (order-independent)");
-    typedef P3Cfg<TW, TCO, NCW, NLW, ADJ, SPS, TR> C;
-    static_assert(SPS == 1 || (PIPE == 1 && !ADJ), "two slices per step: pipelined forward form only");
+    typedef P3Cfg<TW, TCO, NCW, NLW, ADJ, TR> C;
     static_assert(TR == 2 || C::PXW == TW, "taller tiles: one pixel row per multiplying wave");
     static_assert(!(ADJ && PIPE) || C::NI <= 2 || C::PXW % TW == 0,
                   "pipelined reflect-adjoint form: border operands must be prefetched (registers: small tile, or whole pixel rows per wave)");
-    typedef P3Half<DT> Hf;
+    typedef Half<DT> Hf;
     typedef typename Hf::frag frag;
     constexpr int NI = C::NI, MI = 4;
     __shared__ __attribute__((aligned(1024))) unsigned char smem[C::LDS];
-    unsigned char *const wring = smem, *const pbufs = smem + C::NSTW * C::WST, *const dummy = pbufs + 2 * SPS * C::PBUF;
+    unsigned char *const wring = smem, *const pbufs = smem + C::NSTW * C::WST, *const dummy = pbufs + 2 * C::PBUF;
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -129,19 +87,18 @@ conv3x3_patch_kernel(const uint16_t *__restrict__ X, const uint16_t *__restrict_
     else              { pt = tile / nct; ct = tile - pt * nct; }
     const int txi = pt % g.ntx, tyi = (pt / g.ntx) % g.nty, n = pt / (g.ntx * g.nty);
     const int y0 = tyi * C::TR, x0 = txi * TW;
-    const int NK = kcl * (2 / SPS) * 3;         // K-steps: (64-channel chunk, [half,] ky)
+    const int NK = kcl * 2 * 3;                 // K-steps: (64-channel chunk, 32-channel half, ky)
 
-    p3_f32x4 acc[MI][NI];
+    f32x4 acc[MI][NI];
 #pragma unroll
     for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
-        for (int ni = 0; ni < NI; ++ni) acc[mi][ni] = (p3_f32x4){0.f, 0.f, 0.f, 0.f};
+        for (int ni = 0; ni < NI; ++ni) acc[mi][ni] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
     if (loader) {
         // =============================== staging waves ===============================
         const int lw = wave - NCW;
-        const p3_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t *>(Wp), 0, (int)g.w_bytes, 0x00020000);
-        const p3_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t *>(X), 0, (int)g.x_bytes, 0x00020000);
+        const rsrc_t rw = make_rsrc(Wp, g.w_bytes), rx = make_rsrc(X, g.x_bytes);
         const int row16 = lane >> 2;
         // per (phase ky, slot j): instruction id = lw + NLW*j -> weights (id < NW), patch, or padding
         unsigned voff[3][C::NLMAX];
@@ -150,7 +107,7 @@ conv3x3_patch_kernel(const uint16_t *__restrict__ X, const uint16_t *__restrict_
 #pragma unroll
             for (int j = 0; j < C::NLMAX; ++j) {
                 const int id = lw + NLW * j;
-                unsigned v = P3_OOB;
+                unsigned v = IR2RGB_OOB;
                 if (j < C::nl(ky)) {
                     // LDS slot (row R, 16-byte position s) holds source chunk s ^ ((R >> 1) & 2).  ds_read_b128 is
                     // served in the lane groups {0-3,12-15,20-27}, {4-11,16-19,28-31}, ... (MI355X_MICROARCH.md, LDS):
@@ -159,16 +116,16 @@ conv3x3_patch_kernel(const uint16_t *__restrict__ X, const uint16_t *__restrict_
                     // R & 15 == row16 in every region.
                     const int chunk = (lane & 3) ^ ((row16 >> 1) & 2);
                     if (id < C::NW) {
-                        const int row = (id % C::NW1) * 16 + row16, kx = row / TCO, col = row - kx * TCO;
+                        const int row = (id % C::NW) * 16 + row16, kx = row / TCO, col = row - kx * TCO;
                         const int co = ct * TCO + col;
                         v = (unsigned)((((long)co * g.kchunks) * 9 + kx) * 128 + chunk * 16);
                     } else if (id < C::NW + C::np(ky)) {
-                        const int q = (id - C::NW) % (C::np1(ky) > 0 ? C::np1(ky) : 1);
+                        const int q = (id - C::NW) % (C::np(ky) > 0 ? C::np(ky) : 1);
                         const int pr = ky == 0 ? q / C::PROWI : TR + ky - 1;   // (ADJ: ky == 0 covers every row)
                         const int pc = (q % C::PROWI) * 16 + row16;
                         int iy = y0 - g.pad + pr, ix = x0 - g.pad + pc;
                         bool ok = pc < TW + 2;
-                        if (g.pad_mode == 1) { iy = p3_reflect(iy, g.H); ix = p3_reflect(ix, g.W); ok = ok && iy >= 0 && iy < g.H && ix >= 0 && ix < g.W; }
+                        if (g.pad_mode == 1) { iy = reflect(iy, g.H); ix = reflect(ix, g.W); ok = ok && iy >= 0 && iy < g.H && ix >= 0 && ix < g.W; }
                         else ok = ok && iy >= 0 && iy < g.H && ix >= 0 && ix < g.W;
                         if (ok) v = (unsigned)((((long)n * g.H + iy) * g.W + ix) * g.ldx * 2 + g.ci_off * 2 + chunk * 16);
                     }
@@ -178,28 +135,31 @@ conv3x3_patch_kernel(const uint16_t *__restrict__ X, const uint16_t *__restrict_
         int is = 0;   // next K-step to stage
         auto issue = [&]<int KY>(std::integral_constant<int, KY>) {
             const bool live = is < NK;
-            const int hs = is / 3;                       // slice (SPS == 1) or 64-channel chunk (SPS == 2) of this step
-            const int cc = kc0 + (SPS == 2 ? hs : hs >> 1), half0 = SPS == 2 ? 0 : hs & 1;
+            const int hs = is / 3;                       // 32-channel slice of this step
+            const int cc = kc0 + (hs >> 1), half0 = hs & 1;
             const unsigned w_soff = (unsigned)((cc * 9 + KY * 3) * 128 + half0 * 64);
             const unsigned x_soff = (unsigned)((cc * 64 + half0 * 32) * 2);
             unsigned char *wdst = wring + (is % C::NSTW) * C::WST;
-            unsigned char *pdst = pbufs + (hs & 1) * SPS * C::PBUF;
+            unsigned char *pdst = pbufs + (hs & 1) * C::PBUF;
             if ((g.dbg & 1) && is >= C::AHEAD) { ++is; return; }
 #pragma unroll
             for (int j = 0; j < C::nl(KY); ++j) {
                 const int id = lw + NLW * j;             // wave-uniform
-                const unsigned v = live ? voff[KY][j] : P3_OOB;
+                const unsigned v = live ? voff[KY][j] : IR2RGB_OOB;
+                // (id / NW and qq / NP below are 0 here and the modulos above the identity; hipcc does not fold them, and this
+                // arithmetic and the order destination -> offset are kept as they were so that the code stays what was measured)
                 if (id < C::NW) {
-                    const unsigned hoff = (unsigned)(id / C::NW1) * 64u;       // second slice of the step: +32 channels
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (p3_lptr_t)(wdst + id * 1024), 16, v, w_soff + hoff, 0, 0);
+                    const unsigned hoff = (unsigned)(id / C::NW) * 64u;
+                    const lptr_t dst = (lptr_t)(wdst + id * 1024);
+                    lds_dma16(rw, v, w_soff + hoff, dst);
                 } else if (id < C::NW + C::np(KY)) {
-                    constexpr int NP1 = C::np1(KY) > 0 ? C::np1(KY) : 1;
-                    const int qq = id - C::NW, h = qq / NP1, q = qq - h * NP1;
+                    constexpr int NP = C::np(KY) > 0 ? C::np(KY) : 1;
+                    const int qq = id - C::NW, h = qq / NP, q = qq - h * NP;
                     const int slot = KY == 0 ? q : (TR + KY - 1) * C::PROWI + q;
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (p3_lptr_t)(pdst + h * C::PBUF + slot * 1024), 16, v,
-                                                             x_soff + (unsigned)h * 64u, 0, 0);
+                    const lptr_t dst = (lptr_t)(pdst + h * C::PBUF + slot * 1024);
+                    lds_dma16(rx, v, x_soff + (unsigned)h * 64u, dst);
                 } else {
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (p3_lptr_t)dummy, 16, P3_OOB, 0, 0, 0);
+                    lds_dma16(rx, IR2RGB_OOB, 0, dummy);
                 }
             }
             ++is;
@@ -315,50 +275,14 @@ conv3x3_patch_kernel(const uint16_t *__restrict__ X, const uint16_t *__restrict_
                 if (rowterm && kx == 0 && right && tx == TW - 16) term(PRE ? eb_row[2][ni * pi] : entry(patch, ni, rowoff, 2), 14);
             }
         };
-        if constexpr (PIPE == 1 && SPS == 2) {
-            // a step = one ky of a whole 64-channel chunk: six taps (slice, kx); tap t lives in fragment buffer t & 1,
-            // the barrier that opens the next step sits before the MFMAs of the last tap (see below)
-            int ks = 0;
-            __builtin_amdgcn_s_barrier();                       // step 0 has landed
-            fetch(0, wring, pbufs, 0, 0);
-            for (int cc = 0; cc < kcl; ++cc) {
-                const unsigned char *patch = pbufs + (cc & 1) * 2 * C::PBUF;
-                const unsigned char *patch_next = pbufs + ((cc + 1) & 1) * 2 * C::PBUF;
-                auto step = [&]<int KY>(std::integral_constant<int, KY>) {
-                    const unsigned char *wst = wring + (ks % C::NSTW) * C::WST;
-                    const unsigned char *wst_next = wring + ((ks + 1) % C::NSTW) * C::WST;
-                    constexpr int KO = KY * C::PWP * 64;
-                    fetch(1, wst, patch, KO, 1);
-                    mma(0);
-                    fetch(0, wst, patch, KO, 2);
-                    mma(1);
-                    fetch(1, wst + C::WST1, patch + C::PBUF, KO, 0);
-                    mma(0);
-                    fetch(0, wst + C::WST1, patch + C::PBUF, KO, 1);
-                    mma(1);
-                    fetch(1, wst + C::WST1, patch + C::PBUF, KO, 2);
-                    mma(0);
-                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // every LDS read of step ks is complete
-                    if (ks + 1 < NK) {
-                        __builtin_amdgcn_s_barrier();            // step ks+1 has landed; stage ks may be overwritten
-                        if constexpr (KY < 2) fetch(0, wst_next, patch, (KY + 1) * C::PWP * 64, 0);
-                        else fetch(0, wst_next, patch_next, 0, 0);
-                    }
-                    mma(1);
-                    ++ks;
-                };
-                step(std::integral_constant<int, 0>{});
-                step(std::integral_constant<int, 1>{});
-                step(std::integral_constant<int, 2>{});
-            }
-        } else if constexpr (PIPE == 2) {
+        if constexpr (PIPE == 2) {
             // Large tile (NI = 4, two multiplying waves per SIMD, 168 registers): the full pipelined form below needs two
             // complete fragment sets (+32 registers: spills).  Here only the weight fragments are double-buffered (+16);
             // the pixel fragments are refilled column by column -- fb[ni] is reloaded for the NEXT tap right after the four
             // MFMAs that read it -- so the next tap's operands arrive while the current tap multiplies, within one set.
             // The barrier that opens step ks+1 sits in front of the last tap's MFMAs (its fragments are complete:
             // lgkmcnt(0), which is also what makes handing the stage back safe), and that tap refills from step ks+1.
-            static_assert(!ADJ && SPS == 1, "column-refill form: forward, one slice per step");
+            static_assert(!ADJ, "column-refill form: forward only");
             // The reads are inline asm and the waits are counted by hand: left to hipcc, the reads sink down to their uses
             // (it schedules for register pressure at this occupancy) and every MFMA group ends up behind a full
             // s_waitcnt of the read issued just before it.  A wait names the fragments it makes valid ("+v"), so the MFMAs
@@ -535,18 +459,18 @@ conv3x3_patch_kernel(const uint16_t *__restrict__ X, const uint16_t *__restrict_
         // add came last consumes; hipMalloc memory, one workgroup per CU).  A release / acquire fence pair (__threadfence)
         // would be the textbook form, but on this chip it is buffer_wbl2 + buffer_inv: a walk over the XCD's whole L2 per
         // workgroup -- measured 104 us instead of 49 for the launch.
-        typedef __attribute__((ext_vector_type(4))) unsigned p3_u32x4;
+        typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
         constexpr int PER = NCW * MI * NI * 64 * 16;       // bytes per partial tile
         // exact extent of the partial tiles ([tiles][SPLIT] x PER bytes; the host keeps it under 1 GB): an offset past it
         // is dropped / reads zeros instead of touching a neighbour allocation
-        const p3_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc(partials, 0, npt * nct * SPLIT * PER, 0x00020000);
+        const rsrc_t rp = make_rsrc(partials, npt * nct * SPLIT * PER);
         const unsigned mine = (unsigned)((tile * SPLIT + ksplit) * PER), other = (unsigned)((tile * SPLIT + (ksplit ^ 1)) * PER);
         if (!loader) {
 #pragma unroll
             for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
                 for (int ni = 0; ni < NI; ++ni)
-                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(p3_u32x4, acc[mi][ni]), rp,
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[mi][ni]), rp,
                                                            mine + (unsigned)((((wave * MI + mi) * NI + ni) * 64 + lane) * 16), 0, 16);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's partial sums have reached the coherence point ...
@@ -561,7 +485,7 @@ conv3x3_patch_kernel(const uint16_t *__restrict__ X, const uint16_t *__restrict_
             // all 16 loads are issued before the first is consumed (they are served by the memory side, ~2 us: issued in
             // dependent groups they took longer than the K loop); own + other: commutative, either arrival order gives the
             // same bits
-            p3_u32x4 tmp[MI][NI];
+            u32x4 tmp[MI][NI];
 #pragma unroll
             for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
@@ -570,7 +494,7 @@ conv3x3_patch_kernel(const uint16_t *__restrict__ X, const uint16_t *__restrict_
 #pragma unroll
             for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
-                for (int ni = 0; ni < NI; ++ni) acc[mi][ni] += __builtin_bit_cast(p3_f32x4, tmp[mi][ni]);
+                for (int ni = 0; ni < NI; ++ni) acc[mi][ni] += __builtin_bit_cast(f32x4, tmp[mi][ni]);
         }
     }
     constexpr int NCH = TCO / 8;                                    // 16-byte chunks per staged pixel row
@@ -661,28 +585,6 @@ static bool p3_enabled() {
     return v != 0;
 }
 
-// Small tile with one 64-channel chunk per K-step instead of one 32-channel slice (half the barriers).  Measured
-// neutral (51.7 / 54.0 us against 53.7 / 53.9 us): the 2x64 px x 64 cout tile is bound by LDS bandwidth, not by the
-// barrier cadence -- four waves each read all 64 couts' weights for only 32 pixels: 0.75 KB of ds_read_b128 per MFMA
-// = 192 B/clk of the 256 B/clk LDS, plus the DMA writes.  Kept selectable (IR2RGB_CONV3X3P_SPS2=1), off by default.
-static bool p3_sps2() {
-    static int v = -1;
-    if (v < 0) { const char *e = getenv("IR2RGB_CONV3X3P_SPS2"); v = e ? atoi(e) : 0; }
-    return v != 0;
-}
-
-static long p3_min_tiles() {   // fewer tiles than this leave too much of the chip idle: the general kernel runs instead
-    static long v = -1;
-    if (v < 0) { const char *e = getenv("IR2RGB_CONV3X3P_MIN_TILES"); v = e ? atol(e) : 200; }
-    return v;
-}
-
-static int p3_min_cin() {
-    static int v = -1;
-    if (v < 0) { const char *e = getenv("IR2RGB_CONV3X3P_MIN_CIN"); v = e ? atoi(e) : 256; }
-    return v;
-}
-
 // Split-K forms (variants 3, 4; only where the caller supplies a workspace).  IR2RGB_CONV3X3P_SPLIT=0 switches them off,
 // =3 / =4 forces one for A/B runs; default: 4 where it applies, else 3.  Measured on 1024 -> 1024 @32x64 (forward / reflect
 // adjoint, us): unsplit 47.9 / 67.2, variant 3 47.8 / 60.2, variant 4 46.3 / 56.9.  Four workgroups per tile with 8
@@ -711,7 +613,7 @@ int conv3x3p_plan(const ir2rgb_conv_desc *d, P3Geom *g, int *npt_out, bool allow
     if (d->Hout != d->Hin + 2 * d->pad_h - 2 || d->Wout != d->Win + 2 * d->pad_w - 2) return 0;
     // (128-channel layers: the general kernel is faster forward (53 vs 56 us at 256x512), but the in-place reflection adjoint
     // beats its zero-padded convolution + fold pass: 54 us against 62 + 19)
-    const int min_cin = adj && p3_min_cin() > 128 ? 128 : p3_min_cin();
+    const int min_cin = adj ? 128 : 256;
     if ((d->Cin % 64) || d->Cin < min_cin || (d->Cout % 64) || d->Hin < 4 || d->Win < 4 || d->N < 1) return 0;
     if (d->dtype != IR2RGB_BF16 && d->dtype != IR2RGB_F16) return 0;
     const int ldx = d->ldx > 0 ? d->ldx : d->Cin, ldy = d->ldy > 0 ? d->ldy : d->Cout;
@@ -723,7 +625,7 @@ int conv3x3p_plan(const ir2rgb_conv_desc *d, P3Geom *g, int *npt_out, bool allow
     const double wr = waste(d->Hout, 2);
     const long t128 = (long)d->N * ((d->Hout + 1) / 2) * ((d->Wout + 127) / 128) * (d->Cout / 128);
     const long t64 = (long)d->N * ((d->Hout + 1) / 2) * ((d->Wout + 63) / 64) * (d->Cout / 64);
-    const long tmin = p3_min_tiles();
+    const long tmin = 200;   // fewer tiles than this leave too much of the chip idle: the general kernel runs instead
     if ((d->Cout % 128) == 0 && wr * waste(d->Wout, 128) <= 1.13 && t128 >= tmin && (!adj || d->Win % 128 == 0)) variant = 2;
     else if (wr * waste(d->Wout, 64) <= 1.13 && t64 >= tmin) variant = 1;
     if (!variant) return 0;
@@ -753,9 +655,6 @@ int conv3x3p_plan(const ir2rgb_conv_desc *d, P3Geom *g, int *npt_out, bool allow
     g->kchunks = d->Cin / 64;
     g->x_bytes = (unsigned)xb; g->w_bytes = (unsigned)wb;
     g->cout_major = wb > (long)d->N * d->Hin * d->Win * d->Cin * 2 ? 1 : 0;
-#ifdef IR2RGB_ABLATION   // timing experiments only (tools/conv_ablate.py; build with -DIR2RGB_ABLATION): results are garbage
-    { static int dbg = -1; if (dbg < 0) { const char *e = getenv("IR2RGB_CONV3X3P_DBG"); dbg = e ? atoi(e) : 0; } g->dbg = dbg; }
-#endif
     if (d->pad_mode == 1 && (d->pad_h >= d->Hin || d->pad_w >= d->Win)) return 0;
     *npt_out = d->N * ((d->Hout + 1) / 2) * g->ntx;    // rows of the statistics buffer: 2-row tiles in every variant
     return variant;
@@ -769,23 +668,18 @@ long conv3x3p_workspace_bytes(int variant, const P3Geom &g) {
     return ((tiles * 4 + 4095) & ~4095L) + tiles * c.split * (c.ncw * 4L * 4 * 4 * 64) * 4;
 }
 
-template <int DT, int TCO, int NCW, int PIPE, int SPLIT, int TR, int NLWF = 4>
+template <int DT, int TCO, int NCW, int PIPE, int SPLIT, int TR>
 static void p3_launch_split(bool adj, unsigned grid, const uint16_t *X, const uint16_t *W, const float *bias, uint16_t *Y,
                             float *stats, const P3Geom &g, unsigned *tickets, float *partials, hipStream_t s) {
-    if (adj) conv3x3_patch_kernel<DT, 64, TCO, NCW, 4, PIPE, 1, 1, SPLIT, TR><<<grid, (NCW + 4) * 64, 0, s>>>(X, W, bias, Y, stats, g, tickets, partials);
-    else conv3x3_patch_kernel<DT, 64, TCO, NCW, NLWF, PIPE, 0, 1, SPLIT, TR><<<grid, (NCW + NLWF) * 64, 0, s>>>(X, W, bias, Y, stats, g, tickets, partials);
+    if (adj) conv3x3_patch_kernel<DT, 64, TCO, NCW, 4, PIPE, 1, SPLIT, TR><<<grid, (NCW + 4) * 64, 0, s>>>(X, W, bias, Y, stats, g, tickets, partials);
+    else conv3x3_patch_kernel<DT, 64, TCO, NCW, 4, PIPE, 0, SPLIT, TR><<<grid, (NCW + 4) * 64, 0, s>>>(X, W, bias, Y, stats, g, tickets, partials);
 }
 
 template <int DT>
 static void p3_launch_split_variant(int variant, bool adj, unsigned grid, const uint16_t *X, const uint16_t *W, const float *bias,
                                     uint16_t *Y, float *stats, const P3Geom &g, unsigned *tickets, float *partials, hipStream_t s) {
     if (variant == 3) p3_launch_split<DT, 128, 4, 1, 2, 2>(adj, grid, X, W, bias, Y, stats, g, tickets, partials, s);
-    else {
-        static int nlw8 = -1;
-        if (nlw8 < 0) { const char *e = getenv("IR2RGB_CONV3X3P_NLW8"); nlw8 = e ? atoi(e) : 0; }
-        if (nlw8) p3_launch_split<DT, 64, 4, 1, 2, 4, 8>(adj, grid, X, W, bias, Y, stats, g, tickets, partials, s);
-        else p3_launch_split<DT, 64, 4, 1, 2, 4>(adj, grid, X, W, bias, Y, stats, g, tickets, partials, s);
-    }
+    else p3_launch_split<DT, 64, 4, 1, 2, 4>(adj, grid, X, W, bias, Y, stats, g, tickets, partials, s);
 }
 
 int conv3x3p_launch(int variant, const P3Geom &g, int dtype, const void *x, const void *wp, const float *bias, void *y,
@@ -808,44 +702,24 @@ int conv3x3p_launch(int variant, const P3Geom &g, int dtype, const void *x, cons
     if (variant == 2) {
         const unsigned grid = (unsigned)(npt * (g.Cout / 128));
         if (adj) {
-            if (dtype == IR2RGB_BF16) conv3x3_patch_kernel<IR2RGB_BF16, 128, 128, 8, 4, 0, 1, 1><<<grid, 768, 0, s>>>(X, W, bias, Yp, stats, g);
-            else conv3x3_patch_kernel<IR2RGB_F16, 128, 128, 8, 4, 0, 1, 1><<<grid, 768, 0, s>>>(X, W, bias, Yp, stats, g);
+            if (dtype == IR2RGB_BF16) conv3x3_patch_kernel<IR2RGB_BF16, 128, 128, 8, 4, 0, 1><<<grid, 768, 0, s>>>(X, W, bias, Yp, stats, g);
+            else conv3x3_patch_kernel<IR2RGB_F16, 128, 128, 8, 4, 0, 1><<<grid, 768, 0, s>>>(X, W, bias, Yp, stats, g);
         } else {
             // (the fully pipelined form at this tile needs 2 x (MI + NI) fragment registers more than the 168 the 12-wave
-            // workgroup leaves a wave: measured in round 2, 8 VGPRs spilled.  PIPE = 2, round 3: weights double-buffered,
-            // pixel fragments refilled column by column; IR2RGB_CONV3X3P_LARGE_PIPE=0 selects the plain loop for A/B runs)
-            static int lp = -1;
-            if (lp < 0) { const char *e = getenv("IR2RGB_CONV3X3P_LARGE_PIPE"); lp = e ? atoi(e) : 1; }
-            if (lp) {
-                if (dtype == IR2RGB_BF16) conv3x3_patch_kernel<IR2RGB_BF16, 128, 128, 8, 4, 2, 0, 1><<<grid, 768, 0, s>>>(X, W, bias, Yp, stats, g);
-                else conv3x3_patch_kernel<IR2RGB_F16, 128, 128, 8, 4, 2, 0, 1><<<grid, 768, 0, s>>>(X, W, bias, Yp, stats, g);
-            } else {
-                if (dtype == IR2RGB_BF16) conv3x3_patch_kernel<IR2RGB_BF16, 128, 128, 8, 4, 0, 0, 1><<<grid, 768, 0, s>>>(X, W, bias, Yp, stats, g);
-                else conv3x3_patch_kernel<IR2RGB_F16, 128, 128, 8, 4, 0, 0, 1><<<grid, 768, 0, s>>>(X, W, bias, Yp, stats, g);
-            }
+            // workgroup leaves a wave: 8 VGPRs spilled.  PIPE = 2: weights double-buffered, pixel fragments refilled column
+            // by column)
+            if (dtype == IR2RGB_BF16) conv3x3_patch_kernel<IR2RGB_BF16, 128, 128, 8, 4, 2, 0><<<grid, 768, 0, s>>>(X, W, bias, Yp, stats, g);
+            else conv3x3_patch_kernel<IR2RGB_F16, 128, 128, 8, 4, 2, 0><<<grid, 768, 0, s>>>(X, W, bias, Yp, stats, g);
         }
     } else {
+        // software-pipelined, forward and reflect-adjoint alike (the adjoint's border operands are prefetched into registers)
         const unsigned grid = (unsigned)(npt * (g.Cout / 64));
         if (adj) {
-            // software-pipelined like the forward twin (border operands prefetched into registers); IR2RGB_CONV3X3P_ADJ_PIPE=0
-            // selects the plain loop (barrier at the top of every step) for A/B runs
-            static int adj_pipe = -1;
-            if (adj_pipe < 0) { const char *e = getenv("IR2RGB_CONV3X3P_ADJ_PIPE"); adj_pipe = e ? atoi(e) : 1; }
-            if (adj_pipe) {
-                if (dtype == IR2RGB_BF16) conv3x3_patch_kernel<IR2RGB_BF16, 64, 64, 4, 8, 1, 1, 1><<<grid, 768, 0, s>>>(X, W, bias, Yp, stats, g);
-                else conv3x3_patch_kernel<IR2RGB_F16, 64, 64, 4, 8, 1, 1, 1><<<grid, 768, 0, s>>>(X, W, bias, Yp, stats, g);
-            } else {
-                if (dtype == IR2RGB_BF16) conv3x3_patch_kernel<IR2RGB_BF16, 64, 64, 4, 8, 0, 1, 1><<<grid, 768, 0, s>>>(X, W, bias, Yp, stats, g);
-                else conv3x3_patch_kernel<IR2RGB_F16, 64, 64, 4, 8, 0, 1, 1><<<grid, 768, 0, s>>>(X, W, bias, Yp, stats, g);
-            }
+            if (dtype == IR2RGB_BF16) conv3x3_patch_kernel<IR2RGB_BF16, 64, 64, 4, 8, 1, 1><<<grid, 768, 0, s>>>(X, W, bias, Yp, stats, g);
+            else conv3x3_patch_kernel<IR2RGB_F16, 64, 64, 4, 8, 1, 1><<<grid, 768, 0, s>>>(X, W, bias, Yp, stats, g);
         } else {
-            if (p3_sps2()) {
-                if (dtype == IR2RGB_BF16) conv3x3_patch_kernel<IR2RGB_BF16, 64, 64, 4, 8, 1, 0, 2><<<grid, 768, 0, s>>>(X, W, bias, Yp, stats, g);
-                else conv3x3_patch_kernel<IR2RGB_F16, 64, 64, 4, 8, 1, 0, 2><<<grid, 768, 0, s>>>(X, W, bias, Yp, stats, g);
-            } else {
-                if (dtype == IR2RGB_BF16) conv3x3_patch_kernel<IR2RGB_BF16, 64, 64, 4, 8, 1, 0, 1><<<grid, 768, 0, s>>>(X, W, bias, Yp, stats, g);
-                else conv3x3_patch_kernel<IR2RGB_F16, 64, 64, 4, 8, 1, 0, 1><<<grid, 768, 0, s>>>(X, W, bias, Yp, stats, g);
-            }
+            if (dtype == IR2RGB_BF16) conv3x3_patch_kernel<IR2RGB_BF16, 64, 64, 4, 8, 1, 0><<<grid, 768, 0, s>>>(X, W, bias, Yp, stats, g);
+            else conv3x3_patch_kernel<IR2RGB_F16, 64, 64, 4, 8, 1, 0><<<grid, 768, 0, s>>>(X, W, bias, Yp, stats, g);
         }
     }
     return ir2rgb_launch_status();

@@ -23,30 +23,11 @@
 #include "common.h"
 #include "conv7x1_col.h"
 
-typedef __attribute__((ext_vector_type(8))) __bf16 c7_bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 c7_f16x8;
-typedef __attribute__((ext_vector_type(4))) float c7_f32x4;
-typedef __attribute__((address_space(3))) void *c7_lptr_t;
-typedef __amdgpu_buffer_rsrc_t c7_rsrc_t;
-#define C7_OOB 0x80000000u
-
-template <int DT> struct C7Half;
-template <> struct C7Half<IR2RGB_BF16> {
-    typedef c7_bf16x8 frag;
-    static __device__ __forceinline__ c7_f32x4 mfma(frag a, frag b, c7_f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-    static __device__ __forceinline__ uint16_t cvt(float f) { __bf16 h = (__bf16)f; return __builtin_bit_cast(uint16_t, h); }
-};
-template <> struct C7Half<IR2RGB_F16> {
-    typedef c7_f16x8 frag;
-    static __device__ __forceinline__ c7_f32x4 mfma(frag a, frag b, c7_f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-    static __device__ __forceinline__ uint16_t cvt(float f) { _Float16 h = (_Float16)f; return __builtin_bit_cast(uint16_t, h); }
-};
-
 template <int DT, int COUT>
 __global__ void __launch_bounds__(256, 1)
 conv7x1_col_kernel(const uint16_t *__restrict__ X, const uint16_t *__restrict__ Wp, const float *__restrict__ bias,
                    uint16_t *__restrict__ Y, float *__restrict__ stats_partial, const C7Geom g) {
-    typedef C7Half<DT> Hf;
+    typedef Half<DT> Hf;
     typedef typename Hf::frag frag;
     constexpr int TH = 8, TW = 32, KH = 7, PAD = 3, SR = TH + KH - 1;     // 14 staged rows of 32 pixels
     constexpr int NW = 4, WC = COUT / 32, WP = NW / WC;                   // waves: WC along the couts x WP along the pixel blocks
@@ -61,9 +42,9 @@ conv7x1_col_kernel(const uint16_t *__restrict__ X, const uint16_t *__restrict__ 
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wc = wave % WC, wp = wave / WC;
     const int l15 = lane & 15, grp = lane >> 4;
-    const c7_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t *>(X), 0, (int)g.x_bytes, 0x00020000);
-    const c7_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t *>(Wp), 0, (int)g.w_bytes, 0x00020000);
-    const c7_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(Y, 0, (int)g.y_bytes, 0x00020000);
+    const rsrc_t rx = make_rsrc(X, g.x_bytes);
+    const rsrc_t rw = make_rsrc(Wp, g.w_bytes);
+    const rsrc_t ry = make_rsrc(Y, g.y_bytes);
     const int ntiles = g.N * g.nty * g.ntx;
 
     // ---- stage a tile: instruction i = wave + 4*q covers pixel rows R = 8*i .. 8*i+7 (staged row R / 32, pixel R % 32)
@@ -80,8 +61,8 @@ conv7x1_col_kernel(const uint16_t *__restrict__ X, const uint16_t *__restrict__ 
             ys = ys >= g.H ? 2 * g.H - 2 - ys : ys;
             const int xs = x0 + px;
             const bool ok = tile < ntiles && ys >= 0 && ys < g.H && xs < g.W;
-            const unsigned v = ok ? ((unsigned)((n * g.H + ys) * g.W + xs) * (unsigned)g.ldx + (unsigned)g.ci_off + (unsigned)chunk * 8u) * 2u : C7_OOB;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (c7_lptr_t)(smem + buf * SEG + i * 1024), 16, v, 0, 0, 0);
+            const unsigned v = ok ? ((unsigned)((n * g.H + ys) * g.W + xs) * (unsigned)g.ldx + (unsigned)g.ci_off + (unsigned)chunk * 8u) * 2u : IR2RGB_OOB;
+            lds_dma16(rx, v, 0, smem + buf * SEG + i * 1024);
         }
     };
     int tile = blockIdx.x;
@@ -98,7 +79,7 @@ conv7x1_col_kernel(const uint16_t *__restrict__ X, const uint16_t *__restrict__ 
             const int co = wc * 32 + mt * 16 + l15;
             const unsigned off = (unsigned)(((co * KH + ky) * 64 + c * 32 + grp * 8) * 2);
             typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
-            A[j][mt] = __builtin_bit_cast(frag, __builtin_amdgcn_raw_buffer_load_b128(rw, co < g.Cout ? off : C7_OOB, 0, 0));
+            A[j][mt] = __builtin_bit_cast(frag, __builtin_amdgcn_raw_buffer_load_b128(rw, co < g.Cout ? off : IR2RGB_OOB, 0, 0));
         }
     }
     float bv[2][4];
@@ -142,11 +123,11 @@ conv7x1_col_kernel(const uint16_t *__restrict__ X, const uint16_t *__restrict__ 
         for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
             for (int r = 0; r < 4; ++r) s1[mt][r] = s2[mt][r] = 0.f;
-        c7_f32x4 acc[2];
+        f32x4 acc[2];
         auto body = [&]<int T>(std::integral_constant<int, T>) {
             constexpr int b = T / NKS, j = T % NKS;
             constexpr int after = (NT - 1 - T) < (R - 1) ? (NT - 1 - T) : (R - 1);
-            if constexpr (j == 0) { acc[0] = (c7_f32x4){0.f, 0.f, 0.f, 0.f}; acc[1] = (c7_f32x4){0.f, 0.f, 0.f, 0.f}; }
+            if constexpr (j == 0) { acc[0] = (f32x4){0.f, 0.f, 0.f, 0.f}; acc[1] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
             asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(B[T % R]) : "n"(after) : "memory");
             __builtin_amdgcn_sched_barrier(0);
             acc[0] = Hf::mfma(A[j][0], B[T % R], acc[0]);
@@ -172,7 +153,7 @@ conv7x1_col_kernel(const uint16_t *__restrict__ X, const uint16_t *__restrict__ 
                     pk.y = (uint32_t)Hf::cvt(v[2]) | ((uint32_t)Hf::cvt(v[3]) << 16);
                     const int co = wc * 32 + mt * 16 + grp * 4;
                     // (an out-of-range offset drops the store: no branch in the stream)
-                    __builtin_amdgcn_raw_buffer_store_b64(pk, ry, (valid && co < g.Cout) ? (pixoff + (unsigned)co) * 2u : C7_OOB, 0, 0);
+                    __builtin_amdgcn_raw_buffer_store_b64(pk, ry, (valid && co < g.Cout) ? (pixoff + (unsigned)co) * 2u : IR2RGB_OOB, 0, 0);
                 }
             }
         };
@@ -198,14 +179,8 @@ conv7x1_col_kernel(const uint16_t *__restrict__ X, const uint16_t *__restrict__ 
 // ----------------------------------------------------------------------------------------
 // host side (called from conv_mfma.hip)
 // ----------------------------------------------------------------------------------------
-static bool c7_enabled() {
-    static int v = -1;
-    if (v < 0) { const char *e = getenv("IR2RGB_CONV7X1_COL"); v = e ? atoi(e) : 1; }
-    return v != 0;
-}
-
 bool conv7x1_col_plan(const ir2rgb_conv_desc *d, C7Geom *g) {
-    if (!c7_enabled() || d->transposed || d->kh != 7 || d->kw != 1 || d->stride_h != 1 || d->stride_w != 1) return false;
+    if (d->transposed || d->kh != 7 || d->kw != 1 || d->stride_h != 1 || d->stride_w != 1) return false;
     if (d->pad_h != 3 || d->pad_w != 0 || d->pad_mode != 1 || d->out_f32 || d->act != 0 || d->stats_per_sample) return false;
     if (d->Cin != 64 || (d->Cout != 64 && d->Cout != 128) || d->Hin < 4 || d->Hout != d->Hin || d->Wout != d->Win) return false;
     if (d->dtype != IR2RGB_BF16 && d->dtype != IR2RGB_F16) return false;

@@ -35,11 +35,8 @@
 
 #include "common.h"
 #include "conv1x7_thin.h"
+#include "conv3x3_patch.h"
 #include "conv7x1_col.h"
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 #define IR2RGB_MAX_TAPS 49
 
@@ -57,7 +54,6 @@ struct ConvGeom {
     int out_f32;              // 1: Y is fp32 NHWC (head convolutions), 0: half
     FastDiv div_hw, div_w;    // exact division by Hsub*Wsub and by Wsub
     unsigned x_bytes, w_bytes; // extents of X and of this class's packed weights (buffer resources, < 2^31)
-    int variant;              // tuning switches (bit 0: waves 4-7 issue their LDS-DMA after their MFMA block)
     int cout_major;           // XCD mapping: 1 = an XCD sweeps the pixel tiles of few cout tiles (weights stay in its L2)
     // taps form an nty x ntx grid: tap (ty,tx) reads input offset (dy0 + ty*dys, dx0 + tx*dxs).
     // Pure scalar arithmetic: no table load sits between the LDS-DMA issues of the K loop.
@@ -65,49 +61,6 @@ struct ConvGeom {
     int tpi;                  // > 0: pixel tiles are cut per sample, tpi tiles each (ir2rgb_conv_desc.stats_per_sample)
 };
 
-
-template <int DT> struct Half;
-template <> struct Half<IR2RGB_BF16> {
-    typedef bf16x8 frag;
-    static __device__ __forceinline__ f32x4 mfma(frag a, frag b, f32x4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-    }
-    static __device__ __forceinline__ uint16_t cvt(float f) {
-        __bf16 h = (__bf16)f;
-        return __builtin_bit_cast(uint16_t, h);
-    }
-};
-template <> struct Half<IR2RGB_F16> {
-    typedef f16x8 frag;
-    static __device__ __forceinline__ f32x4 mfma(frag a, frag b, f32x4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-    }
-    static __device__ __forceinline__ uint16_t cvt(float f) {
-        _Float16 h = (_Float16)f;
-        return __builtin_bit_cast(uint16_t, h);
-    }
-};
-
-typedef const __attribute__((address_space(1))) void *gptr_t;
-typedef __attribute__((address_space(3))) void *lptr_t;
-
-// Buffer-addressed LDS-DMA: 16 B per lane from (SGPR base + per-lane 32-bit byte offset + scalar byte
-// offset) to LDS at wave-uniform base + lane * 16.  The per-lane offset is range-checked against the
-// resource extent and out-of-range lanes deliver ZEROS: zero padding costs no instruction, and the
-// scalar K offset rides in an SGPR, so a K-step's staging issues no VALU address arithmetic at all.
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
-#define IR2RGB_OOB 0x80000000u
-__device__ __forceinline__ rsrc_t make_rsrc(const void *p, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ void lds_dma16(rsrc_t r, unsigned voff, unsigned soff, unsigned char *dst_wave_base) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lptr_t)dst_wave_base, 16, voff, soff, 0, 0);
-}
-
-__device__ __forceinline__ int reflect(int v, int n) {
-    v = v < 0 ? -v : v;
-    return v >= n ? 2 * n - 2 - v : v;
-}
 
 // NTY x NTX > 0: the tap grid is a compile-time constant, the tap loop is fully unrolled and the
 // gather offsets of this thread's pixel rows are precomputed for every tap (PROWS*NTY*NTX
@@ -284,7 +237,9 @@ conv_igemm_body(const uint16_t *__restrict__ X, const uint16_t *__restrict__ Wp,
         for (int ni = 0; ni < NI; ++ni) acc[mi][ni] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
     const int nk = g.kchunks * g.ntaps;
-    const bool late_dma = (g.variant & 1) && wave >= 4 && AHEAD >= 2;  // wave-uniform (SGPR)
+    // waves 4-7 issue their LDS-DMA after their MFMA block (staggered against their SIMD partners: measured +6..7 % on the
+    // large shapes)
+    const bool late_dma = wave >= 4 && AHEAD >= 2;  // wave-uniform (SGPR)
 
     auto wait_stage = [&](int ks) {
         // stage ks has landed for THIS wave once all but the newest LOADS*(AHEAD-1) (later stages) are done.
@@ -752,34 +707,14 @@ struct ClassPlan {
     int tp;         // pixels per tile: 256 / 128 / 64
 };
 
-static bool merge_classes() {
-    static int v = -1;
-    if (v < 0) { const char *e = getenv("IR2RGB_CONV_MERGE"); v = e ? atoi(e) : 1; }
-    return v != 0;
-}
-
-static int conv_variant() {
-    static int v = -1;
-    if (v < 0) {
-        const char *e = getenv("IR2RGB_CONV_VARIANT");
-        v = e ? atoi(e) : 1;  // default: staggered DMA (measured +6..7 % on the large shapes)
-    }
-    return v;
-}
-
 static int tile_pixels(long P, int Cout, int ksteps) {
     // TP = 256 (one resident workgroup per CU) pays off for long K loops with at least one tile per CU;
     // shorter loops / fewer tiles run two workgroups per CU with TP = 128 or 64.
-    static int forced = -1;          // IR2RGB_CONV_TP=256|128|64: experiments only
-    if (forced < 0) { const char *e = getenv("IR2RGB_CONV_TP"); forced = e ? atoi(e) : 0; }
-    if (forced == 256 || forced == 128 || forced == 64) return forced;
     const long nct = (Cout + 127) / 128;
     const long tiles256 = ((P + 255) / 256) * nct;
-    static int rule = -1;            // IR2RGB_CONV_TP_RULE=0: the earlier rule (TP = 256 also for short loops over >= 768 tiles)
-    if (rule < 0) { const char *e = getenv("IR2RGB_CONV_TP_RULE"); rule = e ? atoi(e) : 1; }
     // long K loops: the deep 3-stage ring of the 256-pixel tile wins; short ones (k x 1 first layers and heads,
     // sub-pixel classes of the up-samplers: 7..36 steps) run 10-20 % faster as two 128-pixel workgroups per CU
-    if (tiles256 >= 256 && (ksteps >= 40 || (rule == 0 && tiles256 >= 768))) return 256;
+    if (tiles256 >= 256 && ksteps >= 40) return 256;
     if (((P + 127) / 128) * nct >= 256) return 128;
     return 64;
 }
@@ -859,7 +794,6 @@ static int make_plan(const ir2rgb_conv_desc *d, ClassPlan plans[4]) {
         return IR2RGB_EINVAL;
     for (int i = 0; i < ncls; ++i) {
         ConvGeom &g = plans[i].geom;
-        g.variant = conv_variant();
         g.div_hw = make_fastdiv((unsigned)(g.Hsub * g.Wsub)); g.div_w = make_fastdiv((unsigned)g.Wsub);
         g.ldx = d->ldx > 0 ? d->ldx : d->Cin; g.ci_off = d->ci_off;
         g.ldy = d->ldy > 0 ? d->ldy : d->Cout; g.co_off = d->co_off;
@@ -870,17 +804,12 @@ static int make_plan(const ir2rgb_conv_desc *d, ClassPlan plans[4]) {
         const long xb = (long)g.N * g.Hin * g.Win * g.ldx * 2, wb = (long)g.Cout * g.Cin * g.ntaps * 2;
         if (xb >= (1L << 31) || wb >= (1L << 31)) return IR2RGB_EINVAL;  // 32-bit buffer offsets
         g.x_bytes = (unsigned)xb; g.w_bytes = (unsigned)wb;
-        {
-            static int force = -2;
-            if (force == -2) { const char *e = getenv("IR2RGB_CONV_COUT_MAJOR"); force = e ? atoi(e) : -1; }
-            const long x_used = (long)g.N * g.Hin * g.Win * g.Cin * 2;
-            g.cout_major = force >= 0 ? force : (wb > x_used ? 1 : 0);
-        }
+        g.cout_major = wb > (long)g.N * g.Hin * g.Win * g.Cin * 2 ? 1 : 0;     // weights outweigh the activations read
     }
     // pixel-tile size: per class, or -- when the classes share one launch -- one size for all of them chosen
     // from the total tile count and the longest K loop
     int tp_all = 0;
-    if (ncls > 1 && merge_classes()) {
+    if (ncls > 1) {
         long p_all = 0, ks_sum = 0;
         for (int i = 0; i < ncls; ++i) {
             const ConvGeom &g = plans[i].geom;
@@ -891,11 +820,9 @@ static int make_plan(const ir2rgb_conv_desc *d, ClassPlan plans[4]) {
         // Classes have K loops of different lengths (3x3 / stride 2: 1, 2, 2 and 4 taps) and a workgroup keeps its class
         // to the end: with 128-pixel tiles and at most ~one round of workgroups (the training sizes: 1024 -> 512 @32x64
         // has 256 of them) every CU runs ONE workgroup and the launch lasts as long as the 4-tap class.  64-pixel tiles give
-        // two co-resident workgroups per CU, long and short ones mixed.  IR2RGB_CONV_CLASSES_SMALL=0: the earlier rule.
-        static int small = -1;
-        if (small < 0) { const char *e = getenv("IR2RGB_CONV_CLASSES_SMALL"); small = e ? atoi(e) : 1; }
+        // two co-resident workgroups per CU, long and short ones mixed.
         const long wg128 = ((p_all + 127) / 128) * ((plans[0].geom.Cout + 127) / 128);
-        if (small && tp_all == 128 && wg128 <= 320) tp_all = 64;
+        if (tp_all == 128 && wg128 <= 320) tp_all = 64;
     }
     for (int i = 0; i < ncls; ++i) {
         ConvGeom &g = plans[i].geom;
@@ -923,22 +850,8 @@ extern "C" long ir2rgb_conv2d_packed_weight_elems(const ir2rgb_conv_desc *d) {
     return e;
 }
 
-// conv3x3_patch.hip: the patch-staged kernel for 3x3 / stride-1 layers with >= 256 input channels
-struct P3Geom {
-    int N, H, W, Ho, Wo, Cin, Cout;
-    int pad, pad_mode, act;
-    int ldx, ci_off, ldy, co_off;
-    int stats_row0, nty, ntx;
-    int cout_major, kchunks;
-    unsigned x_bytes, w_bytes;
-    int dbg;
-};
-int conv3x3p_plan(const ir2rgb_conv_desc *d, P3Geom *g, int *npt_out, bool allow_split = false);
-long conv3x3p_workspace_bytes(int variant, const P3Geom &g);
-int conv3x3p_launch(int variant, const P3Geom &g, int dtype, const void *x, const void *wp, const float *bias, void *y,
-                    float *stats, hipStream_t s, void *workspace, long workspace_bytes);
-
-// One fp32 output channel, zero padding, 512-channel slabs, <= 16 taps: conv_dot_kernel (IR2RGB_CONV_DOT=0: GEMM tile)
+// One fp32 output channel, zero padding, 512-channel slabs, <= 16 taps: conv_dot_kernel (IR2RGB_CONV_DOT=0: the GEMM tile,
+// which is what such a layer with other channel counts gets)
 static bool conv_dot_ok(const ir2rgb_conv_desc *d) {
     static int v = -1;
     if (v < 0) { const char *e = getenv("IR2RGB_CONV_DOT"); v = e ? atoi(e) : 1; }
@@ -962,7 +875,7 @@ extern "C" const char *ir2rgb_conv2d_kernel_name(const ir2rgb_conv_desc *d) {
     const int n = make_plan(d, plans);
     if (n < 0) return "";
     if (n == 1 && conv_dot_ok(d)) return "conv_dot_kernel";
-    return (n > 1 && merge_classes()) ? "conv_igemm_classes_kernel" : "conv_igemm_kernel";
+    return n > 1 ? "conv_igemm_classes_kernel" : "conv_igemm_kernel";
 }
 
 extern "C" int ir2rgb_conv2d_stats_rows(const ir2rgb_conv_desc *d) {
@@ -1149,12 +1062,6 @@ static void launch_conv_taps(const ClassPlan &c, int tp, unsigned grid, const ui
     }
 }
 
-static bool conv_thin() {      // IR2RGB_CONV_THIN=0: thin layers on the full 128-row tile (A/B measurements)
-    static int v = -1;
-    if (v < 0) { const char *e = getenv("IR2RGB_CONV_THIN"); v = e ? atoi(e) : 1; }
-    return v != 0;
-}
-
 template <int DT>
 static void launch_conv(const ClassPlan &c, const uint16_t *x, const uint16_t *wp, const float *bias, uint16_t *y,
                         float *stats, hipStream_t s) {
@@ -1163,7 +1070,7 @@ static void launch_conv(const ClassPlan &c, const uint16_t *x, const uint16_t *w
     const int nct = (g.Cout + 127) / 128;
     const unsigned grid = (unsigned)(c.npt * nct);
     const int nty = g.ntaps / g.ntx;
-    const bool thin = g.Cout <= 32 && conv_thin();
+    const bool thin = g.Cout <= 32;
     if (thin && nty == 4 && g.ntx == 4)      launch_conv_taps<DT, 4, 4, true>(c, tp, grid, x, wp, bias, y, stats, s);
     else if (thin && nty == 1 && g.ntx == 7) launch_conv_taps<DT, 1, 7, true>(c, tp, grid, x, wp, bias, y, stats, s);
     else if (nty == 3 && g.ntx == 3) launch_conv_taps<DT, 3, 3>(c, tp, grid, x, wp, bias, y, stats, s);
@@ -1171,7 +1078,7 @@ static void launch_conv(const ClassPlan &c, const uint16_t *x, const uint16_t *w
     else if (nty == 7 && g.ntx == 1) launch_conv_taps<DT, 7, 1>(c, tp, grid, x, wp, bias, y, stats, s);
     else if (nty == 1 && g.ntx == 7) launch_conv_taps<DT, 1, 7>(c, tp, grid, x, wp, bias, y, stats, s);
     else if (nty == 4 && g.ntx == 1) launch_conv_taps<DT, 4, 1>(c, tp, grid, x, wp, bias, y, stats, s);
-    // sub-pixel classes of the stride-2 transposed convolutions (3x3: 1x1, 1x2, 2x1, 2x2 taps; 4x4: 2x2)
+    // small tap grids: 2x2 / 2x1 / 1x2 / 1x1 kernels, and a transposed convolution that has a single sub-pixel class
     else if (nty == 2 && g.ntx == 2) launch_conv_taps<DT, 2, 2>(c, tp, grid, x, wp, bias, y, stats, s);
     else if (nty == 2 && g.ntx == 1) launch_conv_taps<DT, 2, 1>(c, tp, grid, x, wp, bias, y, stats, s);
     else if (nty == 1 && g.ntx == 2) launch_conv_taps<DT, 1, 2>(c, tp, grid, x, wp, bias, y, stats, s);
@@ -1227,7 +1134,7 @@ extern "C" int ir2rgb_conv2d_fwd_ws(const ir2rgb_conv_desc *d, const void *x, co
             conv_dot_kernel<IR2RGB_F16><<<grid, 256, 0, as_stream(stream)>>>((const uint16_t *)x, (const uint16_t *)wpacked, bias, (float *)y, g);
         return ir2rgb_launch_status();
     }
-    if (n > 1 && merge_classes()) {
+    if (n > 1) {
         // one launch for all classes: same pixel-tile size for all of them (plans were made with it)
         ConvClasses cs;
         int order[4] = {0, 1, 2, 3};
@@ -1260,12 +1167,9 @@ extern "C" int ir2rgb_conv2d_fwd_ws(const ir2rgb_conv_desc *d, const void *x, co
         }
         return ir2rgb_launch_status();
     }
-    for (int i = 0; i < n; ++i) {
-        const uint16_t *wp = reinterpret_cast<const uint16_t *>(wpacked) + plans[i].w_offset;
-        if (d->dtype == IR2RGB_BF16)
-            launch_conv<IR2RGB_BF16>(plans[i], (const uint16_t *)x, wp, bias, (uint16_t *)y, stats_partial, as_stream(stream));
-        else
-            launch_conv<IR2RGB_F16>(plans[i], (const uint16_t *)x, wp, bias, (uint16_t *)y, stats_partial, as_stream(stream));
-    }
+    if (d->dtype == IR2RGB_BF16)
+        launch_conv<IR2RGB_BF16>(plans[0], (const uint16_t *)x, (const uint16_t *)wpacked, bias, (uint16_t *)y, stats_partial, as_stream(stream));
+    else
+        launch_conv<IR2RGB_F16>(plans[0], (const uint16_t *)x, (const uint16_t *)wpacked, bias, (uint16_t *)y, stats_partial, as_stream(stream));
     return ir2rgb_launch_status();
 }

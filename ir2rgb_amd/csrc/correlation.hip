@@ -157,7 +157,7 @@ corr_fwd_tile(const float *__restrict__ f1, const float *__restrict__ f2, float 
 
 // ----------------------------------------------------------------------------------------
 // LDS-staged forward path (the default for the FlowNetC configuration; corr_fwd_tile above stays as the
-// fallback for channel counts that are not multiples of 8 and as the A/B reference, IR2RGB_CORR_LDS=0).
+// fallback for channel counts that are not multiples of 8 and for inputs of 2 GB and more).
 //
 // corr_fwd_tile feeds its FMAs straight from L2: per channel a lane issues 10 global_load_dwordx4 for 96 FMAs,
 // and the texture path hands a CU 64 B per clock -- 16 clocks per 1 KB wave-load, ~39 us of load issue chip-wide
@@ -176,8 +176,6 @@ corr_fwd_tile(const float *__restrict__ f1, const float *__restrict__ f2, float 
 // One s_barrier + one counted vmcnt per 8-channel stage.  Reduction and stores as in corr_fwd_tile.
 // ----------------------------------------------------------------------------------------
 typedef __attribute__((ext_vector_type(2))) float corr_f2;
-typedef __attribute__((address_space(3))) void *corr_lptr_t;
-#define CORR_OOB 0x80000000u
 
 template <int DR, int S2, int T0>
 __global__ void __launch_bounds__(256)
@@ -230,15 +228,14 @@ corr_fwd_lds(const float *__restrict__ f1, const float *__restrict__ f2, float *
         for (int k = 0; k < 4; ++k) acc[t][k] = (corr_f2){0.f, 0.f};
 
     if (row_ok) {
-        const __amdgpu_buffer_rsrc_t r1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(f1), 0, (int)in_bytes, 0x00020000);
-        const __amdgpu_buffer_rsrc_t r2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(f2), 0, (int)in_bytes, 0x00020000);
+        const rsrc_t r1 = make_rsrc(f1, in_bytes), r2 = make_rsrc(f2, in_bytes);
         // ---- per-lane DMA source offsets (bytes) of this wave's instructions: slot -> (tensor, row, chunk) ----
         unsigned voff[PERW];
 #pragma unroll
         for (int j = 0; j < PERW; ++j) {
             const int id = wave + 4 * j;                 // wave-uniform instruction id
             const int slot = id * 64 + lane;
-            unsigned v = CORR_OOB;
+            unsigned v = IR2RGB_OOB;
             if (id < NF1) {
                 const int row = slot / F1P, pos = slot - row * F1P, chunk = pos - ((row >> 1) & 1);
                 const int x = xc * 128 + 4 * chunk;
@@ -260,9 +257,9 @@ corr_fwd_lds(const float *__restrict__ f1, const float *__restrict__ f2, float *
 #pragma unroll
             for (int j = 0; j < PERW; ++j) {
                 const int id = wave + 4 * j;
-                if (id >= NDMA || !live) __builtin_amdgcn_raw_ptr_buffer_load_lds(r1, (corr_lptr_t)dummy, 16, CORR_OOB, 0, 0, 0);
-                else if (id < NF1) __builtin_amdgcn_raw_ptr_buffer_load_lds(r1, (corr_lptr_t)(dst + id * 1024), 16, voff[j], soff, 0, 0);
-                else __builtin_amdgcn_raw_ptr_buffer_load_lds(r2, (corr_lptr_t)(dst + id * 1024), 16, voff[j], soff, 0, 0);
+                if (id >= NDMA || !live) lds_dma16(r1, IR2RGB_OOB, 0, dummy);
+                else if (id < NF1) lds_dma16(r1, voff[j], soff, dst + id * 1024);
+                else lds_dma16(r2, voff[j], soff, dst + id * 1024);
             }
         };
         // ---- per-lane LDS read offsets: row = this lane's channel within the group of 8, shifted if cs is odd ----
@@ -459,10 +456,8 @@ extern "C" int ir2rgb_correlation_fwd(const float *in1, const float *in2, float 
     if (fast) {
         int xchunks = cdiv(W, 128);
         long units = (long)N * H * 21 * xchunks;  // (n, y, tj, xchunk): one workgroup each
-        static int use_lds = -1;
-        if (use_lds < 0) { const char *e = getenv("IR2RGB_CORR_LDS"); use_lds = e ? atoi(e) : 1; }
         const long in_bytes = (long)N * C * H * W * 4;
-        if (use_lds && (C % 8) == 0 && in_bytes < (1L << 31))
+        if ((C % 8) == 0 && in_bytes < (1L << 31))
             corr_fwd_lds<10, 2, 12><<<(unsigned)units, 256, 0, s>>>(in1, in2, out, C, H, W, xchunks, inv, (unsigned)in_bytes);
         else
             corr_fwd_tile<10, 2, 12><<<(unsigned)units, 256, 0, s>>>(in1, in2, out, C, H, W, xchunks, inv);

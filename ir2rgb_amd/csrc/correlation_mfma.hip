@@ -16,25 +16,6 @@
 // c ^ (j & 15) (conflict-free ds_read_b128 of a fragment: 16 pixels x 4 chunks).
 #include "common.h"
 
-typedef __attribute__((ext_vector_type(8))) __bf16 cm_bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 cm_f16x8;
-typedef __attribute__((ext_vector_type(4))) float cm_f32x4;
-typedef __attribute__((address_space(3))) void *cm_lptr_t;
-typedef __amdgpu_buffer_rsrc_t cm_rsrc_t;
-#define CM_OOB 0x80000000u
-
-template <int DT> struct CmHalf;
-template <> struct CmHalf<IR2RGB_BF16> {
-    typedef cm_bf16x8 frag;
-    static __device__ __forceinline__ cm_f32x4 mfma(frag a, frag b, cm_f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-    static __device__ __forceinline__ uint16_t cvt(float f) { __bf16 h = (__bf16)f; return __builtin_bit_cast(uint16_t, h); }
-};
-template <> struct CmHalf<IR2RGB_F16> {
-    typedef cm_f16x8 frag;
-    static __device__ __forceinline__ cm_f32x4 mfma(frag a, frag b, cm_f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-    static __device__ __forceinline__ uint16_t cvt(float f) { _Float16 h = (_Float16)f; return __builtin_bit_cast(uint16_t, h); }
-};
-
 struct CorrMfmaGeom {
     int N, H, W, C;
     int lda, offa, ldb, offb;        // channel-slice views of the two feature maps (elements)
@@ -49,7 +30,7 @@ constexpr int CM_RAD = 10, CM_D = 21, CM_NBUF = 4, CM_MAXC = 256, CM_NPX = 64;
 template <int DT, int OUT, int KC>
 __global__ void __launch_bounds__(384, 1)
 corr_mfma_kernel(const uint16_t *__restrict__ A, const uint16_t *__restrict__ B, void *__restrict__ out, const CorrMfmaGeom g) {
-    typedef CmHalf<DT> Hf;
+    typedef Half<DT> Hf;
     typedef typename Hf::frag frag;
     constexpr int KMAX = KC;                                                // K-steps of 32 channels: C / 32
     __shared__ __attribute__((aligned(1024))) unsigned char smem[CM_NBUF * CM_NPX * CM_MAXC * 2 + 1024 + 4 * 16 * CM_D * 4];
@@ -78,13 +59,13 @@ corr_mfma_kernel(const uint16_t *__restrict__ A, const uint16_t *__restrict__ B,
     if (wave >= 4) {
         // =============================== staging waves ===============================
         const int lw = wave - 4;
-        const cm_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t *>(B), 0, (int)g.b_bytes, 0x00020000);
+        const rsrc_t rb = make_rsrc(B, g.b_bytes);
         const int ninstr = rowbytes >> 10, per = (ninstr + 1) >> 1;        // 1 KB pieces per row, per staging wave (<= 16)
         unsigned voff[16];
 #pragma unroll
         for (int t = 0; t < 16; ++t) {
             const int pid = lw + 2 * t;
-            unsigned v = CM_OOB;
+            unsigned v = IR2RGB_OOB;
             if (t < per && pid < ninstr) {
                 const int slot = pid * 64 + lane, j = slot / cpp, cpos = slot - j * cpp;
                 const int c = cpos ^ (j & 15), x2 = 2 * j + p;
@@ -101,13 +82,13 @@ corr_mfma_kernel(const uint16_t *__restrict__ A, const uint16_t *__restrict__ B,
                 for (int t = 0; t < 16; ++t) {
                     const int pid = lw + 2 * t;
                     if (t < per && pid < ninstr)
-                        __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, (cm_lptr_t)(dst + pid * 1024), 16, voff[t], soff, 0, 0);
+                        lds_dma16(rb, voff[t], soff, dst + pid * 1024);
                     else
-                        __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, (cm_lptr_t)dummy, 16, CM_OOB, 0, 0, 0);
+                        lds_dma16(rb, IR2RGB_OOB, 0, dummy);
                 }
             } else {
 #pragma unroll
-                for (int t = 0; t < 16; ++t) __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, (cm_lptr_t)dummy, 16, CM_OOB, 0, 0, 0);
+                for (int t = 0; t < 16; ++t) lds_dma16(rb, IR2RGB_OOB, 0, dummy);
             }
         };
         issue(0); issue(1); issue(2);
@@ -163,9 +144,9 @@ corr_mfma_kernel(const uint16_t *__restrict__ A, const uint16_t *__restrict__ B,
     for (int s = 0; s < nv; ++s) {
         __builtin_amdgcn_s_barrier();                                      // row s has landed
         const unsigned char *row = smem + (s % CM_NBUF) * rowbytes;
-        cm_f32x4 acc[3];
+        f32x4 acc[3];
 #pragma unroll
-        for (int t = 0; t < 3; ++t) acc[t] = (cm_f32x4){0.f, 0.f, 0.f, 0.f};
+        for (int t = 0; t < 3; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
         if (have) {
             // straight-line: all 3 x KC fragment reads are issued before the first MFMA waits on one (blocks outside the row
             // image are read from a clamped address and their products dropped)
@@ -185,7 +166,7 @@ corr_mfma_kernel(const uint16_t *__restrict__ A, const uint16_t *__restrict__ B,
 #pragma unroll
             for (int t = 0; t < 3; ++t) {
                 const int jb = ib - 1 + t;
-                if (jb < 0 || jb > 3) acc[t] = (cm_f32x4){0.f, 0.f, 0.f, 0.f};
+                if (jb < 0 || jb > 3) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
             }
             // (the previous row's flush has read the tile: same wave, LDS operations of a wave complete in order)
 #pragma unroll

@@ -414,9 +414,7 @@ extern "C" int ir2rgb_bn_finalize_ex(const float *stats_partial, int rows, int C
         return ir2rgb_launch_status();
     }
     if (rows < 1 || count < 1 || !stats_partial || stat_updates < 1) return IR2RGB_EINVAL;
-    static int narrow = -1;     // IR2RGB_BN_FINALIZE_NARROW=0: 32-channel workgroups for every layer (A/B measurements)
-    if (narrow < 0) { const char *e = getenv("IR2RGB_BN_FINALIZE_NARROW"); narrow = e ? atoi(e) : 1; }
-    if (narrow && rows >= 2048 && C <= 256)
+    if (rows >= 2048 && C <= 256)
         bn_finalize_kernel<8><<<cdiv(C, 8), 1024, 0, as_stream(stream)>>>(stats_partial, rows, C, (double)count, gamma, beta,
                                                                          conv_bias, running_mean, running_var, momentum, eps,
                                                                          scale, shift, mean_out, invstd_out, stat_updates);

@@ -15,8 +15,8 @@
 // f(r) = (r & 3) | ((r >> 3) & 1) << 2, which makes the eight rows touched by one transposed read
 // (two 16-lane groups x 4 rows) hit 8 disjoint 32-byte bank windows.
 //
-// Workgroup = 256 threads (4 waves, 2x2), tile 128 (a) x 128 (b) for ONE tap and one K-split,
-// K-step = 64 pixels, two LDS stages (64 KB -> 2 workgroups per CU).  Split-K partial tiles go to
+// Workgroup = 512 threads (4 multiplying waves, 2x2, and 4 staging waves), tile 128 (a) x 128 (b) for ONE tap
+// and one K-split, K-step = 64 pixels, two LDS stages (64 KB -> 2 workgroups per CU).  Split-K partial tiles go to
 // per-split fp32 slabs [split][tap][a][b] with plain stores (no float atomics: they run at ~1.3 TB/s
 // chip-wide and are order-dependent); wgrad_finish sums the slabs and permutes into the torch weight
 // layout -- deterministic.  Algorithmic flops = 2 * Q * Ca * Cb * ntaps; bound: MFMA.
@@ -24,11 +24,7 @@
 
 #include "common.h"
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
 typedef __attribute__((ext_vector_type(8))) short s16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 struct WgradGeom {
     int N, Hq, Wq;          // pixel space of U (Q = N*Hq*Wq)
@@ -37,51 +33,26 @@ struct WgradGeom {
     int stride_y, stride_x, pad_mode;
     int nty, ntx, dy0, dx0; // tap (ty,tx): V coordinate = q*stride + (dy0+ty, dx0+tx)
     int ksplit, ksteps;     // K-steps (64 pixels each) in total and number of splits
-    int use_atomics;
     int tpb;                // taps per workgroup: 2 when Cb <= 64 (the two halves of the 128-column V tile hold two taps)
     FastDiv div_hw, div_w;  // exact division by Hq*Wq and by Wq
     unsigned u_bytes, v_bytes;  // extents of U and V (buffer resources, < 2^31)
 };
 
-typedef __attribute__((address_space(3))) void *lptr_t;
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
-#define WG_OOB 0x80000000u  // per-lane offset past any extent: the LDS-DMA delivers zeros
-
-__device__ __forceinline__ rsrc_t make_rsrc(const void *p, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, (int)bytes, 0x00020000);
+template <int DT>
+__device__ __forceinline__ f32x4 mfma_s16(s16x8 a, s16x8 b, f32x4 c) {
+    typedef typename Half<DT>::frag frag;
+    return Half<DT>::mfma(__builtin_bit_cast(frag, a), __builtin_bit_cast(frag, b), c);
 }
-// buffer-addressed LDS-DMA: 16 B per lane from base + 32-bit per-lane byte offset (range-checked, zeros
-// when out of range) to LDS at wave-uniform base + lane * 16
-__device__ __forceinline__ void dma16(rsrc_t r, unsigned voff, unsigned char *dst_wave_base) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lptr_t)dst_wave_base, 16, voff, 0, 0, 0);
-}
-
-__device__ __forceinline__ int reflect1(int v, int n) {
-    v = v < 0 ? -v : v;
-    return v >= n ? 2 * n - 2 - v : v;
-}
-
-template <int DT> struct Mfma;
-template <> struct Mfma<IR2RGB_BF16> {
-    static __device__ __forceinline__ f32x4 run(s16x8 a, s16x8 b, f32x4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-    }
-};
-template <> struct Mfma<IR2RGB_F16> {
-    static __device__ __forceinline__ f32x4 run(s16x8 a, s16x8 b, f32x4 c) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-    }
-};
 
 __device__ __forceinline__ s16x4 lds_tr(const unsigned char *p) {
     return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4 *)p);
 }
 
-// SPLIT = 1: 512 threads, waves 0..3 multiply and waves 4..7 only stage (as in conv_wgrad3x3_kernel): the eight LDS-DMA
-// issues of a K-step and their gather arithmetic leave the multiplying waves' instruction streams.  Measured on
-// 1024x1024x3x3 @32x64: 119.9 -> 102.4 us; training window 42.6 -> 42.2 ms.  Default (IR2RGB_WGRAD_SPLIT=0: one role).
-template <int DT, int SPLIT>
-__global__ void __launch_bounds__(SPLIT ? 512 : 256, 2)
+// 512 threads: waves 0..3 multiply and waves 4..7 only stage (as in conv_wgrad3x3_kernel): the eight LDS-DMA issues of a
+// K-step and their gather arithmetic leave the multiplying waves' instruction streams.  Measured against the 256-thread
+// form in which every wave did both, on 1024x1024x3x3 @32x64: 119.9 -> 102.4 us; training window 42.6 -> 42.2 ms.
+template <int DT>
+__global__ void __launch_bounds__(512, 2)
 conv_wgrad_kernel(const uint16_t *__restrict__ U, const uint16_t *__restrict__ V, float *__restrict__ D,
                   const WgradGeom g) {
     constexpr int STAGE = 2 * 64 * 256;  // U tile + V tile, 64 pixel rows x 256 B each
@@ -89,7 +60,7 @@ conv_wgrad_kernel(const uint16_t *__restrict__ U, const uint16_t *__restrict__ V
 
     const int tid0 = threadIdx.x, lane = tid0 & 63;
     const int wave8 = __builtin_amdgcn_readfirstlane(tid0 >> 6);
-    const bool loader = SPLIT && wave8 >= 4;
+    const bool loader = wave8 >= 4;
     const int wave = wave8 & 3;            // role-local wave index
     const int tid = tid0 & 255;            // role-local thread index
     const int nta = (g.Ca + 127) >> 7, ntb = (g.Cb + 127) >> 7;
@@ -125,8 +96,8 @@ conv_wgrad_kernel(const uint16_t *__restrict__ U, const uint16_t *__restrict__ V
     const int dy = g.dy0 + ty, dx = g.dx0 + tx;
     const bool a_ok = a0 + chunk * 8 < g.Ca, b_ok = vch < g.Cb && vtap < ntaps;
     const rsrc_t ru = make_rsrc(U, g.u_bytes), rv = make_rsrc(V, g.v_bytes);
-    const unsigned ubase = a_ok ? (unsigned)(a0 + chunk * 8) * 2u : WG_OOB;  // byte offset inside a pixel row
-    const unsigned vbase = b_ok ? (unsigned)vch * 2u : WG_OOB;
+    const unsigned ubase = a_ok ? (unsigned)(a0 + chunk * 8) * 2u : IR2RGB_OOB;  // byte offset inside a pixel row
+    const unsigned vbase = b_ok ? (unsigned)vch * 2u : IR2RGB_OOB;
     const unsigned Q = (unsigned)g.N * g.Hq * g.Wq, HWq = (unsigned)g.Hq * g.Wq;
     const unsigned ca2 = (unsigned)g.Ca * 2u, cb2 = (unsigned)g.Cb * 2u;
     unsigned char *const wave_dst = smem + wave * 1024;  // + buf*STAGE + 4096*i (+16384 for V)
@@ -135,13 +106,13 @@ conv_wgrad_kernel(const uint16_t *__restrict__ U, const uint16_t *__restrict__ V
     // one DMA pair (U row, gathered V row) for pixel q = (n, qy, qx); all selects, no branches
     auto issue_row = [&](unsigned q, unsigned n, unsigned qy, unsigned qx, unsigned char *dst) {
         const bool v = q < Q;
-        dma16(ru, v ? ubase + q * ca2 : WG_OOB, dst);
+        lds_dma16(ru, v ? ubase + q * ca2 : IR2RGB_OOB, 0, dst);
         int iy = (int)qy * g.stride_y + dy, ix = (int)qx * g.stride_x + dx;
         const bool inb = ((unsigned)iy < (unsigned)g.Hv) & ((unsigned)ix < (unsigned)g.Wv);
-        iy = g.pad_mode ? reflect1(iy, g.Hv) : iy;
-        ix = g.pad_mode ? reflect1(ix, g.Wv) : ix;
+        iy = g.pad_mode ? reflect(iy, g.Hv) : iy;
+        ix = g.pad_mode ? reflect(ix, g.Wv) : ix;
         const unsigned vp = (n * (unsigned)g.Hv + (unsigned)iy) * (unsigned)g.Wv + (unsigned)ix;
-        dma16(rv, (v && (g.pad_mode || inb)) ? vbase + vp * cb2 : WG_OOB, dst + 16384);
+        lds_dma16(rv, (v && (g.pad_mode || inb)) ? vbase + vp * cb2 : IR2RGB_OOB, 0, dst + 16384);
     };
     auto issue = [&](int ks, int buf) {
         unsigned char *dst = wave_dst + buf * STAGE;
@@ -204,28 +175,20 @@ conv_wgrad_kernel(const uint16_t *__restrict__ U, const uint16_t *__restrict__ V
 #pragma unroll
         for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
-    if constexpr (SPLIT) {
-        if (loader) {
-            issue(kbeg, 0);
-            int lb = 0;
-            for (int ks = kbeg; ks < kend; ++ks) {
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // step ks has landed
-                __builtin_amdgcn_s_barrier();                         // ... and step ks-1 has been consumed
-                if (ks + 1 < kend) issue(ks + 1, lb ^ 1);
-                lb ^= 1;
-            }
-            return;
-        }
-    } else {
+    if (loader) {
         issue(kbeg, 0);
+        int lb = 0;
+        for (int ks = kbeg; ks < kend; ++ks) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // step ks has landed
+            __builtin_amdgcn_s_barrier();                         // ... and step ks-1 has been consumed
+            if (ks + 1 < kend) issue(ks + 1, lb ^ 1);
+            lb ^= 1;
+        }
+        return;
     }
     int buf = 0;
     for (int ks = kbeg; ks < kend; ++ks) {
-        if constexpr (!SPLIT) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
-        if constexpr (!SPLIT) {
-            if (ks + 1 < kend) issue(ks + 1, buf ^ 1);
-        }
         const unsigned char *tile = smem + buf * STAGE;
         const unsigned char *pa[4], *pb[4];
 #pragma unroll
@@ -240,7 +203,7 @@ conv_wgrad_kernel(const uint16_t *__restrict__ U, const uint16_t *__restrict__ V
 #pragma unroll
             for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
-                for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = Mfma<DT>::run(a[mi], b[ni], acc[mi][ni]);
+                for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = mfma_s16<DT>(a[mi], b[ni], acc[mi][ni]);
         }
         buf ^= 1;
     }
@@ -376,13 +339,13 @@ conv_wgrad3x3_kernel(const uint16_t *__restrict__ U, const uint16_t *__restrict_
         const bool top = is_y == 0, bot = is_y == g.H - 1, first = is_seg == 0, last = is_seg == g.segs - 1;
         const int edge = (top ? 1 : 0) | (bot ? 2 : 0) | (first ? 4 : 0) | (last ? 8 : 0);
 #pragma unroll
-        for (int j = 0; j < 2; ++j) dma16(ru, live ? ubase + u_off[j] : WG_OOB, dst + 4096 * j);
+        for (int j = 0; j < 2; ++j) lds_dma16(ru, live ? ubase + u_off[j] : IR2RGB_OOB, 0, dst + 4096 * j);
 #pragma unroll
         for (int j = 0; j < 7; ++j) {
             const int o = vbase + v_L0[j] + (top ? v_fixU[j] : 0) + (bot ? v_fixD[j] : 0) + (first ? v_fixL[j] : 0) +
                           (last ? v_fixR[j] : 0);
             const bool off = v_dead[j] | !live | (!refl & ((v_edge[j] & edge) != 0));
-            dma16(rv, off ? WG_OOB : (unsigned)o, dst + 4096 * (j + 2));
+            lds_dma16(rv, off ? IR2RGB_OOB : (unsigned)o, 0, dst + 4096 * (j + 2));
         }
         ++is_ks;
         if (++is_seg == g.segs) {
@@ -485,7 +448,7 @@ conv_wgrad3x3_kernel(const uint16_t *__restrict__ U, const uint16_t *__restrict_
                     for (int mi = 0; mi < 4; ++mi) {
                         const s16x8 a = (s16x8){alo[KK][mi][0], alo[KK][mi][1], alo[KK][mi][2], alo[KK][mi][3],
                                                 ahi[KK][mi][0], ahi[KK][mi][1], ahi[KK][mi][2], ahi[KK][mi][3]};
-                        acc[T][mi] = Mfma<DT>::run(a, b, acc[T][mi]);
+                        acc[T][mi] = mfma_s16<DT>(a, b, acc[T][mi]);
                     }
                 };
                 [&]<int... Ss>(std::integer_sequence<int, Ss...>) { (step(std::integral_constant<int, Ss>{}), ...); }
@@ -574,13 +537,13 @@ conv_wgrad_line_kernel(const uint16_t *__restrict__ U, const uint16_t *__restric
             for (int j = 0; j < J; ++j) {
                 const int id = wave + 4 * j;           // wave-uniform
                 if (id >= NID) break;
-                unsigned off = WG_OOB;
+                unsigned off = IR2RGB_OOB;
                 if (id < 8) {                           // gradient rows: output pixels x0 + r of this row
                     const int r = id * 8 + rin;
                     const int chunk = (((sl >> 1) ^ fsw(r)) << 1) | (sl & 1);
                     if (x0 + r < g.Wq)
                         off = ((unsigned)is_row * (unsigned)g.Wq + (unsigned)(x0 + r)) * ca2 + (unsigned)(a0 + chunk * 8) * 2u;
-                    dma16(ru, off, dst + 4096 * j);
+                    lds_dma16(ru, off, 0, dst + 4096 * j);
                 } else {                                // patch rows: tap row pr, column pxl
                     const int R = (id - 8) * 8 + rin;
                     const int run = R / PW, pxl = R - run * PW;
@@ -589,8 +552,8 @@ conv_wgrad_line_kernel(const uint16_t *__restrict__ U, const uint16_t *__restric
                     int iy = is_y * g.stride_y + g.dy0 + pr;
                     int ix = SX == 2 ? 2 * x0 + g.dx0 + 2 * pxl + (run & 1) : x0 + pxl + g.dx0;
                     const bool inb = ((unsigned)iy < (unsigned)g.Hv) & ((unsigned)ix < (unsigned)g.Wv);
-                    iy = g.pad_mode ? reflect1(iy, g.Hv) : iy;
-                    ix = g.pad_mode ? reflect1(ix, g.Wv) : ix;
+                    iy = g.pad_mode ? reflect(iy, g.Hv) : iy;
+                    ix = g.pad_mode ? reflect(ix, g.Wv) : ix;
                     // (reflection of a column far right of a ragged last segment can still leave the row: such patch
                     // columns only ever meet gradient rows that are zero, any in-range address will do)
                     ix = min(max(ix, 0), g.Wv - 1);
@@ -598,7 +561,7 @@ conv_wgrad_line_kernel(const uint16_t *__restrict__ U, const uint16_t *__restric
                     if (R < PR && (g.pad_mode || inb))
                         off = (((unsigned)is_n * (unsigned)g.Hv + (unsigned)iy) * (unsigned)g.Wv + (unsigned)ix) * cb2 +
                               (unsigned)(b0 + chunk * 8) * 2u;
-                    dma16(rv, off, dst + 4096 * j);
+                    lds_dma16(rv, off, 0, dst + 4096 * j);
                 }
             }
             if (++is_seg == g.segs) {
@@ -657,7 +620,7 @@ conv_wgrad_line_kernel(const uint16_t *__restrict__ U, const uint16_t *__restric
                 const s16x4 lo = lds_tr(tile + boff[t][0] + kk * 4096), hi = lds_tr(tile + boff[t][1] + kk * 4096);
                 const s16x8 b = (s16x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
 #pragma unroll
-                for (int mi = 0; mi < 4; ++mi) acc[t][mi] = Mfma<DT>::run(a[mi], b, acc[t][mi]);
+                for (int mi = 0; mi < 4; ++mi) acc[t][mi] = mfma_s16<DT>(a[mi], b, acc[t][mi]);
             }
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this wave's reads of the stage have returned before it is handed back
@@ -718,14 +681,14 @@ conv_wgrad_col_kernel(const uint16_t *__restrict__ U, const uint16_t *__restrict
             for (int j = 0; j < JMAX; ++j) {
                 const int id = wave + 4 * j;           // wave-uniform
                 if (id >= total) break;
-                unsigned off = WG_OOB;
+                unsigned off = IR2RGB_OOB;
                 if (id < 8) {                           // gradient pixels x0 + r of output row y
                     const int r = id * 8 + rin;
                     const int chunk = (((sl >> 1) ^ fsw(r)) << 1) | (sl & 1);
                     if (x0 + r < g.Wq)
                         off = (((unsigned)n * (unsigned)g.Hq + (unsigned)y) * (unsigned)g.Wq + (unsigned)(x0 + r)) * ca2 +
                               (unsigned)(a0 + chunk * 8) * 2u;
-                    dma16(ru, off, smem + ub * 8192 + id * 1024);
+                    lds_dma16(ru, off, 0, smem + ub * 8192 + id * 1024);
                 } else {                                // input row y * SY + jt (virtual, before padding), pixels x0 + r
                     const int q = id - 8;
                     const int jt = (prime ? 0 : NTY - SY) + (q >> 3);
@@ -735,13 +698,13 @@ conv_wgrad_col_kernel(const uint16_t *__restrict__ U, const uint16_t *__restrict
                     int iy = v + g.dy0;
                     const int ix = x0 + r;
                     const bool inb = ((unsigned)iy < (unsigned)g.Hv) & (ix < g.Wv);
-                    iy = g.pad_mode ? reflect1(iy, g.Hv) : iy;
+                    iy = g.pad_mode ? reflect(iy, g.Hv) : iy;
                     iy = min(max(iy, 0), g.Hv - 1);
                     if (ix < g.Wv && (g.pad_mode || inb))
                         off = (((unsigned)n * (unsigned)g.Hv + (unsigned)iy) * (unsigned)g.Wv + (unsigned)ix) * cb2 +
                               (unsigned)(b0 + chunk * 8) * 2u;
                     const int slot = half * RC + v % RC;
-                    dma16(rv, off, smem + PATCH0 + slot * 8192 + (q & 7) * 1024);
+                    lds_dma16(rv, off, 0, smem + PATCH0 + slot * 8192 + (q & 7) * 1024);
                 }
             }
             first = false;
@@ -797,7 +760,7 @@ conv_wgrad_col_kernel(const uint16_t *__restrict__ U, const uint16_t *__restrict
                 const s16x4 lo = lds_tr(pt + boffl[0]), hi = lds_tr(pt + boffl[1]);
                 const s16x8 b = (s16x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
 #pragma unroll
-                for (int mi = 0; mi < 4; ++mi) acc[t][mi] = Mfma<DT>::run(a[mi], b, acc[t][mi]);
+                for (int mi = 0; mi < 4; ++mi) acc[t][mi] = mfma_s16<DT>(a[mi], b, acc[t][mi]);
             }
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this wave's reads have returned before the buffers are handed back
@@ -947,11 +910,7 @@ static int plan(const ir2rgb_conv_desc *d, WgradGeom *g) {
     g->ksteps = (int)((Q + 63) / 64);
     // K-split by a cost model: rounds of 512 resident workgroups (2 per CU) x (K-steps per split + pipeline
     // fill) against the extra slab traffic of the finish pass (split x elems x 8 bytes at ~4 TB/s).
-    {
-        static int pairs = -1;
-        if (pairs < 0) { const char *e = getenv("IR2RGB_WGRAD_TAP_PAIRS"); pairs = e ? atoi(e) : 1; }
-        g->tpb = (pairs && g->Cb <= 64 && d->kh * d->kw > 1) ? 2 : 1;
-    }
+    g->tpb = (g->Cb <= 64 && d->kh * d->kw > 1) ? 2 : 1;
     const long tiles = (long)((d->kh * d->kw + g->tpb - 1) / g->tpb) * ((g->Ca + 127) / 128) * ((g->Cb + 127) / 128);
     const double elems = (double)d->kh * d->kw * g->Ca * g->Cb;
     int best = 1;
@@ -963,7 +922,6 @@ static int plan(const ir2rgb_conv_desc *d, WgradGeom *g) {
         if (cost < best_cost) { best_cost = cost; best = ks; }
     }
     g->ksplit = best;
-    g->use_atomics = 0;
     g->div_hw = make_fastdiv((unsigned)(g->Hq * g->Wq)); g->div_w = make_fastdiv((unsigned)g->Wq);
     {
         const long ub = Q * g->Ca * 2, vb = (long)g->N * g->Hv * g->Wv * g->Cb * 2;
@@ -976,17 +934,12 @@ static int plan(const ir2rgb_conv_desc *d, WgradGeom *g) {
 // k x 1 / 1 x k layers on conv_wgrad_line_kernel: 7x1, 1x7 (stride 1 along the taps' axis is not required: the taps run
 // along y for k x 1, where the stride enters the row index) and the stride-2 4x1; 64-multiples on both channel axes.
 static bool plan_line(const ir2rgb_conv_desc *d, WgradLineGeom *g) {
-    static int on = -1;
-    if (on < 0) { const char *e = getenv("IR2RGB_WGRAD_LINE"); on = e ? atoi(e) : 1; }
-    if (!on || (d->Cin % 64) || (d->Cout % 64)) return false;
-    static int s2 = -1;             // IR2RGB_WGRAD_S2=0: the stride-2 3x3 layers on the one-tap kernel (A/B measurements)
-    if (s2 < 0) { const char *e = getenv("IR2RGB_WGRAD_S2"); s2 = e ? atoi(e) : 1; }
-    // (measured against the one-tap kernel, us at the training sizes: 64->128 @512x1024 49 vs 60, 512->1024 @64x128 54 vs 60,
+    if ((d->Cin % 64) || (d->Cout % 64)) return false;
+    // the stride-2 3x3 layers (measured against the one-tap kernel, us at the training sizes: 64->128 @512x1024 49 vs 60, 512->1024 @64x128 54 vs 60,
     // 1024->512 transposed 53 vs 58, 128->64 transposed 49 vs 56 -- but 128->256 52 vs 43, 256->512 48 vs 43: every 64 x 64
-    // tile restages the 57-KB patch, which only pays at the two ends of the channel range; s2 = 2 forces it everywhere)
+    // tile restages the 57-KB patch, which only pays at the two ends of the channel range)
     const long tl = (long)(d->Cout / 64) * (d->Cin / 64);
-    const bool k3s2 = s2 && d->kh == 3 && d->kw == 3 && d->stride_h == 2 && d->stride_w == 2 && d->pad_mode == 0 &&
-                      (s2 == 2 || tl <= 2 || tl >= 128);
+    const bool k3s2 = d->kh == 3 && d->kw == 3 && d->stride_h == 2 && d->stride_w == 2 && d->pad_mode == 0 && (tl <= 2 || tl >= 128);
     const bool k7x1 = d->kh == 7 && d->kw == 1, k1x7 = d->kh == 1 && d->kw == 7, k4x1 = d->kh == 4 && d->kw == 1;
     if (!k3s2 && (d->transposed || d->stride_w != 1)) return false;
     if (!(k7x1 || k1x7 || k4x1 || k3s2)) return false;
@@ -1023,20 +976,13 @@ static bool plan_line(const ir2rgb_conv_desc *d, WgradLineGeom *g) {
 template <int DT>
 static void launch_line(const ir2rgb_conv_desc *d, const WgradLineGeom &g, const uint16_t *U, const uint16_t *V, float *D, hipStream_t s) {
     const unsigned grid = (unsigned)((long)g.ksplit * (g.Ca / 64) * (g.Cb / 64));
-    static int ring = -1;           // IR2RGB_WGRAD_RING=0: the k x 1 layers on the row-major line kernel (A/B measurements)
-    if (ring < 0) { const char *e = getenv("IR2RGB_WGRAD_RING"); ring = e ? atoi(e) : 1; }
+    // (7x1 / 4x1 at another stride than the ring kernel's: the row-major line kernel)
     if (d->kh == 3 && d->kw == 3) conv_wgrad_line_kernel<DT, 3, 3, 2><<<grid, 512, 0, s>>>(U, V, D, g);
-    else if (d->kh == 7 && ring && d->stride_h == 1) conv_wgrad_col_kernel<DT, 7, 1><<<grid, 512, 0, s>>>(U, V, D, g);
-    else if (d->kh == 4 && ring && d->stride_h == 2) conv_wgrad_col_kernel<DT, 4, 2><<<grid, 512, 0, s>>>(U, V, D, g);
+    else if (d->kh == 7 && d->stride_h == 1) conv_wgrad_col_kernel<DT, 7, 1><<<grid, 512, 0, s>>>(U, V, D, g);
+    else if (d->kh == 4 && d->stride_h == 2) conv_wgrad_col_kernel<DT, 4, 2><<<grid, 512, 0, s>>>(U, V, D, g);
     else if (d->kh == 7) conv_wgrad_line_kernel<DT, 7, 1><<<grid, 512, 0, s>>>(U, V, D, g);
     else if (d->kw == 7) conv_wgrad_line_kernel<DT, 1, 7><<<grid, 512, 0, s>>>(U, V, D, g);
     else conv_wgrad_line_kernel<DT, 4, 1><<<grid, 512, 0, s>>>(U, V, D, g);
-}
-
-static bool use_wgrad9() {
-    static int v = -1;
-    if (v < 0) { const char *e = getenv("IR2RGB_WGRAD9"); v = e ? atoi(e) : 1; }
-    return v != 0;
 }
 
 extern "C" long ir2rgb_conv2d_wgrad_workspace_elems(const ir2rgb_conv_desc *d) {
@@ -1044,7 +990,7 @@ extern "C" long ir2rgb_conv2d_wgrad_workspace_elems(const ir2rgb_conv_desc *d) {
     int rc = plan(d, &g);
     if (rc) return rc;
     Wgrad9Geom g9;
-    if (use_wgrad9() && plan9(d, &g9)) return g9.ksplit > 1 ? (long)g9.ksplit * 9 * g9.Ca * g9.Cb : 4;
+    if (plan9(d, &g9)) return g9.ksplit > 1 ? (long)g9.ksplit * 9 * g9.Ca * g9.Cb : 4;
     WgradLineGeom gl;
     if (plan_line(d, &gl)) return (long)gl.ksplit * d->kh * d->kw * gl.Ca * gl.Cb;
     return (long)g.ksplit * d->kh * d->kw * g.Ca * g.Cb;
@@ -1084,7 +1030,7 @@ static int wgrad_impl(const ir2rgb_conv_desc *d, const void *x, const void *gy, 
     Wgrad9Geom g9;
     // accumulate mode (a parameter used several times per pass: the discriminators) sums in the finish pass of the
     // one-tap kernel; the nine-tap kernel's direct-write form has no such pass, so those layers take the one-tap kernel
-    if (!acc && use_wgrad9() && plan9(d, &g9)) {
+    if (!acc && plan9(d, &g9)) {
         if (((uintptr_t)dw | (uintptr_t)workspace) & 15) return IR2RGB_EALIGN;
         float *dst = g9.ksplit > 1 ? workspace : dw;
         const unsigned grid9 = (unsigned)((long)g9.ksplit * (g9.Ca / 64) * (g9.Cb / 64));
@@ -1103,15 +1049,8 @@ static int wgrad_impl(const ir2rgb_conv_desc *d, const void *x, const void *gy, 
         return ir2rgb_launch_status();
     }
     const unsigned grid = (unsigned)((long)g.ksplit * ((ntaps + g.tpb - 1) / g.tpb) * ((g.Ca + 127) / 128) * ((g.Cb + 127) / 128));
-    static int split = -1;
-    if (split < 0) { const char *e = getenv("IR2RGB_WGRAD_SPLIT"); split = e ? atoi(e) : 1; }
-    if (split) {
-        if (d->dtype == IR2RGB_BF16) conv_wgrad_kernel<IR2RGB_BF16, 1><<<grid, 512, 0, s>>>(U, V, workspace, g);
-        else conv_wgrad_kernel<IR2RGB_F16, 1><<<grid, 512, 0, s>>>(U, V, workspace, g);
-    } else {
-        if (d->dtype == IR2RGB_BF16) conv_wgrad_kernel<IR2RGB_BF16, 0><<<grid, 256, 0, s>>>(U, V, workspace, g);
-        else conv_wgrad_kernel<IR2RGB_F16, 0><<<grid, 256, 0, s>>>(U, V, workspace, g);
-    }
+    if (d->dtype == IR2RGB_BF16) conv_wgrad_kernel<IR2RGB_BF16><<<grid, 512, 0, s>>>(U, V, workspace, g);
+    else conv_wgrad_kernel<IR2RGB_F16><<<grid, 512, 0, s>>>(U, V, workspace, g);
     launch_wgrad_finish(workspace, dw, g.Ca, g.Cb, ntaps, g.ksplit, s, acc);
     return ir2rgb_launch_status();
 }
