@@ -238,7 +238,7 @@ def conv_dgrad(gy, conv, spec, x_shape, weight_fn=None, tag="dgrad", out=None):
 # Gradient sinks (data-parallel runs): weight parameter -> its slice of the optimizer's flat all-reduce buffer.  A
 # convolution whose weight is registered here writes its weight gradient straight into that slice and returns it, so
 # autograd adopts a tensor that already lives in the buffer and no gather copy precedes the all-reduce.  Only sound for
-# a parameter that receives ONE contribution per backward pass (the caller's promise: vid2vid.FlatGrads(direct=True)).
+# a parameter that receives ONE contribution per backward pass (the caller's promise: flatgrads.FlatGrads(direct=True)).
 GRAD_SINKS = {}
 
 
@@ -247,7 +247,7 @@ def wgrad_destination(weight, shape):
     handed for it: -> (out, accumulate, grad).  ``out`` None: a fresh tensor, which is then the gradient."""
     sink = GRAD_SINKS.get(weight) if GRAD_SINKS else None
     have = weight.grad
-    if (ACCUMULATE_IN_KERNEL and sink is None and have is not None and have.dtype is torch.float32 and have.is_contiguous()
+    if (sink is None and have is not None and have.dtype is torch.float32 and have.is_contiguous()
             and have.shape == weight.shape):
         # a later use of the same parameter in this pass (the discriminators see two or three inputs per window): dw is
         # added to .grad by the kernel's own finish pass; autograd gets nothing to add
@@ -292,22 +292,18 @@ def conv_wgrad(x, gy, weight_shape, spec, out=None, accumulate=False):
 # pass ends (engine callback).
 # Measured: with the one-tap weight-gradient kernel (126 us, half of the chip idle) the overlap saved 2 ms per
 # window; with the nine-tap kernel (44 us, every CU busy) it COSTS 1.7 ms (44.2 vs 42.5 ms per window): the
-# overlapped kernels slow the critical chain and the stream hand-offs add bubbles -- also when only the
-# remaining one-tap launches use the side stream (IR2RGB_WGRAD_STREAM=2: 44.3 ms).  Hence default off
-# (IR2RGB_WGRAD_STREAM=1 enables it; tests/test_losses_gpu.py keeps it covered).
+# overlapped kernels slow the critical chain and the stream hand-offs add bubbles (sending only the remaining one-tap
+# launches to the side stream measured no better: 44.3 ms).  Hence default off (IR2RGB_WGRAD_STREAM=1 enables it;
+# tests/test_losses_gpu.py keeps it covered).
 # ---------------------------------------------------------------------------------------------
 WGRAD_SIDE_STREAM = os.environ.get("IR2RGB_WGRAD_STREAM", "0") != "0"
-# "2": only weight gradients that do NOT fill the chip (strided / transposed / first layers, one-tap kernel) go to the
-# side stream; the nine-tap kernel of the residual blocks occupies every CU and slows the data-gradient chain it overlaps
-WGRAD_SIDE_SMALL_ONLY = os.environ.get("IR2RGB_WGRAD_STREAM", "0") == "2"
-_SIDE = {}
+_SIDE_PENDING = set()       # devices whose side stream the running backward pass has used
 
 
-def _join_side(dev_index):
-    st = _SIDE[dev_index]
-    st["pending"] = False
+def _join_side(dev, side):
+    _SIDE_PENDING.discard(dev)
     C.SIDE_BUSY = False
-    torch.cuda.current_stream(dev_index).wait_stream(st["stream"])
+    torch.cuda.current_stream(dev).wait_stream(side)
 
 
 def enable_side_wgrad(module, enabled=True):
@@ -329,13 +325,8 @@ def wgrad_overlapped(conv, fn, *inputs):
         # the gradient goes straight into the all-reduce buffer, and the hook that puts its chunk on the wire runs on the
         # main stream: it must not overtake a kernel on the side stream
         return fn()
-    if WGRAD_SIDE_SMALL_ONLY and tuple(conv.kernel_size) == (3, 3) and tuple(conv.stride) == (1, 1) and \
-            not isinstance(conv, torch.nn.ConvTranspose2d) and conv.in_channels >= 64:
-        return fn()
-    st = _SIDE.get(dev.index)
-    if st is None:
-        st = _SIDE[dev.index] = {"stream": torch.cuda.Stream(dev), "pending": False}
-    main, side = torch.cuda.current_stream(dev), st["stream"]
+    from .networks import SLOT_WGRAD, side_stream      # (networks imports this module)
+    main, side = torch.cuda.current_stream(dev), side_stream(dev, SLOT_WGRAD)
     if param.grad is not None:
         main.wait_stream(side)
         return fn()
@@ -345,10 +336,10 @@ def wgrad_overlapped(conv, fn, *inputs):
     for t in inputs:
         t.record_stream(side)
     out.record_stream(main)
-    if not st["pending"]:
-        st["pending"] = True
+    if dev not in _SIDE_PENDING:
+        _SIDE_PENDING.add(dev)
         C.SIDE_BUSY = True
-        torch.autograd.Variable._execution_engine.queue_callback(lambda: _join_side(dev.index))
+        torch.autograd.Variable._execution_engine.queue_callback(lambda: _join_side(dev, side))
     return out
 
 
@@ -364,7 +355,6 @@ def wgrad_overlapped(conv, fn, *inputs):
 #                     discriminator's pass: nothing flows back into the generator)
 # ---------------------------------------------------------------------------------------------
 SKIP_PARAM_GRADS, SKIP_INPUT_GRAD = 1, 2
-ACCUMULATE_IN_KERNEL = os.environ.get("IR2RGB_WGRAD_ACC", "1") != "0"    # dw += inside the weight-gradient kernel (see backward)
 FUSED_BN = os.environ.get("IR2RGB_FUSED_BN", "1") != "0"    # bn_finalize + bn_apply in one launch where the statistics are few rows
 
 

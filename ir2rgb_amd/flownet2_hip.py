@@ -14,6 +14,7 @@ same buffers.  Left on torch (tiny 2..12-channel fp32 tensors): the x4 interpola
 normalisation / concatenation glue of FlowNet2.forward.
 """
 import ctypes
+import os
 
 import torch
 import torch.nn.functional as F
@@ -155,7 +156,6 @@ def corr_nhwc(mod, av, bv, yv, slope):
     cfg = tuple(getattr(mod, k, None) for k in ("pad_size", "kernel_size", "max_displacement", "stride1", "stride2"))
     if cfg != (20, 1, 20, 1, 2) or getattr(mod, "corr_multiply", 1) != 1 or yv.ch != 441 or av.ch != bv.ch:
         return False
-    import os
     if os.environ.get("IR2RGB_CORR_MFMA", "1") == "0":
         return False
     n = av.n

@@ -10,8 +10,6 @@ and returns an fp32 tensor ``[nslots]``; each term adds ``weight * mean(...)`` i
 Gradients flow to every ``a`` that requires them (one launch for the whole group).  These are the
 reference's criterionFeat / criterionGAN / criterionFlow terms (discriminator.py:154-210, loss.py).
 """
-import ctypes
-
 import torch
 from torch.autograd import Function
 
@@ -60,14 +58,25 @@ def _build_items(terms, tensors, grads):
     return arr
 
 
-# Gradient destinations: (data_ptr, shape, dtype) of a loss input -> the tensor its gradient is to be written into
-# (vid2vid.split_groups registers the pieces of a batched discriminator output with their slices of ONE gradient buffer,
-# so the pieces' gradients need no gather copy).  The destination itself is returned as the gradient.
+# Gradient destinations: (data_ptr, shape, dtype) of a loss input -> (the tensor its gradient is to be written into, the
+# ``owner`` module of the network that produced the input).  split_groups below registers the pieces of a batched
+# discriminator output with their slices of ONE gradient buffer, so the pieces' gradients need no gather copy; the
+# destination itself is returned as the gradient.  The dict is keyed by address, so an entry must not outlive the tensor
+# it describes: it lives from one forward of its network to that network's next (drop_grad_dsts), at most one window.
 GRAD_DST = {}
 
 
 def _dst_key(t):
     return (t.data_ptr(), tuple(t.shape), t.dtype)
+
+
+def drop_grad_dsts(owner=None):
+    """Forget the destinations registered for ``owner``'s outputs (split_groups); None: all of them."""
+    if owner is None:
+        GRAD_DST.clear()
+        return
+    for k in [k for k, v in GRAD_DST.items() if v[1] is owner]:
+        del GRAD_DST[k]
 
 
 # A destination is written ONCE per backward pass: a second term that differentiates the same piece in the same pass (the
@@ -78,13 +87,55 @@ _DST_USED = set()
 
 def _take_dst(t):
     key = _dst_key(t)
-    g = GRAD_DST.get(key)
-    if g is None or key in _DST_USED:
+    ent = GRAD_DST.get(key)
+    if ent is None or key in _DST_USED:
         return None
     if not _DST_USED:
         torch.autograd.Variable._execution_engine.queue_callback(_DST_USED.clear)     # (when this backward pass ends)
     _DST_USED.add(key)
-    return g
+    return ent[0]
+
+
+class _SplitGroupsFn(Function):
+    """t [G * n, ...] -> G views [n, ...]; backward: the pieces' gradients in ONE buffer of t's layout (autograd's own
+    slicing would allocate and fill a full-size zero tensor per piece and add them up; materialised zero gradients would
+    also arrive NCHW-contiguous and drag the whole buffer out of NHWC).  The buffer exists from the forward on and its
+    slices are registered as the gradient destinations of the pieces (GRAD_DST): a fused loss kernel that
+    differentiates a piece writes straight into it, anything else is copied in; a piece without gradient is zero-filled
+    unless its sample group is inactive in this pass (``owner._ir2rgb_active``, autograd.backward_flags: nobody reads it)."""
+
+    @staticmethod
+    def forward(ctx, t, G, owner):
+        n = t.shape[0] // G
+        ctx.set_materialize_grads(False)
+        ctx.G, ctx.n, ctx.owner = G, n, owner
+        fmt = torch.channels_last if t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last) else torch.contiguous_format
+        ctx.buf = torch.empty(tuple(t.shape), dtype=t.dtype, device=t.device, memory_format=fmt)
+        pieces = tuple(t[g * n:(g + 1) * n] for g in range(G))
+        for g, piece in enumerate(pieces):
+            GRAD_DST[_dst_key(piece)] = (ctx.buf[g * n:(g + 1) * n], owner)
+        return pieces
+
+    @staticmethod
+    def backward(ctx, *grads):
+        if all(g is None for g in grads):
+            return None, None, None
+        out, n = ctx.buf, ctx.n
+        active = getattr(ctx.owner, "_ir2rgb_active", None) if ctx.owner is not None else None
+        for i, g in enumerate(grads):
+            dst = out[i * n:(i + 1) * n]
+            if g is None:
+                if active is None or i < active:
+                    dst.zero_()
+            elif g.data_ptr() != dst.data_ptr():
+                dst.copy_(g)
+        return out, None, None
+
+
+def split_groups(t, G, owner=None):
+    """``owner``: a convolution module of the network that produced ``t`` (carries the pass's active-group flag, and names
+    the network to drop_grad_dsts)."""
+    return _SplitGroupsFn.apply(t, G, owner)
 
 
 class _FusedLossFn(Function):

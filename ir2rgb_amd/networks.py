@@ -189,12 +189,35 @@ import contextlib as _contextlib
 import os as _os
 
 BRANCH_STREAMS = _os.environ.get("IR2RGB_BRANCH_STREAMS", "auto")   # "auto" | "1" | "0" | set by branch_streams()
+
+# Every side stream of the package comes from side_stream(): a process's streams are the main one plus the slots below that
+# it has used.  They are created at first use, never ahead of it: the runtime maps streams to the device's four hardware
+# queues in creation order.  What runs where, in a training window:
+#   main                      everything else; the image discriminator's finest scale
+#   SLOT_FLOWNET              FlowNet2's graph replay and the real-frame bookkeeping, beside the generator forward
+#   SLOT_BRANCH               the generators' second branch (forwards without autograd; finer scales when training)
+#   SLOT_D_SCALE1 + i - 1     scale i >= 1 of the image discriminator.  Scale 1 SHARES the generators' branch stream, which
+#                             is idle while the discriminators run, so that fewer streams compete for the four queues
+#                             (26.2-27.0 ms per window against 26.4-27.9 with a stream of its own, same box;
+#                             GPU_MAX_HW_QUEUES=6 / 8 made the window 45 % SLOWER: the streams are fitted to the queues, not
+#                             the other way round)
+#   SLOT_D_TEMPORAL + s       temporal discriminator s, forward and backward
+#   SLOT_WGRAD                weight gradients beside the data-gradient chain (autograd.WGRAD_SIDE_STREAM, off by default)
+# The default trainer (two image scales, two temporal scales) so opens main + four: FlowNet2, branch / image scale 1, and
+# one per temporal discriminator.
+SLOT_BRANCH = SLOT_D_SCALE1 = 0
+SLOT_D_TEMPORAL = 16
+SLOT_FLOWNET, SLOT_WGRAD = 32, 33
 _SIDE_STREAMS = {}
-# side-stream slot of the image discriminator's scale 1 (scale i: + i - 1).  Default 0 = the generators' second-branch
-# stream, which is idle while the discriminators run, so that fewer streams compete for the device's four hardware queues
-# (26.2-27.0 ms per window against 26.4-27.9 with a stream of its own, same box; GPU_MAX_HW_QUEUES=6 / 8 made the window
-# 45 % SLOWER: the streams are fitted to the queues, not the other way round).
-_D_SCALE_SLOT0 = int(_os.environ.get("IR2RGB_D_SCALE_SLOT", "0"))
+
+
+def side_stream(device, slot):
+    """The side stream of ``device`` for ``slot`` (SLOT_*), created at first use."""
+    key = (device.index, slot)
+    st = _SIDE_STREAMS.get(key)
+    if st is None:
+        st = _SIDE_STREAMS[key] = torch.cuda.Stream(device)
+    return st
 
 
 @_contextlib.contextmanager
@@ -212,12 +235,11 @@ class _Branch:
     """``with _Branch(x) as b: y = f(x)`` runs the body on the device's side stream after everything queued on the
     current stream; ``b.join(y, ...)`` makes the current stream wait for it and returns the tensors."""
 
-    def __init__(self, *inputs, owner=None, slot=0, force=None):
+    def __init__(self, *inputs, owner=None, slot=SLOT_BRANCH, force=None):
         self.inputs = [t for t in inputs if isinstance(t, torch.Tensor)]
         # (``owner.branch_streams_training``: a module may ask for two streams also while autograd records -- the trainer
         # sets it on the finer spatial scales, whose kernels bench.py does not bracket)
-        # ``slot``: which of the device's side streams (0: the generators' second branch; the discriminators use their own,
-        # see MultiScaleDiscriminator.forward and Vid2VidTrainer.train_window).  ``force``: the caller decides (True / False)
+        # ``slot``: which of the device's side streams (SLOT_*, see side_stream).  ``force``: the caller decides (True / False)
         # instead of IR2RGB_BRANCH_STREAMS.
         if force is None:
             on = BRANCH_STREAMS == "1" or (BRANCH_STREAMS == "auto" and (not torch.is_grad_enabled() or
@@ -232,10 +254,7 @@ class _Branch:
         if self.enabled:
             dev = self.inputs[0].device
             self.main = torch.cuda.current_stream(dev)
-            key = dev.index if self.slot == 0 else (dev.index, self.slot)
-            self.side = _SIDE_STREAMS.get(key)
-            if self.side is None:
-                self.side = _SIDE_STREAMS[key] = torch.cuda.Stream(dev)
+            self.side = side_stream(dev, self.slot)
             self.side.wait_stream(self.main)
             for t in self.inputs:
                 t.record_stream(self.side)
@@ -531,7 +550,7 @@ class MultiScaleDiscriminator(nn.Module):
                 xs.append(A.avg_pool3s2(xs[-1]))
             pending = []
             for i in range(1, self.num_D):
-                br = _Branch(xs[i], slot=_D_SCALE_SLOT0 + i - 1, force=True)
+                br = _Branch(xs[i], slot=SLOT_D_SCALE1 + i - 1, force=True)
                 with br:
                     outs = _run_patchgan(self._groups(self.num_D - 1 - i), xs[i], self.compute_dtype, self.training,
                                          sample_groups, group_order)

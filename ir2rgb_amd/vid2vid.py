@@ -22,11 +22,14 @@ import torch.distributed as dist
 import torch.nn.functional as F
 
 from . import autograd, layers, networks
+from . import conv as _conv
 from . import streamcheck as SC
-from .losses import fused_losses
-from .optim import FusedAdam
-from .ext import warp_diff_norm
+from .flatgrads import FlatGrads
+from .flownet import FlowNet
 from .frames import FrameHistory
+from .losses import _SplitGroupsFn, drop_grad_dsts, fused_losses, split_groups  # noqa: F401  (re-exported)
+from .networks import SLOT_D_TEMPORAL, SLOT_FLOWNET, _Branch, side_stream
+from .optim import FusedAdam
 
 DEFAULTS = dict(  # options/base_options.py, options/train_options.py
     input_nc=3, output_nc=3, n_input_gen_frames=3, first_layer_gen_filters=128, gen_network="composite", gen_ds_layers=3,
@@ -46,9 +49,8 @@ DEFAULTS = dict(  # options/base_options.py, options/train_options.py (SURVEY se
     batched_repack=True,  # all packed weight copies refreshed by one launch after the optimizer steps (layers.WeightRepacker)
     build_flow_net=True,  # False: trainer.flow_net is left None for the caller to set (tests plug a stand-in for FlowNet2)
     branch_streams_fine_scales=True,   # the finer spatial scales' generators run their two branches on two HIP streams, forward
-    discriminator_streams=True,        # the image discriminator's scales and the temporal discriminators each on their own HIP stream (forward and, through autograd, backward): independent networks of small layers that fill a fraction of the chip one at a time
-    adam_stream=False,                 # the generators' Adam step on its own HIP stream beside the discriminators' backward passes: measured again in round 3 with the discriminators on their own streams, 26.9 ms per window against 26.3 without (round 1: 39.05 vs 38.8) -- off
                                        # and backward (the coarsest scale's kernels are what bench.py brackets: one stream)
+    discriminator_streams=True,        # the image discriminator's scales and the temporal discriminators each on their own HIP stream (forward and, through autograd, backward): independent networks of small layers that fill a fraction of the chip one at a time
 )
 
 
@@ -97,48 +99,6 @@ def gan_loss(pred, real):
     return total
 
 
-class _SplitGroupsFn(torch.autograd.Function):
-    """t [G * n, ...] -> G views [n, ...]; backward: the pieces' gradients in ONE buffer of t's layout (autograd's own
-    slicing would allocate and fill a full-size zero tensor per piece and add them up; materialised zero gradients would
-    also arrive NCHW-contiguous and drag the whole buffer out of NHWC).  The buffer exists from the forward on and its
-    slices are registered as the gradient destinations of the pieces (losses.GRAD_DST): a fused loss kernel that
-    differentiates a piece writes straight into it, anything else is copied in; a piece without gradient is zero-filled
-    unless its sample group is inactive in this pass (``owner._ir2rgb_active``, autograd.backward_flags: nobody reads it)."""
-
-    @staticmethod
-    def forward(ctx, t, G, owner):
-        from . import losses
-        n = t.shape[0] // G
-        ctx.set_materialize_grads(False)
-        ctx.G, ctx.n, ctx.owner = G, n, owner
-        fmt = torch.channels_last if t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last) else torch.contiguous_format
-        ctx.buf = torch.empty(tuple(t.shape), dtype=t.dtype, device=t.device, memory_format=fmt)
-        pieces = tuple(t[g * n:(g + 1) * n] for g in range(G))
-        for g, piece in enumerate(pieces):
-            losses.GRAD_DST[losses._dst_key(piece)] = ctx.buf[g * n:(g + 1) * n]
-        return pieces
-
-    @staticmethod
-    def backward(ctx, *grads):
-        if all(g is None for g in grads):
-            return None, None, None
-        out, n = ctx.buf, ctx.n
-        active = getattr(ctx.owner, "_ir2rgb_active", None) if ctx.owner is not None else None
-        for i, g in enumerate(grads):
-            dst = out[i * n:(i + 1) * n]
-            if g is None:
-                if active is None or i < active:
-                    dst.zero_()
-            elif g.data_ptr() != dst.data_ptr():
-                dst.copy_(g)
-        return out, None, None
-
-
-def split_groups(t, G, owner=None):
-    """``owner``: a convolution module of the network that produced ``t`` (carries the pass's active-group flag)."""
-    return _SplitGroupsFn.apply(t, G, owner)
-
-
 @contextlib.contextmanager
 def frozen(module):
     ps = [p for p in module.parameters() if p.requires_grad]
@@ -149,283 +109,6 @@ def frozen(module):
     finally:
         for p in ps:
             p.requires_grad_(True)
-
-
-class FlowNet(torch.nn.Module):
-    """Frozen FlowNet2 + confidence mask (models/flownet.py)."""
-
-    def __init__(self, conv_dtype=torch.bfloat16, seed=1, use_graph=None):
-        super().__init__()
-        from .flownet2_pytorch.models import FlowNet2
-        import os
-        self.use_graph = (os.environ.get("IR2RGB_FLOWNET_GRAPH", "1") != "0") if use_graph is None else bool(use_graph)
-        self._graphs = {}   # shape key -> call count | (graph, in1, in2, (flow, conf)) | False (capture failed)
-        rng = torch.random.get_rng_state()
-        torch.manual_seed(seed)  # no checkpoint offline: the reference's own init (models.py:68-77)
-        self.flowNet = FlowNet2(conv_dtype=conv_dtype)
-        torch.random.set_rng_state(rng)
-        self.flowNet.eval()
-        for p in self.flowNet.parameters():
-            p.requires_grad_(False)
-
-    @torch.no_grad()
-    def forward(self, input_A, input_B, side=None):
-        """``side``: a HIP stream a graph REPLAY of this call may run on (see Vid2VidTrainer.train_window); calls that
-        still have lazy work to do (eager warm-up, capture) stay on the current stream.  ``self.ran_on`` tells which."""
-        if input_A.dim() == 5:
-            b, n, c, h, w = input_A.shape
-            flow, conf = self.compute_flow_and_conf(input_A.reshape(-1, c, h, w), input_B.reshape(-1, c, h, w), side)
-            return flow.view(b, n, 2, h, w), conf.view(b, n, 1, h, w)
-        return self.compute_flow_and_conf(input_A, input_B, side)
-
-    def will_replay(self, n, im):
-        """True when a call on ``n`` frame pairs shaped like ``im`` [., 3, H, W] would be a graph replay (no lazy work)."""
-        return isinstance(self._graphs.get(((n,) + tuple(im.shape[1:]), im.dtype, str(im.device))), tuple)
-
-    def compute_flow_and_conf(self, im1, im2, side=None):
-        """FlowNet2 is frozen, runs without autograd and with fixed shapes: ~330 small launches per call.
-        After two eager calls at a shape the whole call (convolutions, operators, interpolations, the
-        confidence mask) is captured into a HIP graph and replayed -- one launch, no host work between
-        the kernels.  Any failure to capture falls back to the eager path for that shape (logged once)."""
-        self.ran_on = None
-        key = (tuple(im1.shape), im1.dtype, str(im1.device))
-        ent = self._graphs.get(key)
-        if not self.use_graph or not im1.is_cuda or ent is False:
-            return self._flow_and_conf_eager(im1, im2)
-        if ent is None or isinstance(ent, int):
-            n = (ent or 0) + 1
-            self._graphs[key] = n
-            if n <= 2:
-                return self._flow_and_conf_eager(im1, im2)
-            try:
-                a, b = im1.clone(), im2.clone()
-                torch.cuda.synchronize(im1.device)
-                g = torch.cuda.CUDAGraph()
-                # (with a process group alive its watchdog thread polls events meanwhile: only this thread's calls are
-                # subject to the capture rules then)
-                mode = "thread_local" if dist.is_available() and dist.is_initialized() else "global"
-                with torch.cuda.graph(g, capture_error_mode=mode):
-                    out = self._flow_and_conf_eager(a, b)
-                ent = self._graphs[key] = (g, a, b, out)
-            except Exception as e:  # noqa: BLE001  capture is an optimisation, never a requirement
-                self._graphs[key] = False
-                print(f"[ir2rgb_amd] FlowNet2 graph capture failed at {key[0]} ({type(e).__name__}: {e}); staying eager",
-                      flush=True)
-                return self._flow_and_conf_eager(im1, im2)
-        g, a, b, (flow, conf) = ent
-        if side is not None and torch.cuda.current_stream(im1.device) == side:
-            # the caller already works on the second stream (Vid2VidTrainer.reference_flows, resident inputs): no wait
-            a.copy_(im1)
-            b.copy_(im2)
-            g.replay()
-            self.ran_on = side
-            out = flow.clone(), conf.clone()
-            if SC.ENABLED:
-                SC.produced(out[0], "reference flow (FlowNet2 replay)"), SC.produced(out[1], "flow confidence (FlowNet2 replay)")
-            return out
-        if side is not None:
-            main = torch.cuda.current_stream(im1.device)
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                a.copy_(im1)
-                b.copy_(im2)
-                g.replay()
-                out = flow.clone(), conf.clone()
-                if SC.ENABLED:
-                    SC.produced(out[0], "reference flow (FlowNet2 replay)"), SC.produced(out[1], "flow confidence (FlowNet2 replay)")
-            for t in (im1, im2):
-                t.record_stream(side)
-            self.ran_on = side
-            return out
-        a.copy_(im1)
-        b.copy_(im2)
-        g.replay()
-        return flow.clone(), conf.clone()   # the graph owns its outputs: the next replay overwrites them
-
-    def _flow_and_conf_eager(self, im1, im2):
-        assert im1.size(1) == 3 and im1.shape == im2.shape
-        old_h, old_w = im1.shape[2:]
-        new_h, new_w = old_h // 64 * 64, old_w // 64 * 64
-        resize = old_h != new_h      # flownet.py:42 tests the height only ...
-        if not resize and old_w != new_w:
-            # ... and with a width that is not a multiple of 64 the reference dies in FlowNet2's torch.cat
-            raise ValueError(f"FlowNet: width {old_w} is not a multiple of 64 while height {old_h} is "
-                             "(the reference resizes only when the height is off, flownet.py:42)")
-        if resize:
-            im1 = F.interpolate(im1, size=(new_h, new_w), mode="bilinear")
-            im2 = F.interpolate(im2, size=(new_h, new_w), mode="bilinear")
-        flow = self.flowNet(torch.stack([im1, im2], dim=2)).float().contiguous()
-        _, _, norm = warp_diff_norm(im1.float().contiguous(), im2.float().contiguous(), flow, want_warped=False,
-                                    want_diff=False)
-        conf = (norm * norm < 0.02).float()  # flownet.py:50,56-57: sum of squares < 0.02
-        if resize:
-            flow = F.interpolate(flow, size=(old_h, old_w), mode="bilinear") * old_h / new_h
-            conf = F.interpolate(conf, size=(old_h, old_w), mode="bilinear")
-        return flow, conf
-
-
-class FlatGrads:
-    """One flat fp32 gradient buffer per optimizer.  ``zero`` drops the .grad references, so the first
-    contribution of a backward pass is adopted by autograd without an add kernel per parameter;
-    ``all_reduce_async`` makes every .grad a view of the flat buffer and, for world > 1, issues a chunked
-    RCCL all-reduce (~128 MB per collective) that AVERAGES (ReduceOp.AVG: no scaling pass over the buffer).
-    A parameter that received no gradient gets a zero one, as the reference's zero_grad() + Adam step would
-    see (train_vid2vid.py:93-105).
-
-    ``direct=True`` (world > 1, every parameter used once per backward pass -- the generators): the convolutions
-    write their weight gradients straight into their slices (ir2rgb_amd.autograd.GRAD_SINKS), so 99.9 % of the
-    buffer is in place when the pass ends; the rest (biases, BatchNorm parameters, first / thin / padded layers) is
-    gathered by one multi-tensor copy, as everything is when ``direct`` is off (the discriminators: several
-    contributions per parameter and pass, summed by the autograd engine before they are adopted).  The in-place
-    weights sit at the front of the buffer in parameter order, cut into chunks; a chunk goes onto the wire from the
-    autograd hook of the parameter that completes it, i.e. WHILE the backward pass is still running (the generators'
-    1.4 GB of residual-block gradients are produced over the last ~5 ms of their pass: the all-reduce then ends about
-    when the pass does instead of starting there); ``all_reduce_async`` sends what is left."""
-
-    def __init__(self, params, chunk_elems=32 * 1024 * 1024, world=1, direct=False):
-        self.params = [p for p in params if p.requires_grad]
-        pad4 = lambda k: (k + 3) & ~3  # noqa: E731  every view starts on a 16-byte boundary (vector path of adam_kernel)
-        n = sum(pad4(p.numel()) for p in self.params)
-        dev = self.params[0].device
-        self.flat = torch.zeros(n, dtype=torch.float32, device=dev)
-        self.direct = bool(direct and world > 1)
-        # layout: with ``direct`` the convolution weights (written in place by their weight-gradient kernels) come first,
-        # in parameter order, so that whole chunks of the buffer are complete -- and can be all-reduced -- while the
-        # backward pass is still running; biases / BatchNorm parameters (gathered by one copy when the pass ends) follow
-        is_sink = [self.direct and p.dim() == 4 for p in self.params]
-        order = [i for i, s in enumerate(is_sink) if s] + [i for i, s in enumerate(is_sink) if not s]
-        self.views, off = [None] * len(self.params), 0
-        starts = {}
-        for i in order:
-            p = self.params[i]
-            starts[i] = off
-            self.views[i] = self.flat[off:off + p.numel()].view_as(p)
-            off += pad4(p.numel())
-        self.chunk = chunk_elems
-        self.handles = []
-        self.scale_after = None
-        # early chunks: [lo, hi) ranges of the sink region, each a list of parameter indices; a chunk is all-reduced from
-        # the autograd hook of the parameter whose gradient completes it (all_reduce_async picks up what is left)
-        self.chunks, self._fired, self._pending, self._issued, self._world = [], set(), [], [], world
-        self._direct_capable, self._sink_ids = self.direct, []
-        if self.direct:
-            cur, lo = [], 0
-            sink_ids = self._sink_ids = [i for i in order if is_sink[i]]
-            for k, i in enumerate(sink_ids):
-                cur.append(i)
-                hi = starts[i] + pad4(self.params[i].numel())
-                if hi - lo >= chunk_elems or k == len(sink_ids) - 1:
-                    self.chunks.append((lo, hi, tuple(cur)))
-                    cur, lo = [], hi
-            self.sink_end = self.chunks[-1][1] if self.chunks else 0
-            chunk_of = {i: c for c, (_, _, ids) in enumerate(self.chunks) for i in ids}
-            for i in sink_ids:
-                p = self.params[i]
-                autograd.GRAD_SINKS[p] = self.views[i]
-                p.register_post_accumulate_grad_hook(self._make_hook(i, chunk_of[i]))
-        else:
-            self.sink_end = 0
-
-    def set_direct(self, on):
-        """Arm / disarm the in-place sinks for the backward passes to come.  They are only sound while every parameter
-        receives ONE contribution per pass: a window that generates several frames applies each generator several times,
-        and a second contribution would overwrite the first in the same slice (autograd then sums two aliases of it) --
-        the trainer switches to the gathered form for such windows (Vid2VidTrainer.generate)."""
-        on = bool(on) and self._direct_capable
-        if on == self.direct:
-            return
-        self.direct = on
-        for i in self._sink_ids:
-            if on:
-                autograd.GRAD_SINKS[self.params[i]] = self.views[i]
-            else:
-                autograd.GRAD_SINKS.pop(self.params[i], None)
-        self._pending, self._issued = [], []
-
-    def _make_hook(self, i, c):
-        def hook(p):
-            if not self._pending or i in self._fired:
-                return
-            self._fired.add(i)
-            if p.grad is None or p.grad.data_ptr() != self.views[i].data_ptr():
-                self._pending[c] = -1                      # this gradient is not in place: the chunk waits for the gather
-                return
-            if self._pending[c] > 0:
-                self._pending[c] -= 1
-                if self._pending[c] == 0:
-                    lo, hi, _ = self.chunks[c]
-                    self._reduce(lo, hi)
-                    self._issued[c] = True
-        return hook
-
-    def _reduce(self, lo, hi):
-        avg = dist.get_backend() == "nccl"     # RCCL averages in the collective; gloo (CPU tests) has no AVG
-        self.scale_after = None if avg else 1.0 / self._world
-        for i in range(lo, hi, self.chunk):
-            self.handles.append(dist.all_reduce(self.flat[i:min(i + self.chunk, hi)], op=dist.ReduceOp.AVG if avg else dist.ReduceOp.SUM,
-                                                async_op=True))
-
-    def zero(self):
-        for p in self.params:
-            p.grad = None
-        if self.direct:      # arm the early chunks for the backward pass that follows
-            self._fired = set()
-            self._pending = [len(ids) for _, _, ids in self.chunks]
-            self._issued = [False] * len(self.chunks)
-
-    def all_reduce_async(self, world):
-        self._world = world
-        src, dst, missing = [], [], []
-        for p, v in zip(self.params, self.views):
-            if p.grad is None:
-                missing.append(v)
-                p.grad = v
-            elif world > 1 and p.grad.data_ptr() != v.data_ptr():
-                src.append(p.grad)
-                dst.append(v)
-                p.grad = v
-            elif world > 1:
-                p.grad = v              # written in place by its convolution (GRAD_SINKS)
-        issued, self._pending = self._issued, []           # (disarm the hooks)
-        if missing:
-            if any(issued):
-                lo_hi = [(lo, hi) for (lo, hi, _), done in zip(self.chunks, issued) if done]
-                base = self.flat.data_ptr()
-                for v in missing:       # a parameter without gradient inside a chunk that is already on the wire cannot happen:
-                    o = (v.data_ptr() - base) // 4          # its chunk never completes
-                    assert not any(lo <= o < hi for lo, hi in lo_hi), "FlatGrads: early chunk reduced before it was complete"
-            torch._foreach_zero_(missing)      # one multi-tensor launch instead of one fill per parameter
-        if world <= 1:
-            return
-        if src:
-            torch._foreach_copy_(dst, src)
-        # what the hooks have not sent: unfinished chunks of the sink region (merged into runs), then the gathered tail
-        run = None
-        for (lo, hi, _), done in zip(self.chunks, issued or [False] * len(self.chunks)):
-            if done:
-                if run is not None:
-                    self._reduce(*run)
-                    run = None
-            else:
-                run = (lo, hi) if run is None else (run[0], hi)
-        tail_lo = self.sink_end
-        if run is not None:
-            tail_lo = run[0]
-        self._reduce(tail_lo, self.flat.numel())
-        self._issued = []
-
-    def wait(self):
-        for h in self.handles:
-            h.wait()
-        self.handles = []
-        if self.scale_after is not None:
-            self.flat.mul_(self.scale_after)
-            self.scale_after = None
-
-
-# IR2RGB_D_T_SLOTS=own (default): one stream per temporal discriminator; shared: both on one (measured slower: 27.4 vs
-# 26.2-27.0 ms per window on the same box)
-_T_SLOTS = os.environ.get("IR2RGB_D_T_SLOTS", "own")
 
 
 class _LossDict(dict):
@@ -459,29 +142,26 @@ class Vid2VidTrainer:
         for m in self.netG + [self.netD] + self.netD_T:
             m.to(device).train()
             m.compute_dtype = o["compute_dtype"]
-        import os
-        # gloo (the CPU-side rehearsal backend) moves CUDA tensors through the host and synchronises the device: next to it a
-        # second stream under autograd is pathological (the two-rank rehearsal of bench.py: 7.9 s per window with the
-        # finer-scale generators' branches on two streams, 0.39 s without; the discriminators' streams cost 30 ms there).
-        # RCCL ranks keep all streams (tests/test_rccl_gpu.py).
-        gloo = world_size > 1 and dist.is_available() and dist.is_initialized() and dist.get_backend() != "nccl"
-        fine = os.environ.get("IR2RGB_BRANCH_FINE", "0" if gloo else "1") != "0"
+        # ---- the schedule: every stream decision and every environment variable the trainer honours, read once
+        cuda = device.type == "cuda"
+        # gloo (the CPU-side rehearsal backend of bench.py) moves CUDA tensors through the host and synchronises the device:
+        # next to it a second stream is pathological (two-rank rehearsal: 7.9 s per window with the finer-scale generators'
+        # branches on two streams, 0.39 s without; 7.6 s with FlowNet2's replay on a second stream, 0.43 s on the main one;
+        # the discriminators' streams cost 30 ms there).  RCCL ranks keep all streams (tests/test_rccl_gpu.py: bit-identical
+        # to the single-process trainer next to RCCL's collectives).
+        gloo = world_size > 1 and not (dist.is_available() and dist.is_initialized() and dist.get_backend() == "nccl")
         for g in self.netG[1:]:
-            g.branch_streams_training = bool(o["branch_streams_fine_scales"]) and fine
-        self.d_streams = bool(o["discriminator_streams"]) and os.environ.get("IR2RGB_D_STREAMS", "1") != "0" and device.type == "cuda"
-        self.adam_stream_on = os.environ.get("IR2RGB_ADAM_STREAM", "1" if o["adam_stream"] else "0") != "0" and device.type == "cuda"
-        self._adam_stream, self._adam_pending = None, False
+            g.branch_streams_training = bool(o["branch_streams_fine_scales"]) and not gloo
+        self.d_streams = bool(o["discriminator_streams"]) and cuda
         self.netD.scale_streams = self.d_streams
         # FlowNet2 is replayed from a HIP graph in every configuration (a capture next to a process group runs in
-        # thread-local mode, FlowNet.compute_flow_and_conf), on its own stream -- also for data-parallel ranks on RCCL
-        # (tests/test_rccl_gpu.py: bit-identical to the single-process trainer next to RCCL's collectives).  Only the gloo
-        # rehearsal of bench.py keeps it on the main stream: gloo moves CUDA tensors through the host and synchronises
-        # (7.6 s per window measured with the replay on a second stream, 0.43 s on the main one).  IR2RGB_FLOW_STREAM_DP=0/1
-        # overrides.
+        # thread-local mode, FlowNet.compute_flow_and_conf), on its own stream unless IR2RGB_FLOW_STREAM=0 (or gloo)
+        self.flow_stream_on = cuda and not gloo and os.environ.get("IR2RGB_FLOW_STREAM", "1") != "0"
         self.flow_net = None
         if o["build_flow_net"]:
             self.flow_net = FlowNet(o["flownet_dtype"], use_graph=None).to(device)
         self._side_wgrad = None          # set per window in generate(): safe only when n_load == 1
+        self.last_outputs = None         # (fake_B, fake_B_raw, flow, weight) of the last train_window
         self.vgg_loss = None
         if not o["no_vgg"]:
             from .vgg import VGGLoss
@@ -507,21 +187,10 @@ class Vid2VidTrainer:
         self.reset_sequence()
 
     def _flow_stream(self, t):
-        """The side stream FlowNet2 runs on (None: same stream as everything else; IR2RGB_FLOW_STREAM=0 or CPU tensors)."""
-        import os
-        if not t.is_cuda or os.environ.get("IR2RGB_FLOW_STREAM", "1") == "0":
+        """The side stream FlowNet2 runs on (None: same stream as everything else)."""
+        if not self.flow_stream_on or not t.is_cuda or not isinstance(self.flow_net, FlowNet):
             return None
-        if self.world > 1:
-            dp = os.environ.get("IR2RGB_FLOW_STREAM_DP")
-            if dp is None:
-                dp = "1" if (dist.is_available() and dist.is_initialized() and dist.get_backend() == "nccl") else "0"
-            if dp != "1":
-                return None
-        if not isinstance(self.flow_net, FlowNet):
-            return None
-        if getattr(self, "_flow_side", None) is None:
-            self._flow_side = torch.cuda.Stream(t.device)
-        return self._flow_side
+        return side_stream(t.device, SLOT_FLOWNET)
 
     # ------------------------------------------------------------------ per-sequence state
     def reset_sequence(self):
@@ -601,7 +270,7 @@ class Vid2VidTrainer:
         [G_GAN, G_GAN_Feat], each already summed over the inputs.  (Two groups, not one: a backward pass then differentiates
         only the group its total depends on, and every prediction tensor receives one gradient per pass.)  The real
         logits appear in one term of weight len(pred_fakes): the reference evaluates that term once per compute_loss_D call
-        on identical activations -- two terms on one tensor would write one gradient destination twice (losses.GRAD_DST)."""
+        on identical activations -- two terms on one tensor would write one gradient destination twice (losses._take_dst)."""
         o = self.opt
         fw, dw = 4.0 / (o["n_layers_D"] + 1), 1.0 / o["num_D"]
         k = float(len(pred_fakes))
@@ -651,23 +320,18 @@ class Vid2VidTrainer:
         how often its batch statistics enter the running statistics; ``order``: the order the groups' statistics enter
         them in).  Callers put the generated frames FIRST: the generator's backward pass then works on the leading
         groups only (autograd.backward_flags(active_groups=...)).  -> one prediction pyramid per input."""
-        from . import losses as _losses
         G = len(inputs)
+        owner = next(m for m in netD.modules() if isinstance(m, torch.nn.Conv2d))
         # gradient destinations registered by this network's previous forward are dropped here: an entry lives from one
-        # forward of a network to its next, whoever the caller is (losses.GRAD_DST is keyed by address)
-        keys = self.__dict__.setdefault("_dst_keys", {})
-        for k in keys.pop(id(netD), ()):
-            _losses.GRAD_DST.pop(k, None)
-        before = set(_losses.GRAD_DST)
+        # forward of a network to its next, whoever the caller is (the registry is keyed by address)
+        drop_grad_dsts(owner)
         with layers.repeated_forward(tuple(repeats)):
             out = netD(torch.cat(inputs, 0), sample_groups=G, group_order=order)
-        owner = next(m for m in netD.modules() if isinstance(m, torch.nn.Conv2d))
         preds = [[[] for _ in out] for _ in range(G)]
         for i, scale in enumerate(out):
             for t in scale:
                 for g, piece in enumerate(split_groups(t, G, owner)):
                     preds[g][i].append(piece)
-        keys[id(netD)] = [k for k in _losses.GRAD_DST if k not in before]
         return preds
 
     def image_losses(self, real_B, fake_B, fake_B_raw, real_A, real_B_prev, fake_B_prev, flow, weight, flow_ref, conf_ref):
@@ -757,8 +421,7 @@ class Vid2VidTrainer:
             if not self._early_on:                          # first time: the histories were last written on the main stream
                 side.wait_stream(main)
                 self._early_on = True
-            import os
-            if self._backward_done is not None and os.environ.get("IR2RGB_FLOW_BOUND", "1") == "1":
+            if self._backward_done is not None:
                 # not before the previous window's generator backward pass is through: the host runs windows ahead of the
                 # GPU, and a FlowNet2 that started whenever it was issued would also share the chip with that pass's
                 # compute-bound convolutions (no gain, and it spoils bench.py's per-kernel brackets); beside the
@@ -884,11 +547,10 @@ class Vid2VidTrainer:
             loss_D_T.append((lt["D_T_fake"] + lt["D_T_real"]) * 0.5)
         return loss_G, loss_D, loss_D_T
 
-    def backward_passes(self, loss_G, loss_D, loss_D_T, g_inputs=None, early_adam=False):
+    def backward_passes(self, loss_G, loss_D, loss_D_T, g_inputs=None):
         """The three ``loss.backward()`` of train_vid2vid.py:104-111 (zero_grad included); each optimizer's gradient
         all-reduce is issued as soon as its pass ends, so it overlaps the next pass.  ``g_inputs``: the tensors
-        the generator's pass differentiates with respect to (default: the generator parameters).  ``early_adam`` (train_window):
-        the generators' optimizer step is issued right after their pass, on its own stream; optimizer_steps() then skips it."""
+        the generator's pass differentiates with respect to (default: the generator parameters)."""
         self.grads_G.zero()
         self.grads_D.zero()
         for gdt in self.grads_DT:
@@ -910,18 +572,6 @@ class Vid2VidTrainer:
             if self._backward_done is None:
                 self._backward_done = torch.cuda.Event()
             self._backward_done.record()
-        if self.adam_stream_on and early_adam:
-            # The generators' optimizer step needs nothing but their finished pass: it starts here, on its own stream, beside
-            # the discriminators' backward passes (which never touch generator weights or gradients) -- 2 ms of pure HBM
-            # streaming next to small latency-bound launches.  optimizer_steps() joins it before the repack.
-            main = torch.cuda.current_stream(self.device)
-            if self._adam_stream is None:
-                self._adam_stream = torch.cuda.Stream(self.device)
-            self._adam_stream.wait_stream(main)
-            with torch.cuda.stream(self._adam_stream):
-                self.grads_G.wait()
-                self.optimizer_G.step()
-            self._adam_pending = True
         with autograd.backward_flags(d_nets if shared else [], autograd.SKIP_INPUT_GRAD):
             if self.d_streams and shared and loss_D_T:
                 # one pass over the three disjoint graphs: every node runs on the stream of its forward, so the
@@ -943,18 +593,13 @@ class Vid2VidTrainer:
 
     def optimizer_steps(self, n_temporal):
         """The three ``optimizer.step()`` of train_vid2vid.py:104-111, then one launch refreshing every packed weight."""
-        if self._adam_pending:          # (issued by backward_passes on the Adam stream)
-            self._adam_pending = False
-        else:
-            self.grads_G.wait()
-            self.optimizer_G.step()
+        self.grads_G.wait()
+        self.optimizer_G.step()
         self.grads_D.wait()
         self.optimizer_D.step()
         for s in range(n_temporal):
             self.grads_DT[s].wait()
             self.optimizer_D_T[s].step()
-        if self._adam_stream is not None:
-            torch.cuda.current_stream(self.device).wait_stream(self._adam_stream)
         if self.repacker is not None:
             self.repacker.run()          # every packed forward / data-gradient weight copy, one launch
 
@@ -963,8 +608,7 @@ class Vid2VidTrainer:
         ``D_T{s}`` and every term under the reference's names (``G_GAN`` ... ``W``; temporal ones with the scale
         appended, ``G_T_GAN0`` ...).  ``self.last_outputs`` keeps (fake_B, fake_B_raw, flow, weight), detached."""
         fake_prev_last = self.fake_B_prev
-        from . import losses as _losses
-        _losses.GRAD_DST.clear()            # (gradient destinations of the previous window's discriminator outputs)
+        drop_grad_dsts()                    # (gradient destinations of the previous window's discriminator outputs)
         # The reference flows depend on real frames only (train_vid2vid.py:62-65 computes them after the generator, from
         # real_Bp = input_B[:, tG-2:]): FlowNet2 -- frozen, no autograd, replayed from a HIP graph from its third call at a
         # shape on -- runs on a second HIP stream BESIDE the generator forward and is joined before the losses that read
@@ -975,7 +619,6 @@ class Vid2VidTrainer:
         side = self._flow_stream(input_B)
         flow_ref, conf_ref, rb_s, extra_flows = self.reference_flows(real_Bp_in[:, 1:], real_Bp_in[:, :-1], side)
         ran_on = getattr(self.flow_net, "ran_on", None)
-        from . import conv as _conv
         _conv.SIDE_BUSY = ran_on is not None        # (per-launch timing brackets skip kernels that share the chip)
         fake_B, fake_B_raw, flow, weight, real_A, real_Bp = self.generate(input_A, input_B)
         _conv.SIDE_BUSY = False
@@ -996,6 +639,9 @@ class Vid2VidTrainer:
         if fake_B.size(1) > 1:
             fbp = torch.cat([fbp, fake_B[:, :-1].detach()], 1)
         flat = lambda t: t.reshape((-1,) + tuple(t.shape[2:]))  # noqa: E731
+        # (a reshape that has to copy is a launch: evaluated where image_losses is called, not here)
+        image_args = lambda: [flat(t) for t in (real_B, fake_B, fake_B_raw, real_A, real_B_prev, fbp, flow, weight,  # noqa: E731
+                                                flow_ref, conf_ref)]
         if SC.ENABLED:      # the losses read FlowNet2's results on this stream
             SC.consumed(flow_ref, "reference flow (FlowNet2 replay)"), SC.consumed(conf_ref, "flow confidence (FlowNet2 replay)")
         if self.d_streams:
@@ -1003,29 +649,26 @@ class Vid2VidTrainer:
             # far: the generator and the frame bookkeeping), then the image discriminator on the main stream: four
             # independent networks of small layers side by side instead of one after the other.  The streams are joined
             # before the totals; the backward passes follow the forward streams (autograd), see backward_passes.
-            from .networks import _Branch
             rb_s, fb_s, fl_s, cf_s = self.skipped_frames(rb_s, extra_flows, fake_B, flow_ref, conf_ref)
             active = [s for s in range(self.t_scales) if rb_s[s] is not None]
             LT, joins = [], []
             for s in active:
-                br = _Branch(rb_s[s], fb_s[s], fl_s[s], cf_s[s], slot=16 + (s if _T_SLOTS == "own" else 0), force=True)
+                br = _Branch(rb_s[s], fb_s[s], fl_s[s], cf_s[s], slot=SLOT_D_TEMPORAL + s, force=True)
                 with br:
                     lt = self.temporal_losses(s, rb_s[s], fb_s[s], fl_s[s], cf_s[s])
                 LT.append(lt)
                 joins.append((br, lt))
-            L = self.image_losses(flat(real_B), flat(fake_B), flat(fake_B_raw), flat(real_A), flat(real_B_prev), flat(fbp),
-                                  flat(flow), flat(weight), flat(flow_ref), flat(conf_ref))
+            L = self.image_losses(*image_args())
             for br, lt in joins:
                 vec = getattr(lt, "vecs", None)
                 br.join(*(list(lt.values()) + ([v for v in vec if v is not None] if vec else [])))
         else:
-            L = self.image_losses(flat(real_B), flat(fake_B), flat(fake_B_raw), flat(real_A), flat(real_B_prev), flat(fbp),
-                                  flat(flow), flat(weight), flat(flow_ref), flat(conf_ref))
+            L = self.image_losses(*image_args())
             rb_s, fb_s, fl_s, cf_s = self.skipped_frames(rb_s, extra_flows, fake_B, flow_ref, conf_ref)
             active = [s for s in range(self.t_scales) if rb_s[s] is not None]
             LT = [self.temporal_losses(s, rb_s[s], fb_s[s], fl_s[s], cf_s[s]) for s in active]
         loss_G, loss_D, loss_D_T = self.get_losses(L, LT)
-        self.backward_passes(loss_G, loss_D, loss_D_T, early_adam=True)
+        self.backward_passes(loss_G, loss_D, loss_D_T)
         self.optimizer_steps(len(loss_D_T))
         self.last_outputs = tuple(t.detach() for t in (fake_B, fake_B_raw, flow, weight))
         out = {"G": loss_G.detach(), "D": loss_D.detach()}
