@@ -414,6 +414,30 @@ int ir2rgb_adam_chunk_elems(void);
 int ir2rgb_adam_step(const void *table, const void *blocks, int nblocks, float lr, float beta1, float beta2, float eps,
                      int step, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Frame I/O of frame-by-frame inference (frame_io.hip): the 8-bit image boundary and the recurrence state
+ * as device-resident histories.  A history is fp32 [T][C][H][W], oldest frame first; both entry points move
+ * slots 1..T-1 down to 0..T-2 in place (same element index, same thread) and fill slot T-1.  Rows whose
+ * width is a multiple of 4 with 16-byte aligned bases take 16-byte accesses, everything else the scalar
+ * form; float pointers that are not 4-byte aligned are IR2RGB_EALIGN.  No buffer may alias another.
+ * ------------------------------------------------------------------------------------------ */
+
+/* One new input frame.  frame: uint8 [H][W][C] interleaved (src_f32 0) or an already normalised fp32
+ * [C][H][W] frame (src_f32 1); C in {1, 3}.  hist0 [T][C][H][W] receives (float(v) / 255 - 0.5) / 0.5 with
+ * correctly rounded divisions, i.e. transforms.ToTensor + Normalize(0.5, 0.5) (reference
+ * data/transform.py:82-85).  hist1, when not NULL, is the half-resolution history
+ * [T][C][(H-1)/2+1][(W-1)/2+1] and receives AvgPool2d(3, 2, 1, count_include_pad=False) of the new frame
+ * (base_model.py:64-82), bit-identical to ir2rgb_avgpool3s2 of the new hist0 slot.  Coarser levels: call
+ * ir2rgb_avgpool3s2 on the newest slot of the level above. */
+int ir2rgb_frame_push_u8(const void *frame, float *hist0, float *hist1, int T, int C, int H, int W, int src_f32,
+                         void *stream);
+
+/* One generated frame.  x: fp32 [3][H][W] (the output of ir2rgb_warp_blend_fwd or ir2rgb_head_finish) ->
+ * the newest slot of hist [T][3][H][W] (torch.cat([prev[1:], fake_B]), generator.py:214) and, when img_u8 is
+ * not NULL, the uint8 [H][W][3] image trunc(clip((x + 1) / 2 * 255, 0, 255)) in fp32 in that order
+ * (util.tensor2im, util/util.py:45-67). */
+int ir2rgb_frame_finish_u8(const float *x, float *hist, uint8_t *img_u8, int T, int H, int W, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,3 +5,13 @@ include/ir2rgb_hip.h).  Importing the package never touches the GPU; the library
 first use and its absence is an error (there is no CPU fallback).
 """
 __version__ = "0.1.0"
+
+__all__ = ["VideoTranslator"]
+
+
+def __getattr__(name):
+    # resolved on first use: importing the package stays free of torch and of the GPU
+    if name == "VideoTranslator":
+        from .inference import VideoTranslator
+        return VideoTranslator
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

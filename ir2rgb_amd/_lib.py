@@ -98,6 +98,8 @@ PROTOTYPES = {
     "ir2rgb_loss_multi_bwd": (c_int, [_pitem, c_int, c_int, P, P]),
     "ir2rgb_adam_chunk_elems": (c_int, []),
     "ir2rgb_adam_step": (c_int, [P, P, c_int, c_float, c_float, c_float, c_float, c_int, P]),
+    "ir2rgb_frame_push_u8": (c_int, [P, P, P] + [c_int] * 5 + [P]),
+    "ir2rgb_frame_finish_u8": (c_int, [P, P, P] + [c_int] * 3 + [P]),
 }
 
 _lib = None
