@@ -395,7 +395,8 @@ typedef struct ir2rgb_loss_item {
 
 /* Floats of `partial` scratch that ir2rgb_loss_multi_fwd needs. */
 int ir2rgb_loss_partial_elems(void);
-/* out[0 .. max slot] = the summed terms (slots no term names are not written). */
+/* out[0 .. max slot] = the summed terms: every slot up to the largest one named is written, and one of them that no
+ * term names receives 0; slots above the largest named one are not written. */
 int ir2rgb_loss_multi_fwd(const ir2rgb_loss_item *items, int count, int dtype, float *partial, float *out,
                           void *stream);
 /* Writes items[i].ga for every item that has one; gout = gradient w.r.t. out (device, fp32). */

@@ -46,13 +46,29 @@ def finalize(rows, count, gamma, beta, conv_bias, rm, rv, momentum, eps, updates
     shift = beta - mean * scale
     e_shift = FIN * (np.abs(beta) + np.abs(mean * scale)) + np.abs(mean) * e_scale
     keep = (1.0 - momentum) ** updates
-    unbiased = var * count / (count - 1.0)
+    # (count == 1: nn.BatchNorm2d refuses one value per channel; the kernels then keep the biased variance, 0)
+    unbiased = var * count / (count - 1.0) if count > 1 else var
     rm_new = keep * rm + (1.0 - keep) * (mean + conv_bias)
     rv_new = keep * rv + (1.0 - keep) * unbiased
     return dict(mean=(mean, FIN * np.abs(mean)), invstd=(invstd, e_inv), scale=(scale, e_scale),
                 shift=(shift, e_shift),
                 running_mean=(rm_new, updates * FIN * (np.abs(rm) + np.abs(mean) + np.abs(conv_bias))),
                 running_var=(rv_new, updates * FIN * (np.abs(rv) + unbiased) + e_var))
+
+
+def finalize_frozen(gamma, beta, conv_bias, rm, rv, eps):
+    """Evaluation mode (ir2rgb_bn_finalize_ex, frozen != 0): scale / shift / mean / invstd from the running statistics,
+    formed in fp32 by the kernel (the sum, the root and the quotient of invstd, then products and differences: each result
+    within FIN of the magnitudes that enter it, and the errors of its inputs carried through)."""
+    invstd = 1.0 / np.sqrt(rv + eps)
+    e_inv = FIN * invstd
+    mu = rm - conv_bias
+    e_mu = FIN * (np.abs(rm) + np.abs(conv_bias))
+    scale = gamma * invstd
+    e_scale = FIN * np.abs(scale) + np.abs(gamma) * e_inv
+    shift = beta - mu * scale
+    e_shift = FIN * (np.abs(beta) + np.abs(mu * scale)) + np.abs(mu) * e_scale + np.abs(scale) * e_mu
+    return dict(mean=(mu, e_mu), invstd=(invstd, e_inv), scale=(scale, e_scale), shift=(shift, e_shift))
 
 
 def apply(y, scale, shift, act, res1, res2, fmt, e_scale=0.0, e_shift=0.0):
@@ -79,9 +95,10 @@ def sign_safe(y, scale, shift):
     return np.abs(pre) > 64 * B.U32 * (np.abs(y * scale) + np.abs(shift))
 
 
-def bwd(gz, y, scale, shift, mean, invstd, act, fmt, base=None):
+def bwd(gz, y, scale, shift, mean, invstd, act, fmt, base=None, frozen=False):
     """fp64 backward of act + BatchNorm (scale None: activation only).  gz / y [P, C] fp64 of half values, the vectors
-    [C] fp64 of fp32 values.  base = (dgamma0, dbeta0) of the accumulating form.  -> dict name -> (ref, bound)."""
+    [C] fp64 of fp32 values.  base = (dgamma0, dbeta0) of the accumulating form.  frozen: evaluation-mode statistics
+    (act | 16) -- mean / invstd are constants, gy = scale * g', the sums as in training.  -> dict name -> (ref, bound)."""
     n = gz.shape[0]
     chain = B.b_rw(n + 2)
     u = B.U_OUT[fmt]
@@ -97,9 +114,13 @@ def bwd(gz, y, scale, shift, mean, invstd, act, fmt, base=None):
         db, dg = gp.sum(0), (gp * yhat).sum(0)
         e_db = chain * np.abs(gp).sum(0) + FIN * np.abs(db)
         e_dg = chain * np.abs(gp * yhat).sum(0) + FIN * np.abs(dg)
-        gy = scale * (gp - db / n - yhat * dg / n)
-        mag = np.abs(scale) * (np.abs(gp) + np.abs(db) / n + np.abs(yhat * dg) / n)
-        e_gy = np.abs(scale) * (e_db / n + np.abs(yhat) * e_dg / n) + FIN * mag
+        if frozen:
+            gy = scale * gp
+            e_gy = FIN * np.abs(gy)
+        else:
+            gy = scale * (gp - db / n - yhat * dg / n)
+            mag = np.abs(scale) * (np.abs(gp) + np.abs(db) / n + np.abs(yhat * dg) / n)
+            e_gy = np.abs(scale) * (e_db / n + np.abs(yhat) * e_dg / n) + FIN * mag
         out = dict(gy=(gy, u * np.abs(gy) + (1 + u) * e_gy + B.ETA[fmt]), dbeta=(db, e_db), dgamma=(dg, e_dg))
     if base is not None:
         g0, b0 = base

@@ -254,11 +254,19 @@ def _pc(t, dtype, dev):
 
 
 def _bn_case(dev, rec, shifted):
+    """One BatchNorm record.  What a record can ask for beyond the window's launches (tests/test_edge_bn_gpu.py): the
+    plain ir2rgb_bn_finalize entry; no conv_bias; evaluation mode (the frozen argument of ir2rgb_bn_finalize_ex, act | 16
+    of ir2rgb_bn_bwd, also with act | 32); and, with the key "two_launch", the bit-identity of ir2rgb_bn_finalize_apply
+    with ir2rgb_bn_finalize_ex + ir2rgb_bn_apply as a second assertion."""
     from ir2rgb_amd import _lib
     from oracle import bn_ref as BR
     a = rec["args"]
     g = _gen(rec) if not shifted else torch.Generator().manual_seed(20)
     entry = rec["entry"]
+    plain = entry == "ir2rgb_bn_finalize"
+    if plain:           # the same arguments without conv_bias and frozen
+        a = a[:6] + [False] + a[6:] + [0]
+        entry = "ir2rgb_bn_finalize_ex"
     if entry == "ir2rgb_bn_bwd":
         P, C, act = a[10], a[11], a[12]
     elif entry == "ir2rgb_bn_apply":
@@ -274,7 +282,10 @@ def _bn_case(dev, rec, shifted):
             ref, bnd = rb
             got = got.double().cpu().numpy().reshape(ref.shape)
             assert np.isfinite(got).all(), f"{fmt} {name}: non-finite"
-            r = (np.abs(got - ref) / bnd).max()
+            err = np.abs(got - ref)
+            # (a sum whose every term is zero -- one pixel, a channel the activation switches off -- has the bound 0 and
+            # must be exact: 0 / 0 is then a pass, anything else over a zero bound is not)
+            r = np.divide(err, bnd, out=np.where(err > 0, np.inf, 0.0), where=bnd > 0).max()
             worst[fmt] = max(worst.get(fmt, 0.0), float(r))
             assert r <= 1.0, f"{fmt} {name}: worst err/bound {r:.3g}"
         f32 = dict(device=dev, dtype=torch.float32)
@@ -286,13 +297,25 @@ def _bn_case(dev, rec, shifted):
             gamma, beta, cb = _vec(C, g, 0.5, 1.5), _vec(C, g), _vec(C, g) * 0.2
             rm, rv = _vec(C, g), _vec(C, g, 0.5, 2.0)
             mom, eps, upd = a[9], a[10], a[15]
-            ref = BR.finalize(rows.double().numpy(), float(P), gamma.double().numpy(), beta.double().numpy(),
-                              cb.double().numpy(), rm.double().numpy(), rv.double().numpy(), mom, eps, upd)
+            frozen = entry == "ir2rgb_bn_finalize_ex" and a[16]
+            cb0 = cb.double().numpy() if a[6] else np.zeros(C)
+            if frozen:
+                ref = BR.finalize_frozen(gamma.double().numpy(), beta.double().numpy(), cb0, rm.double().numpy(),
+                                         rv.double().numpy(), eps)
+            else:
+                ref = BR.finalize(rows.double().numpy(), float(P), gamma.double().numpy(), beta.double().numpy(),
+                                  cb0, rm.double().numpy(), rv.double().numpy(), mom, eps, upd)
             dv = [t.to(dev) for t in (rows, gamma, beta, cb, rm, rv)]
+            if not a[6]:
+                dv[3] = None
             outs = [torch.empty(C, **f32) for _ in range(4)]
-            if entry == "ir2rgb_bn_finalize_ex":
+            if plain:
+                rc = lib.ir2rgb_bn_finalize(dv[0], R_, C, P, dv[1], dv[2], dv[4], dv[5], mom, eps, *outs, upd, stream)
+                _lib.check(rc, "bn_finalize")
+                z = None
+            elif entry == "ir2rgb_bn_finalize_ex":
                 rc = lib.ir2rgb_bn_finalize_ex(dv[0], R_, C, P, dv[1], dv[2], dv[3], dv[4], dv[5], mom, eps,
-                                               *outs, upd, 0, stream)
+                                               *outs, upd, int(a[16]), stream)
                 _lib.check(rc, "bn_finalize_ex")
                 z = None
             else:
@@ -306,8 +329,24 @@ def _bn_case(dev, rec, shifted):
             torch.cuda.synchronize()
             for name, t in zip(("scale", "shift", "mean", "invstd"), outs):
                 check(name, t, ref[name] if name != "mean" else (ref["mean"][0], ref["mean"][1] + B.ETA["f32"]))
-            check("running_mean", dv[4], ref["running_mean"])
-            check("running_var", dv[5], ref["running_var"])
+            if frozen:          # nothing is updated in evaluation mode
+                assert torch.equal(dv[4].cpu(), rm) and torch.equal(dv[5].cpu(), rv), f"{fmt}: frozen finalize wrote the running statistics"
+            else:
+                check("running_mean", dv[4], ref["running_mean"])
+                check("running_var", dv[5], ref["running_var"])
+            if rec.get("two_launch"):       # the same through ir2rgb_bn_finalize_ex + ir2rgb_bn_apply, bit for bit
+                dv2 = [t.to(dev) for t in (rows, gamma, beta, cb, rm, rv)]
+                if not a[6]:
+                    dv2[3] = None
+                outs2 = [torch.empty(C, **f32) for _ in range(4)]
+                z2 = torch.empty_like(z)
+                _lib.check(lib.ir2rgb_bn_finalize_ex(dv2[0], R_, C, P, dv2[1], dv2[2], dv2[3], dv2[4], dv2[5], mom, eps,
+                                                     *outs2, upd, 0, stream), "bn_finalize_ex")
+                _lib.check(lib.ir2rgb_bn_apply(x, outs2[0], outs2[1], rdev[0], rdev[1], z2, P, C, act, dt, stream), "bn_apply")
+                torch.cuda.synchronize()
+                same = [torch.equal(p.view(torch.int32), q.view(torch.int32)) for p, q in zip(outs + dv[4:], outs2 + dv2[4:])]
+                assert all(same) and torch.equal(z.view(torch.int16), z2.view(torch.int16)), \
+                    f"{fmt}: fused finalize + apply differs from the two launches ({same})"
             if z is not None:
                 rr = [r.double().numpy() if r is not None else None for r in res]
                 check("z", z, BR.apply(yd, ref["scale"][0], ref["shift"][0], act, rr[0], rr[1], fmt,
@@ -337,15 +376,18 @@ def _bn_case(dev, rec, shifted):
             invstd = (1.0 / (y.double().var(0, unbiased=False) + 1e-5).sqrt()).float()
             mean = mean.float()
             gamma, beta = _vec(C, g, 0.5, 1.5), _vec(C, g)
+            if act & 16:        # evaluation mode: the running statistics, not the batch's
+                mean = (mean + _vec(C, g) * 0.25).to(torch.bfloat16).float()
+                invstd = (1.0 / (_vec(C, g, 0.5, 2.0) + 1e-5).sqrt()).float()
             scale = (gamma * invstd) if has_scale else None
             shift = (beta - mean * scale) if has_scale else None
             _bn_bwd_check(dev, fmt, dtype, y, g, None if scale is None else scale.double().numpy(),
                           None if shift is None else shift.double().numpy(), mean.double().numpy(),
-                          invstd.double().numpy(), act & 15, bool(act & 32), check)
+                          invstd.double().numpy(), act & 15, bool(act & 32), check, frozen=bool(act & 16))
     return worst
 
 
-def _bn_bwd_check(dev, fmt, dtype, y, g, scale, shift, mean, invstd, act, acc, check):
+def _bn_bwd_check(dev, fmt, dtype, y, g, scale, shift, mean, invstd, act, acc, check, frozen=False):
     from ir2rgb_amd import autograd as AG
     from oracle import bn_ref as BR
     P, C = y.shape
@@ -354,12 +396,12 @@ def _bn_bwd_check(dev, fmt, dtype, y, g, scale, shift, mean, invstd, act, acc, c
     gz[torch.from_numpy(~BR.sign_safe(yd, scale, shift))] = 0
     base = (torch.randn(C, generator=g), torch.randn(C, generator=g)) if acc else None
     ref = BR.bwd(gz.double().numpy(), yd, scale, shift, mean, invstd, act, fmt,
-                 None if base is None else (base[0].double().numpy(), base[1].double().numpy()))
+                 None if base is None else (base[0].double().numpy(), base[1].double().numpy()), frozen=frozen)
     t = (lambda v: torch.from_numpy(np.asarray(v, dtype=np.float32)).to(dev) if v is not None else None)
     params = (base[0].to(dev), base[1].to(dev)) if acc else None
     norm = scale is not None
     gy, dgamma, dbeta = AG.bn_bwd(_pc(gz, dtype, dev), _pc(y, dtype, dev), t(scale), t(shift), t(mean) if norm else None,
-                                  t(invstd) if norm else None, act, params=params)
+                                  t(invstd) if norm else None, act | (16 if frozen else 0), params=params)
     torch.cuda.synchronize()
     check("gy", gy.permute(0, 2, 3, 1), ref["gy"])
     check("dbeta", dbeta, ref["dbeta"])
