@@ -439,6 +439,29 @@ int ir2rgb_frame_push_u8(const void *frame, float *hist0, float *hist1, int T, i
  * (util.tensor2im, util/util.py:45-67). */
 int ir2rgb_frame_finish_u8(const float *x, float *hist, uint8_t *img_u8, int T, int H, int W, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Video scores (video_metrics.hip): the reference's scripts/ssim_metric.py per frame, in fp64 on the device.
+ * orig, pred: uint8 [N][H][W][3], N in [1, 65535], H, W >= 7, 3*H*W < 2^31.  For every frame n
+ *   gray  = (r/255)*0.2125 + (g/255)*0.7154 + (b/255)*0.0721              skimage.color.rgb2gray
+ *   R     = max(gray(orig)) - min(gray(pred))                              the script's dynamic_range, or
+ *           range[n] when `range` (device, N doubles) is not NULL
+ *   l2    = sqrt(sum (gray(orig) - gray(pred))^2)                          np.linalg.norm in mse_single_frame
+ *   ssim  = mean over the (H-6)*(W-6) windows inside the image of
+ *           ((2 ux uy + C1)(2 vxy + C2)) / ((ux^2 + uy^2 + C1)(vx + vy + C2)),  C1 = (0.01 R)^2, C2 = (0.03 R)^2,
+ *           window 7x7, uniform weights, sample covariance (49/48): skimage's compare_ssim defaults
+ * and out[n] = {ssim, l2, R}.  No special cases (an all-black pair gives NaN, as in NumPy).  R never passes
+ * through the host.  All sums have a fixed order: results are bit-reproducible.
+ * The workspace is the caller's: ir2rgb_video_metrics_workspace_bytes(N, H, W) bytes (negative for invalid
+ * sizes), fully written before it is read, so it needs no zeroing and carries nothing between calls.
+ * ir2rgb_video_metrics_tile(0 / 1) -> rows / columns of windows one workgroup evaluates (host only).
+ * IR2RGB_EINVAL: NULL orig / pred / out / workspace, sizes out of range, workspace too small;
+ * IR2RGB_EALIGN: out, range or workspace not on an 8-byte boundary.  Both before any launch.
+ * ------------------------------------------------------------------------------------------ */
+long ir2rgb_video_metrics_workspace_bytes(int N, int H, int W);
+int ir2rgb_video_metrics_tile(int which);
+int ir2rgb_video_metrics_u8(const uint8_t *orig, const uint8_t *pred, const double *range, double *out, void *workspace,
+                            long workspace_bytes, int N, int H, int W, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,7 +6,7 @@ first use and its absence is an error (there is no CPU fallback).
 """
 __version__ = "0.1.0"
 
-__all__ = ["VideoTranslator"]
+__all__ = ["VideoTranslator", "VideoScore", "video_metrics", "ssim_reference"]
 
 
 def __getattr__(name):
@@ -14,4 +14,7 @@ def __getattr__(name):
     if name == "VideoTranslator":
         from .inference import VideoTranslator
         return VideoTranslator
+    if name in ("VideoScore", "video_metrics", "ssim_reference"):
+        from . import metrics
+        return getattr(metrics, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -100,6 +100,9 @@ PROTOTYPES = {
     "ir2rgb_adam_step": (c_int, [P, P, c_int, c_float, c_float, c_float, c_float, c_int, P]),
     "ir2rgb_frame_push_u8": (c_int, [P, P, P] + [c_int] * 5 + [P]),
     "ir2rgb_frame_finish_u8": (c_int, [P, P, P] + [c_int] * 3 + [P]),
+    "ir2rgb_video_metrics_workspace_bytes": (c_long, [c_int] * 3),
+    "ir2rgb_video_metrics_tile": (c_int, [c_int]),
+    "ir2rgb_video_metrics_u8": (c_int, [P] * 5 + [c_long] + [c_int] * 3 + [P]),
 }
 
 _lib = None

@@ -98,6 +98,11 @@ class SequenceState:
         self.n_pushed += 1
         return self.n_pushed >= self.tG
 
+    def output_frame(self, k):
+        """Index of the input frame whose translation is output ``k`` of the sequence: the first tG-1 frames produce
+        none, so a ground-truth track is read at ``output_frame(k)``."""
+        return self.tG - 1 + int(k)
+
     def begin_step(self):
         """-> is_first_frame of the step that starts now (generator.py:187)."""
         first, self.started = not self.started, True
@@ -287,6 +292,23 @@ class VideoTranslator:
             out = self.push(f, real_rgb[i] if i < len(real_rgb) else None)
             if out is not None:
                 yield out
+
+    def evaluate(self, frames, targets, real_rgb=None, data_range="reference"):
+        """``translate(frames, real_rgb)`` scored against a ground-truth RGB track (reference scripts/ssim_metric.py):
+        output ``k`` is compared with ``targets[tG-1+k]`` -- ``targets`` is indexed like ``frames``, uint8 [H,W,3] each,
+        moved to the device if needed.  -> ``ir2rgb_amd.metrics.VideoScore``; its ``result()`` is the only host
+        synchronisation.  The scores are enqueued on the current stream after each step; the captured graph is the one
+        ``translate`` replays.  ``data_range``: see ``ir2rgb_amd.metrics.video_metrics``."""
+        from .metrics import VideoScore
+        if not hasattr(targets, "__getitem__"):
+            targets = list(targets)
+        score = VideoScore(data_range)
+        for k, out in enumerate(self.translate(frames, real_rgb)):
+            i = self.seq.output_frame(k)
+            if i >= len(targets):
+                raise ValueError(f"evaluate: output {k} is scored against targets[{i}], {len(targets)} targets given")
+            score.add(self._as_frame(targets[i], 3, "evaluate(targets)"), out)
+        return score
 
     def inference(self, input_A, input_B=None):
         """The reference-shaped call (generator.py:184-195): ``input_A`` fp32 [1,tG,C,H,W] normalised, ``input_B`` fp32

@@ -7,8 +7,9 @@ bench.py configuration), 50 frames after warm-up, three ways on the same weights
   (c) graph     VideoTranslator(use_graph=True): one HIP-graph replay per frame
 
 Each figure: device events around the 50 frames and one synchronise; the three ways alternate over ``--rounds`` rounds and
-the median round is reported (frames/s, ms/frame).  The two frame-I/O kernels are timed alone beside the bytes they move
-(computed from the shapes).  Needs the GPU; prints one JSON document and writes it to ``--out``.
+the median round is reported (frames/s, ms/frame).  The two frame-I/O kernels and the score of one frame
+(ir2rgb_amd.metrics.video_metrics) are timed alone beside the bytes they move (computed from the shapes).  Needs the GPU;
+prints one JSON document and writes it to ``--out``.
 
     python tools/bench_infer.py --out profiles/inference_512x1024.json
 """
@@ -77,10 +78,11 @@ def timed(fn):
 
 
 def kernel_times(dev, H, W, reps=200):
-    from ir2rgb_amd import inference as I
+    from ir2rgb_amd import inference as I, metrics as M
     frame = torch.randint(0, 256, (H, W, 3), dtype=torch.uint8, device=dev)
     Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
     h0, h1 = torch.zeros(TG, 3, H, W, device=dev), torch.zeros(TG, 3, Ho, Wo, device=dev)
+    truth = torch.randint(0, 256, (H, W, 3), dtype=torch.uint8, device=dev)
     x, hb, img = torch.rand(3, H, W, device=dev) * 2 - 1, torch.zeros(TG - 1, 3, H, W, device=dev), torch.zeros(H, W, 3, dtype=torch.uint8, device=dev)
 
     def many(f):
@@ -96,7 +98,9 @@ def kernel_times(dev, H, W, reps=200):
     for name, f, byts in (
             ("frame_push_u8 (T=3, two levels)", lambda: I.frame_push(frame, h0, h1), px + (2 * TG - 1) * 4 * (px + pp)),
             ("frame_push_u8 (T=3, one level)", lambda: I.frame_push(frame, h0), px + (2 * TG - 1) * 4 * px),
-            ("frame_finish_u8 (T=2, uint8 image)", lambda: I.frame_finish(x, hb, img), 4 * px + (2 * (TG - 1) - 1) * 4 * px + px)):
+            ("frame_finish_u8 (T=2, uint8 image)", lambda: I.frame_finish(x, hb, img), 4 * px + (2 * (TG - 1) - 1) * 4 * px + px),
+            # both uint8 frames are read by the reduce pass and again (from L2 / Infinity Cache) by the window pass
+            ("video_metrics_u8 (one frame, three launches)", lambda: M.video_metrics(truth, frame), 2 * 2 * px)):
         us = many(f)
         res[name] = {"us_per_launch": round(us, 2), "bytes_moved": int(byts), "GB_per_s": round(byts / us / 1e3, 1)}
     res["note"] = ("bytes_moved counts the in-place history shift (slots read and written) beside the frame itself: "
