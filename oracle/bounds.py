@@ -98,7 +98,7 @@ def check_stats(got, acc):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# Non-convolution entry points of the window (tests/test_window_ops_gpu.py, oracle/window_ops_ref.py).  Constants fixed
+# Non-convolution entry points of the window (oracle/replay_ops.py, oracle/window_ops_ref.py).  Constants fixed
 # before any comparison:
 #
 # * short fp32 sums of L terms (reflect folds, the xexpand adjoint, 3x3 pooling, the 8-MAC flow up-sampler, the KH + 1

@@ -18,6 +18,7 @@ launches (``conv2d_pack_*``) are left unrecorded: test_losses_gpu.py's batched-r
 ``entry_class`` sorts every entry of ``_lib.PROTOTYPES`` into conv, bn, pack, query or op.
 
 ``tests/window_geometries.json`` is the committed result; ``python -m oracle.window --write`` regenerates it on a GPU.
+Its records are replayed against fp64 by oracle/replay_kernels.py (conv, bn) and oracle/replay_ops.py (op).
 """
 import contextlib
 import json

@@ -1,4 +1,4 @@
-"""The fp64 references of the edge records (tests/test_edge_ops_gpu.py, tests/test_edge_bn_gpu.py) checked without a GPU.
+"""The fp64 references of the edge records (oracle/edge_records.py) checked without a GPU.
 
 oracle/window_ops_ref.py and oracle/bn_ref.py had only been exercised at the window's large shapes; at H <= 2 * pad,
 one-pixel planes or N > 1 they could themselves be wrong.  At every edge record each reference is compared with an
@@ -10,9 +10,6 @@ faults of tests/test_window_ops_bounds_cpu.py are shown to be rejected by the bo
 bound that is tight at 512 x 1024 can be vacuous at 4 x 5); and every replayed entry and every BatchNorm entry point
 must have an edge record.
 """
-import importlib.util
-import os
-
 import numpy as np
 import pytest
 import torch
@@ -20,34 +17,25 @@ import torch.nn.functional as F
 
 from oracle import bn_ref as BR
 from oracle import bounds as B
+from oracle import conv_ref as R
+from oracle import edge_records as E
+from oracle import replay_kernels as K
+from oracle import replay_ops as G
 from oracle import window as WG
 from oracle import window_ops_ref as O
+from oracle.replay import gen, ids, passes, rnd
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 RTOL = 1e-12
-
-
-def _load(name):
-    spec = importlib.util.spec_from_file_location("_refs_" + name, os.path.join(HERE, name + ".py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-E = _load("test_edge_ops_gpu")
-EB = _load("test_edge_bn_gpu")
-G = E.G
-K = EB.K
 
 
 def _recs(*entries):
     recs = [r for r in E.EDGE if r["entry"] in entries]
-    return pytest.mark.parametrize("rec", recs, ids=G._ids(recs))
+    return pytest.mark.parametrize("rec", recs, ids=ids(recs))
 
 
 def _bn_recs(*entries):
-    recs = [r for r in EB.EDGE_BN if r["entry"] in entries]
-    return pytest.mark.parametrize("rec", recs, ids=K._ids(recs))
+    recs = [r for r in E.EDGE_BN if r["entry"] in entries]
+    return pytest.mark.parametrize("rec", recs, ids=ids(recs))
 
 
 def _close(got, want, what=""):
@@ -64,15 +52,6 @@ def _rand(g, *shape, scale=1.0):
     return torch.randn(*shape, generator=g, dtype=torch.float64) * scale
 
 
-def _rnd(x, fmt):
-    dt = {"bf16": torch.bfloat16, "f16": torch.float16, "f32": torch.float32}[fmt]
-    return torch.from_numpy(np.ascontiguousarray(x)).to(dt).double().numpy()
-
-
-def _passes(got, ref, bnd):
-    return B.check_bound(got, ref, bnd)[0]
-
-
 def _act(pre, nb, mul):
     return torch.tanh(pre) if nb == 1 else (torch.sigmoid(pre) if nb == 2 else pre * mul)
 
@@ -87,21 +66,21 @@ def test_every_replayed_entry_has_an_edge_record():
 
 
 def test_every_batchnorm_entry_point_has_an_edge_record():
-    have = {r["entry"] for r in EB.EDGE_BN}
+    have = {r["entry"] for r in E.EDGE_BN}
     assert have == set(WG.BN_ENTRIES), sorted(have ^ set(WG.BN_ENTRIES))
-    assert len({WG.canon(r) for r in EB.EDGE_BN}) == len(EB.EDGE_BN), "a duplicate edge record"
-    bwd = [r["args"] for r in EB.EDGE_BN if r["entry"] == "ir2rgb_bn_bwd"]
+    assert len({WG.canon(r) for r in E.EDGE_BN}) == len(E.EDGE_BN), "a duplicate edge record"
+    bwd = [r["args"] for r in E.EDGE_BN if r["entry"] == "ir2rgb_bn_bwd"]
     for form in (0, 16, 32, 48):
         assert {a[12] & 15 for a in bwd if a[2] and a[12] & 48 == form} == {0, 1, 2}, form
     assert any(not a[2] for a in bwd)
-    assert any(r["args"][16] for r in EB.EDGE_BN if r["entry"] == "ir2rgb_bn_finalize_ex")
-    assert {r["args"][15] for r in EB.EDGE_BN if r["entry"] == "ir2rgb_bn_finalize_ex"} == {1, 2, 3}
+    assert any(r["args"][16] for r in E.EDGE_BN if r["entry"] == "ir2rgb_bn_finalize_ex")
+    assert {r["args"][15] for r in E.EDGE_BN if r["entry"] == "ir2rgb_bn_finalize_ex"} == {1, 2, 3}
 
 
 def test_edge_records_are_not_window_records():
     """The edge tables add geometries; a record that repeats a manifest entry would add nothing."""
     man = {WG.canon(r) for r in WG.load()["launches"]}
-    assert not [r for r in E.EDGE + EB.EDGE_BN if WG.canon(r) in man]
+    assert not [r for r in E.EDGE + E.EDGE_BN if WG.canon(r) in man]
 
 
 def test_loss_records_are_what_the_kernel_accepts():
@@ -144,9 +123,9 @@ def _head_torch(T, bias, Cout, KH, pad, acts, mul):
 
 @_recs("ir2rgb_head_finish", "ir2rgb_head_finish_bwd")
 def test_head_reference_matches_reflect_pad_and_autograd(rec):
-    a = G._args(rec)
+    a = G.named_args(rec)
     N, H, W, Cout, KH, CT, pad, acts, mul = (a[k] for k in "N H W Cout KH CT pad_h acts mul".split())
-    g = E.gen(rec)
+    g = gen(rec)
     T = _rand(g, N, H, W, CT, scale=0.5).requires_grad_(True)
     bias = _rand(g, Cout, scale=0.5).requires_grad_(True)
     use_bias = a.get("bias", True)
@@ -165,9 +144,9 @@ def test_head_reference_matches_reflect_pad_and_autograd(rec):
 # ---------------------------------------------------------------------------------------------------------------------
 # warp_blend
 def _warp_rec_inputs(rec):
-    a = G._args(rec)
+    a = G.named_args(rec)
     N, Cp, H, W = a["N"], a["Cp"], a["H"], a["W"]
-    g = E.gen(rec)
+    g = gen(rec)
     raw, prev, flow, w = G._warp_inputs(N, Cp, H, W, g)
     return a, g, [t.double() for t in (raw, prev, flow, w)]
 
@@ -210,9 +189,9 @@ def test_warp_reference_matches_grid_sample(rec):
 def test_resample_reference_matches_grid_sample(rec):
     """resample2d (corners clamped, weights from the unclamped fraction) equals grid_sample(align_corners=True, border):
     beyond the border both corners clamp onto the edge pixel, whatever the weights."""
-    a = G._args(rec)
+    a = G.named_args(rec)
     N, C, H, W = a["N"], a["C"], a["H"], a["W"]
-    g = E.gen(rec)
+    g = gen(rec)
     img1, img2 = _rand(g, N, C, H, W), _rand(g, N, C, H, W)
     flow = G._pixel_flow(N, H, W, g).double()
     v, _, _, _ = O.resample2d(img2.numpy(), flow.numpy())
@@ -233,9 +212,9 @@ def test_resample_reference_matches_grid_sample(rec):
 # pooling, up-sampler, xexpand, fold
 @_recs("ir2rgb_avgpool3s2")
 def test_avgpool_reference_matches_torch(rec):
-    a = G._args(rec)
+    a = G.named_args(rec)
     P, H, W = a["planes"], a["H"], a["W"]
-    g = E.gen(rec)
+    g = gen(rec)
     x = _rand(g, P, H, W).requires_grad_(True)
     y = F.avg_pool2d(x[:, None], 3, 2, 1, count_include_pad=False)[:, 0]
     _close(O.avgpool3s2(x.detach().numpy())[0], y, "avgpool")
@@ -246,8 +225,8 @@ def test_avgpool_reference_matches_torch(rec):
 
 @_recs("ir2rgb_flow_upsample_slice")
 def test_flow_upsample_reference_matches_conv_transpose(rec):
-    a = G._args(rec)
-    g = E.gen(rec)
+    a = G.named_args(rec)
+    g = gen(rec)
     x, w, b = _rand(g, a["N"], 2, a["h"], a["w"], scale=4), _rand(g, 2, 2, 4, 4, scale=0.5), _rand(g, 2)
     bias = b if a["bias"] else None
     want = F.conv_transpose2d(x, w, bias, stride=2, padding=1)
@@ -265,11 +244,11 @@ def _xexpand_torch(x, Wout, KW, s, p, pm, Cx):
 
 @_recs("ir2rgb_xexpand", "ir2rgb_xexpand_cx", "ir2rgb_xexpand_bwd")
 def test_xexpand_reference_matches_unfold_and_autograd(rec):
-    a = G._args(rec)
+    a = G.named_args(rec)
     N, Cin, H, W, Wout, KW, s, p, pm = (a[k] for k in "N Cin H W Wout KW stride_w pad_w pad_mode".split())
     Cx = a.get("Cx", 64)
     assert Wout == (W + 2 * p - KW) // s + 1 and Cin * KW <= Cx and (not pm or p < W)
-    g = E.gen(rec)
+    g = gen(rec)
     x = _rand(g, N, Cin, H, W).requires_grad_(True)
     want = _xexpand_torch(x, Wout, KW, s, p, pm, Cx)
     _close(O.xexpand(x.detach().numpy(), Wout, KW, s, p, pm, Cx), want, "xexpand")
@@ -280,9 +259,9 @@ def test_xexpand_reference_matches_unfold_and_autograd(rec):
 
 @_recs("ir2rgb_fold_reflect")
 def test_fold_reference_is_the_adjoint_of_reflection_pad(rec):
-    a = G._args(rec)
+    a = G.named_args(rec)
     N, H, W, C, ph, pw = (a[k] for k in "N H W C pad_h pad_w".split())
-    g = E.gen(rec)
+    g = gen(rec)
     x = _rand(g, N, C, H, W).requires_grad_(True)
     xp = F.pad(x, (pw, pw, ph, ph), mode="reflect")
     dxpad = _rand(g, N, C, H + 2 * ph, W + 2 * pw)
@@ -296,7 +275,7 @@ def test_fold_reference_is_the_adjoint_of_reflection_pad(rec):
 # losses and Adam
 @_recs("ir2rgb_loss_multi_fwd", "ir2rgb_loss_multi_bwd")
 def test_loss_reference_matches_torch(rec):
-    g = E.gen(rec)
+    g = gen(rec)
     for it in rec["items"]:
         n = it["n"]
         a = _rand(g, n).requires_grad_(True)
@@ -322,7 +301,7 @@ def test_loss_reference_matches_torch(rec):
 @pytest.mark.parametrize("step", [1, 14])
 def test_adam_reference_matches_torch_optim(step):
     rec = E.ADAM
-    g = E.gen(rec)
+    g = gen(rec)
     b1, b2 = float(np.float32(rec["beta1"])), float(np.float32(rec["beta2"]))
     for n in sorted({n for n, _, _ in rec["tensors"]}):
         p, gr = _rand(g, n, scale=0.05), _rand(g, n, scale=0.01)
@@ -347,7 +326,7 @@ def _bn_act(z, act):
 
 
 def _bn_inputs(rec, P, C):
-    g = K._gen(rec)
+    g = gen(rec)
     y = K._bn_data(P, C, g).double()
     vec = [K._vec(C, g, 0.5, 1.5).double(), K._vec(C, g).double(), (K._vec(C, g) * 0.2).double(), K._vec(C, g).double(),
            K._vec(C, g, 0.5, 2.0).double()]
@@ -465,7 +444,7 @@ def test_bn_bwd_reference_matches_autograd(rec):
 # the planted faults of test_window_ops_bounds_cpu.py at an edge record of each family
 def _edge(entry, **want):
     for r in E.EDGE:
-        if r["entry"] == entry and all(G._args(r)[k] == v for k, v in want.items()):
+        if r["entry"] == entry and all(G.named_args(r)[k] == v for k, v in want.items()):
             return r
     raise LookupError((entry, want))
 
@@ -476,15 +455,15 @@ def _edge(entry, **want):
 def test_head_finish_bwd_missing_mirror_rejected_at_edge_record(fmt, H, edge):
     """pad < H <= 2 * pad: the mirror of one border lands next to the other one.  One mirror contribution dropped."""
     rec = _edge("ir2rgb_head_finish_bwd", H=H, W=5)
-    a = G._args(rec)
-    g = E.gen(rec)
+    a = G.named_args(rec)
+    g = gen(rec)
     shape = (a["N"], a["Cout"], H, a["W"])
     pre = _rand(g, *shape, scale=2)
-    out = _rnd(torch.stack([_act(pre[:, co], O.nibble(a["acts"], co), a["mul"]) for co in range(a["Cout"])], 1).numpy(), "f32")
-    gout = _rnd(_rand(g, *shape).numpy(), "f32")
+    out = rnd(torch.stack([_act(pre[:, co], O.nibble(a["acts"], co), a["mul"]) for co in range(a["Cout"])], 1).numpy(), "f32")
+    gout = rnd(_rand(g, *shape).numpy(), "f32")
     dT, _, S, _ = O.head_finish_bwd(gout, out, a["Cout"], a["KH"], a["CT"], a["pad_h"], a["acts"], a["mul"])
     bnd = B.bound_rw(dT, S, fmt, 3, 6)
-    assert _passes(_rnd(dT, fmt), dT, bnd)
+    assert passes(rnd(dT, fmt), dT, bnd)
     y = 0 if edge == "top" else H - 1
     ky = 0 if edge == "top" else a["KH"] - 1
     dst = int(O.refl(np.array([y + ky - a["pad_h"]]), H)[0])
@@ -493,20 +472,20 @@ def test_head_finish_bwd_missing_mirror_rejected_at_edge_record(fmt, H, edge):
     o, gg = out[:, 0, y], gout[:, 0, y]
     bad = dT.copy()
     bad[:, dst, :, ky] -= gg * (1 - o * o) if nb == 1 else (gg * o * (1 - o) if nb == 2 else gg * a["mul"])
-    assert not _passes(_rnd(bad, fmt), dT, bnd)
+    assert not passes(rnd(bad, fmt), dT, bnd)
 
 
 @pytest.mark.parametrize("H", [4, 9])
 def test_head_finish_dropped_mirror_rejected_at_edge_record(H):
     """The forward with the bottom mirror replaced by an edge repeat (clamp instead of reflect)."""
     rec = _edge("ir2rgb_head_finish", H=H, W=5)
-    a = G._args(rec)
-    g = E.gen(rec)
+    a = G.named_args(rec)
+    g = gen(rec)
     T = _rand(g, a["N"], H, a["W"], a["CT"], scale=0.5).numpy()
     bias = _rand(g, a["Cout"], scale=0.5).numpy()
     out, pre, S = O.head_finish(T, bias, a["Cout"], a["KH"], a["pad_h"], a["acts"], a["mul"])
     bnd = B.bound_act(out, O.act_slope(out, a["acts"], a["mul"], a["Cout"]), S, a["KH"] + 1)
-    assert _passes(_rnd(out, "f32"), out, bnd)
+    assert passes(rnd(out, "f32"), out, bnd)
     Tc = np.concatenate([T, np.repeat(T[:, -1:], a["pad_h"], 1)], 1)       # rows beyond H - 1 repeat the last row
     pre_bad = pre.copy()
     for co in range(a["Cout"]):
@@ -515,7 +494,7 @@ def test_head_finish_dropped_mirror_rejected_at_edge_record(H):
             if t > H - 1:
                 pre_bad[:, co, H - 1] += Tc[:, t, :, co * a["KH"] + ky] - T[:, O.refl(np.array([t]), H)[0], :, co * a["KH"] + ky]
     bad = np.stack([_act(torch.from_numpy(pre_bad[:, co]), O.nibble(a["acts"], co), a["mul"]).numpy() for co in range(a["Cout"])], 1)
-    assert not _passes(_rnd(bad, "f32"), out, bnd)
+    assert not passes(rnd(bad, "f32"), out, bnd)
 
 
 @pytest.mark.parametrize("backward", [0, 1])
@@ -523,17 +502,17 @@ def test_head_finish_dropped_mirror_rejected_at_edge_record(H):
 def test_avgpool_count_include_pad_rejected_at_edge_record(backward, shape):
     rec = _edge("ir2rgb_avgpool3s2", planes=shape[0], H=shape[1], W=shape[2], backward=backward)
     P, H, W = shape
-    g = E.gen(rec)
+    g = gen(rec)
     if not backward:
-        x = _rnd(_rand(g, P, H, W).numpy(), "f32")
+        x = rnd(_rand(g, P, H, W).numpy(), "f32")
         (ref, S), (bad, _) = O.avgpool3s2(x), O.avgpool3s2(x, count_include_pad=True)
         bnd = B.bound_sum(ref, S, "f32", 10)
     else:
-        gy = _rnd(_rand(g, P, (H - 1) // 2 + 1, (W - 1) // 2 + 1).numpy(), "f32")
+        gy = rnd(_rand(g, P, (H - 1) // 2 + 1, (W - 1) // 2 + 1).numpy(), "f32")
         (ref, S), (bad, _) = O.avgpool3s2_bwd(gy, H, W), O.avgpool3s2_bwd(gy, H, W, count_include_pad=True)
         bnd = B.bound_sum(ref, S, "f32", 8)
-    assert _passes(_rnd(ref, "f32"), ref, bnd)
-    assert not _passes(_rnd(bad, "f32"), ref, bnd)
+    assert passes(rnd(ref, "f32"), ref, bnd)
+    assert not passes(rnd(bad, "f32"), ref, bnd)
 
 
 @pytest.mark.parametrize("step", [1, 14])
@@ -541,37 +520,37 @@ def test_avgpool_count_include_pad_rejected_at_edge_record(backward, shape):
 def test_adam_tail_not_updated_rejected_at_edge_record(step, n):
     rec = E.ADAM
     assert n % 4 and [n, True, 1] in rec["tensors"] and [n, False, 1] in rec["tensors"]
-    g = E.gen(rec)
-    p = _rnd(_rand(g, n, scale=0.05).numpy(), "f32")
-    gr = _rnd(_rand(g, n, scale=0.01).numpy(), "f32")
-    m = np.zeros(n) if step == 1 else _rnd(_rand(g, n, scale=0.01).numpy(), "f32")
-    v = np.zeros(n) if step == 1 else _rnd((torch.rand(n, generator=g, dtype=torch.float64) * 1e-4).numpy(), "f32")
+    g = gen(rec)
+    p = rnd(_rand(g, n, scale=0.05).numpy(), "f32")
+    gr = rnd(_rand(g, n, scale=0.01).numpy(), "f32")
+    m = np.zeros(n) if step == 1 else rnd(_rand(g, n, scale=0.01).numpy(), "f32")
+    v = np.zeros(n) if step == 1 else rnd((torch.rand(n, generator=g, dtype=torch.float64) * 1e-4).numpy(), "f32")
     b1, b2 = float(np.float32(rec["beta1"])), float(np.float32(rec["beta2"]))
     p1, m1, v1, upd, Sm, ss, den = O.adam(p, gr, m, v, rec["lr"], b1, b2, rec["eps"], step)
     bm = 4 * B.U32 * Sm + B.ETA["f32"]
     bp = B.U32 * np.abs(p1) + 16 * B.U32 * upd + ss * bm / den + B.ETA["f32"]
-    assert _passes(_rnd(p1, "f32"), p1, bp)
+    assert passes(rnd(p1, "f32"), p1, bp)
     bad = p1.copy()
     bad[n - n % 4:] = p[n - n % 4:]
-    assert not _passes(_rnd(bad, "f32"), p1, bp)
+    assert not passes(rnd(bad, "f32"), p1, bp)
     bad_m = m1.copy()
     bad_m[n - n % 4:] = m[n - n % 4:]
-    assert not _passes(_rnd(bad_m, "f32"), m1, bm)
+    assert not passes(rnd(bad_m, "f32"), m1, bm)
 
 
 @pytest.mark.parametrize("fmt", ["bf16", "f16"])
 def test_bn_bwd_frozen_as_training_rejected_at_edge_record(fmt):
     """Evaluation mode answered with the training-mode gradient (the mean / variance terms left in), at 2 and 513 pixels."""
-    for rec in [r for r in EB.EDGE_BN if r["entry"] == "ir2rgb_bn_bwd" and r["args"][12] & 16 and r["args"][10] in (2, 513)]:
+    for rec in [r for r in E.EDGE_BN if r["entry"] == "ir2rgb_bn_bwd" and r["args"][12] & 16 and r["args"][10] in (2, 513)]:
         a = rec["args"]
         P, C, act = a[10], a[11], a[12] & 15
         g, y, (gamma, beta, _, rm, rv) = _bn_inputs(rec, P, C)
-        gz = K.R.draw((P, C), g).double().numpy()
+        gz = R.draw((P, C), g).double().numpy()
         invstd = (1.0 / torch.sqrt(rv + 1e-5)).numpy()
         scale = gamma.numpy() * invstd
         shift = beta.numpy() - rm.numpy() * scale
         gz[~BR.sign_safe(y.numpy(), scale, shift)] = 0
         good = BR.bwd(gz, y.numpy(), scale, shift, rm.numpy(), invstd, act, fmt, frozen=True)
         bad = BR.bwd(gz, y.numpy(), scale, shift, rm.numpy(), invstd, act, fmt)
-        assert not BR.rejects(_rnd(good["gy"][0], fmt), good["gy"])
-        assert BR.rejects(_rnd(bad["gy"][0], fmt), good["gy"]), (P, C, act)
+        assert not BR.rejects(rnd(good["gy"][0], fmt), good["gy"])
+        assert BR.rejects(rnd(bad["gy"][0], fmt), good["gy"]), (P, C, act)

@@ -1,5 +1,5 @@
-"""The comparators of tests/test_window_ops_gpu.py must catch the bugs they are there for, and every entry point the
-window launches must be checked somewhere (no GPU).
+"""The comparators of oracle/replay_ops.py must catch the bugs they are there for, and every entry point the window
+launches must be checked somewhere (no GPU).
 
 At geometries of tests/window_geometries.json, fp64 "faulty outputs" are built from oracle/window_ops_ref.py -- a
 dropped reflection mirror, a wrong activation nibble, the align_corners lattice "fixed", a clamped pixel that keeps its
@@ -7,7 +7,6 @@ flow gradient, count_include_pad pooling, a loss mean over a rounded n, Adam wit
 un-updated n % 4 tail, swapped up-sampler taps -- and the bounds of oracle/bounds.py must reject each one, while the
 unfaulted reference rounded to the output format passes.
 """
-import importlib.util
 import os
 
 import numpy as np
@@ -15,41 +14,24 @@ import pytest
 import torch
 
 from oracle import bounds as B
+from oracle import replay_ops as G
 from oracle import window as WG
 from oracle import window_ops_ref as O
+from oracle.replay import passes, rnd
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 OPS = WG.op_entries()
 
 
-def _gpu_module():
-    spec = importlib.util.spec_from_file_location("_window_ops_gpu", os.path.join(HERE, "test_window_ops_gpu.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-G = _gpu_module()
-
-
 def _pick(entry, pred=lambda a: True):
     for r in OPS:
-        if r["entry"] == entry and ("args" not in r or pred(G._args(r))) and ("args" in r or pred(r)):
+        if r["entry"] == entry and ("args" not in r or pred(G.named_args(r))) and ("args" in r or pred(r)):
             return r
     raise LookupError(entry)
 
 
 def _gen(seed):
     return torch.Generator().manual_seed(seed)
-
-
-def _rnd(x, fmt):
-    dt = {"bf16": torch.bfloat16, "f16": torch.float16, "f32": torch.float32}[fmt]
-    return torch.from_numpy(np.ascontiguousarray(x)).to(dt).double().numpy()
-
-
-def _passes(got, ref, bnd):
-    return B.check_bound(got, ref, bnd)[0]
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -70,7 +52,7 @@ def test_every_op_record_is_replayed_or_covered():
     entries = {r["entry"] for r in OPS}
     assert entries, "the manifest holds no op records"
     missing = sorted(e for e in entries if e not in G.REPLAY and e not in G.COVERED_ELSEWHERE)
-    assert not missing, "op entries neither replayed by test_window_ops_gpu.py nor in COVERED_ELSEWHERE: " + \
+    assert not missing, "op entries neither in oracle/replay_ops.py's REPLAY nor in COVERED_ELSEWHERE: " + \
         ", ".join(missing)
     assert not set(G.REPLAY) & set(G.COVERED_ELSEWHERE)
     for e in entries & set(G.REPLAY):
@@ -80,6 +62,14 @@ def test_every_op_record_is_replayed_or_covered():
         path, name = test.split("::")
         with open(os.path.join(os.path.dirname(HERE), path)) as f:
             assert f"def {name}(" in f.read(), test
+
+
+def test_argument_names_match_the_prototypes():
+    """named_args and edge_records.op zip ARGS with a record's arguments or the prototype's types, and zip stops at the
+    shorter: a name too few or too many would shift or drop an argument silently."""
+    from ir2rgb_amd import _lib
+    for entry, names in G.ARGS.items():
+        assert len(names.split()) == len(_lib.PROTOTYPES[entry][1]) - 1, entry      # (the stream has no name)
 
 
 def test_launch_ids_of_op_records():
@@ -92,7 +82,7 @@ def test_launch_ids_of_op_records():
 @pytest.fixture(scope="module")
 def head():
     rec = _pick("ir2rgb_head_finish", lambda a: any(O.nibble(a["acts"], c) == 0 for c in range(a["Cout"])))
-    a = G._args(rec)
+    a = G.named_args(rec)
     a = dict(a, N=1)
     g = _gen(3)
     T = torch.randn(1, a["H"], a["W"], a["CT"], generator=g, dtype=torch.float64).numpy() * 0.5
@@ -104,7 +94,7 @@ def head():
 
 def test_head_finish_unfaulted_passes(head):
     a, T, bias, out, pre, bnd = head
-    assert _passes(_rnd(out, "f32"), out, bnd)
+    assert passes(rnd(out, "f32"), out, bnd)
 
 
 def test_head_finish_sigmoid_on_flow_channel_rejected(head):
@@ -112,7 +102,7 @@ def test_head_finish_sigmoid_on_flow_channel_rejected(head):
     co = next(c for c in range(a["Cout"]) if O.nibble(a["acts"], c) == 0)
     bad = out.copy()
     bad[:, co] = 1 / (1 + np.exp(-pre[:, co]))
-    assert not _passes(_rnd(bad, "f32"), out, bnd)
+    assert not passes(rnd(bad, "f32"), out, bnd)
 
 
 def test_head_finish_dropped_tile_edge_rejected(head):
@@ -121,13 +111,13 @@ def test_head_finish_dropped_tile_edge_rejected(head):
     bad = out.copy()
     bad[..., a["H"] - 1 - (a["H"] - 1) % 8:, :] = 0
     bad[..., a["W"] - 1 - (a["W"] - 1) % 16:] = 0
-    assert not _passes(_rnd(bad, "f32"), out, bnd)
+    assert not passes(rnd(bad, "f32"), out, bnd)
 
 
 @pytest.fixture(scope="module")
 def head_bwd():
     rec = _pick("ir2rgb_head_finish_bwd")
-    a = dict(G._args(rec), N=1)
+    a = dict(G.named_args(rec), N=1)
     g = _gen(4)
     shape = (1, a["Cout"], a["H"], a["W"])
     pre = torch.randn(shape, generator=g, dtype=torch.float64).numpy() * 2
@@ -135,8 +125,8 @@ def head_bwd():
     for co in range(a["Cout"]):
         nb = O.nibble(a["acts"], co)
         out[:, co] = np.tanh(pre[:, co]) if nb == 1 else (1 / (1 + np.exp(-pre[:, co])) if nb == 2 else pre[:, co] * a["mul"])
-    out = _rnd(out, "f32")
-    gout = _rnd(torch.randn(shape, generator=g, dtype=torch.float64).numpy(), "f32")
+    out = rnd(out, "f32")
+    gout = rnd(torch.randn(shape, generator=g, dtype=torch.float64).numpy(), "f32")
     dT, db, S, Sb = O.head_finish_bwd(gout, out, a["Cout"], a["KH"], a["CT"], a["pad_h"], a["acts"], a["mul"])
     return a, gout, out, dT, S
 
@@ -144,7 +134,7 @@ def head_bwd():
 @pytest.mark.parametrize("fmt", ["bf16", "f16"])
 def test_head_finish_bwd_unfaulted_passes(head_bwd, fmt):
     a, gout, out, dT, S = head_bwd
-    assert _passes(_rnd(dT, fmt), dT, B.bound_rw(dT, S, fmt, 3, 6))
+    assert passes(rnd(dT, fmt), dT, B.bound_rw(dT, S, fmt, 3, 6))
 
 
 @pytest.mark.parametrize("fmt", ["bf16", "f16"])
@@ -163,7 +153,7 @@ def test_head_finish_bwd_missing_mirror_rejected(head_bwd, fmt, edge):
     nb = O.nibble(a["acts"], 0)
     d = g * (1 - o * o) if nb == 1 else (g * o * (1 - o) if nb == 2 else g * a["mul"])
     bad[:, dst, :, ky] -= d
-    assert not _passes(_rnd(bad, fmt), dT, B.bound_rw(dT, S, fmt, 3, 6))
+    assert not passes(rnd(bad, fmt), dT, B.bound_rw(dT, S, fmt, 3, 6))
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -171,7 +161,7 @@ def test_head_finish_bwd_missing_mirror_rejected(head_bwd, fmt, edge):
 @pytest.fixture(scope="module")
 def warp():
     rec = _pick("ir2rgb_warp_blend_bwd")
-    a = G._args(rec)
+    a = G.named_args(rec)
     N, Cp, H, W = 1, a["Cp"], a["H"], a["W"]
     raw, prev, flow, w = (t.double().numpy() for t in G._warp_inputs(N, Cp, H, W, _gen(5)))
     gout = torch.randn(N, 3, H, W, generator=_gen(6), dtype=torch.float64).numpy()
@@ -184,14 +174,14 @@ def warp():
 
 def test_warp_blend_unfaulted_passes(warp):
     _, r, bout, bgf = warp
-    assert _passes(_rnd(r["out"], "f32"), r["out"], bout)
-    assert _passes(_rnd(r["gflow"], "f32"), r["gflow"], bgf)
+    assert passes(rnd(r["out"], "f32"), r["out"], bout)
+    assert passes(rnd(r["gflow"], "f32"), r["gflow"], bgf)
 
 
 def test_warp_blend_align_corners_lattice_rejected(warp):
     (raw, prev, flow, w, gout), r, bout, _ = warp
     bad = O.warp_blend(raw, prev, flow, w, align_corners_true=True)["out"]
-    assert not _passes(_rnd(bad, "f32"), r["out"], bout)
+    assert not passes(rnd(bad, "f32"), r["out"], bout)
 
 
 def test_warp_blend_clamped_flow_gradient_rejected(warp):
@@ -199,7 +189,7 @@ def test_warp_blend_clamped_flow_gradient_rejected(warp):
     bad = O.warp_blend(raw, prev, flow, w, gout=gout, keep_clamped_grad=True)["gflow"]
     clamped = ~((r["ix"] > 0) & (r["ix"] < w.shape[3] - 1))
     assert clamped.any()
-    assert not _passes(_rnd(bad, "f32"), r["gflow"], bgf)
+    assert not passes(rnd(bad, "f32"), r["gflow"], bgf)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -207,7 +197,7 @@ def test_warp_blend_clamped_flow_gradient_rejected(warp):
 @pytest.mark.parametrize("backward", [0, 1])
 def test_avgpool_count_include_pad_rejected(backward):
     rec = _pick("ir2rgb_avgpool3s2", lambda a: a["backward"] == backward)
-    a = G._args(rec)
+    a = G.named_args(rec)
     P, H, W = min(a["planes"], 2), a["H"], a["W"]
     g = _gen(7)
     if not backward:
@@ -221,8 +211,8 @@ def test_avgpool_count_include_pad_rejected(backward):
         bad, _ = O.avgpool3s2_bwd(gy, H, W, count_include_pad=True)
         bnd = B.bound_sum(ref, S, "f32", 8)
     assert set(np.unique(O.avgpool_divisors(H)[:, None] * O.avgpool_divisors(W)[None, :])) <= {1, 2, 3, 4, 6, 9}
-    assert _passes(_rnd(ref, "f32"), ref, bnd)
-    assert not _passes(_rnd(bad, "f32"), ref, bnd)
+    assert passes(rnd(ref, "f32"), ref, bnd)
+    assert not passes(rnd(bad, "f32"), ref, bnd)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -241,8 +231,8 @@ def test_loss_mean_over_rounded_n_rejected():
             ref = 1.0               # an all-positive mean: S = |ref|
             bad = ref * n / n_bad
             bnd = B.bound_rw(np.array([ref]), np.array([ref]), "f32", chain, 4)
-            assert _passes(np.float32(ref), np.array([ref]), bnd)
-            assert not _passes(np.array([np.float32(bad)], dtype=np.float64), np.array([ref]), bnd), (n, n_bad, chain)
+            assert passes(np.float32(ref), np.array([ref]), bnd)
+            assert not passes(np.array([np.float32(bad)], dtype=np.float64), np.array([ref]), bnd), (n, n_bad, chain)
             caught += 1
     assert caught
 
@@ -256,10 +246,10 @@ def adam_rec():
 
 def _adam_case(rec, n, step, **kw):
     g = _gen(8)
-    p = _rnd(torch.randn(n, generator=g, dtype=torch.float64).numpy() * 0.05, "f32")
-    gr = _rnd(torch.randn(n, generator=g, dtype=torch.float64).numpy() * 0.01, "f32")
-    m = np.zeros(n) if step == 1 else _rnd(torch.randn(n, generator=g, dtype=torch.float64).numpy() * 0.01, "f32")
-    v = np.zeros(n) if step == 1 else _rnd(torch.rand(n, generator=g, dtype=torch.float64).numpy() * 1e-4, "f32")
+    p = rnd(torch.randn(n, generator=g, dtype=torch.float64).numpy() * 0.05, "f32")
+    gr = rnd(torch.randn(n, generator=g, dtype=torch.float64).numpy() * 0.01, "f32")
+    m = np.zeros(n) if step == 1 else rnd(torch.randn(n, generator=g, dtype=torch.float64).numpy() * 0.01, "f32")
+    v = np.zeros(n) if step == 1 else rnd(torch.rand(n, generator=g, dtype=torch.float64).numpy() * 1e-4, "f32")
     b1, b2 = float(np.float32(rec["beta1"])), float(np.float32(rec["beta2"]))
     args = (p, gr, m, v, rec["lr"], b1, b2, rec["eps"], step)
     p1, m1, v1, upd, Sm, ss, den = O.adam(*args)
@@ -271,9 +261,9 @@ def _adam_case(rec, n, step, **kw):
 @pytest.mark.parametrize("step", [1, 14])
 def test_adam_without_bias_correction_rejected(adam_rec, step):
     args, p1, bp = _adam_case(adam_rec, 4099, step)
-    assert _passes(_rnd(p1, "f32"), p1, bp)
+    assert passes(rnd(p1, "f32"), p1, bp)
     bad = O.adam(*args, bias_correction=False)[0]
-    assert not _passes(_rnd(bad, "f32"), p1, bp)
+    assert not passes(rnd(bad, "f32"), p1, bp)
 
 
 @pytest.mark.parametrize("step", [1, 14])
@@ -284,7 +274,7 @@ def test_adam_tail_not_updated_rejected(adam_rec, step):
     args, p1, bp = _adam_case(adam_rec, n, step)
     bad = p1.copy()
     bad[n - n % 4:] = args[0][n - n % 4:]
-    assert not _passes(_rnd(bad, "f32"), p1, bp)
+    assert not passes(rnd(bad, "f32"), p1, bp)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -292,16 +282,16 @@ def test_adam_tail_not_updated_rejected(adam_rec, step):
 @pytest.mark.parametrize("fmt", ["bf16", "f16"])
 def test_flow_upsample_swapped_ky_parity_rejected(fmt):
     rec = _pick("ir2rgb_flow_upsample_slice")
-    a = G._args(rec)
+    a = G.named_args(rec)
     g = _gen(9)
-    x = _rnd(torch.randn(1, 2, a["h"], a["w"], generator=g, dtype=torch.float64).numpy() * 4, "bf16")
-    w = _rnd(torch.randn(2, 2, 4, 4, generator=g, dtype=torch.float64).numpy() * 0.5, "bf16")
-    bias = _rnd(torch.randn(2, generator=g, dtype=torch.float64).numpy(), "bf16") if a["bias"] else None
+    x = rnd(torch.randn(1, 2, a["h"], a["w"], generator=g, dtype=torch.float64).numpy() * 4, "bf16")
+    w = rnd(torch.randn(2, 2, 4, 4, generator=g, dtype=torch.float64).numpy() * 0.5, "bf16")
+    bias = rnd(torch.randn(2, generator=g, dtype=torch.float64).numpy(), "bf16") if a["bias"] else None
     ref, S = O.flow_upsample(x, w, bias)
     bad, _ = O.flow_upsample(x, w, bias, swap_ky_parity=True)
     bnd = B.bound_sum(ref, S, fmt, 9)
-    assert _passes(_rnd(ref, fmt), ref, bnd)
-    assert not _passes(_rnd(bad, fmt), ref, bnd)
+    assert passes(rnd(ref, fmt), ref, bnd)
+    assert not passes(rnd(bad, fmt), ref, bnd)
 
 
 def test_flow_upsample_matches_conv_transpose():

@@ -1,629 +1,28 @@
 """Every non-convolution launch of the 512 x 1024 training window, replayed at its recorded geometry against fp64.
 
-One test per ``"kind": "op"`` record of tests/window_geometries.json (oracle/window.py records them), with the
-references of oracle/window_ops_ref.py and the bounds of oracle/bounds.py, fixed before anything runs.  Entries that take
-a dtype run in bf16 and f16 from one fp64 reference on operands exact in both formats.  Every element is compared, and
-what a launch must leave alone is checked too: channels outside a slice, dT channels >= Cout*KH (zero), loss slots no
-term names, the pool bytes around each Adam tensor.  Bias gradients and loss slots must repeat bit for bit.
-Run with -s to see the worst err/bound table.  Entries replayed elsewhere are listed in COVERED_ELSEWHERE.
+One test per ``"kind": "op"`` record of tests/window_geometries.json (oracle/window.py records them), through the replay
+functions of oracle/replay_ops.py: the references of oracle/window_ops_ref.py and the bounds of oracle/bounds.py, fixed
+before anything runs.  Entries that take a dtype run in bf16 and f16 from one fp64 reference on operands exact in both
+formats.  Every element is compared, and what a launch must leave alone is checked too: channels outside a slice, dT
+channels >= Cout*KH (zero), loss slots no term names, the pool bytes around each Adam tensor.  Bias gradients and loss
+slots must repeat bit for bit.
+Run with -s to see the worst err/bound table.  Entries replayed elsewhere are listed in replay_ops.COVERED_ELSEWHERE.
 """
-import time
-import zlib
-
-import numpy as np
 import pytest
-import torch
 
-from oracle import bounds as B
-from oracle import conv_ref as R
+from oracle import replay
+from oracle import replay_ops as RO
 from oracle import window as WG
-from oracle import window_ops_ref as O
 
-DTYPES = (("bf16", torch.bfloat16, 1), ("f16", torch.float16, 2))
-
-ARGS = {    # argument names of the header's prototypes, without the stream
-    "ir2rgb_gather_f32": "src idx dst n",
-    "ir2rgb_avgpool3s2": "x y planes H W backward",
-    "ir2rgb_xexpand": "inp out N Cin H W Wout KW stride_w pad_w pad_mode dtype",
-    "ir2rgb_xexpand_cx": "inp out N Cin H W Wout KW stride_w pad_w pad_mode Cx dtype",
-    "ir2rgb_flow_upsample_slice": "inp weight bias out N h w ld c_off dtype",
-    "ir2rgb_head_finish": "T bias out N H W Cout KH CT pad_h acts mul",
-    "ir2rgb_warp_blend_fwd": "raw prev flow w out warp_out N Cp H W",
-    "ir2rgb_thin_grad_expand": "gz g64 g8 dbias N Cout H W dtype",
-    "ir2rgb_fold_reflect": "dxpad dx N H W C pad_h pad_w dtype",
-    "ir2rgb_head_finish_bwd": "gout out dT dbias partial N H W Cout KH CT pad_h acts mul dtype",
-    "ir2rgb_warp_blend_bwd": "gout raw prev flow w graw gflow gw N Cp H W",
-    "ir2rgb_xexpand_bwd": "dxe din N Cin H W Wout KW stride_w pad_w pad_mode dtype",
-    "ir2rgb_warp_diff_norm_fwd": "img1 img2 flow warped diff norm N C H W",
-    "ir2rgb_channelnorm_fwd": "inp out N C H W norm_deg",
-}
-
-# "op" entries of the window that this file does not replay, and the test that covers them at the window's geometry
-COVERED_ELSEWHERE = {
-    "ir2rgb_correlation_nhwc_half": "tests/test_ops_gpu.py::test_correlation_nhwc_half_full_size",
-}
-
-OPS = WG.op_entries()
-TABLE = []
-
-
-def _ids(recs):
-    seen, out = {}, []
-    for r in recs:
-        i = WG.launch_id(r)
-        seen[i] = seen.get(i, 0) + 1
-        out.append(i if seen[i] == 1 else f"{i}#{seen[i]}")
-    return out
-
-
-def _gen(rec):
-    return torch.Generator().manual_seed(zlib.crc32(WG.canon(rec).encode()))
-
-
-def _args(rec):
-    return dict(zip(ARGS[rec["entry"]].split(), rec["args"]))
-
-
-def _call(entry, *a):
-    from ir2rgb_amd import _lib
-    ref = next(x for x in a if isinstance(x, torch.Tensor))
-    rc = getattr(_lib.lib(), entry)(*a, _lib.current_stream(ref))
-    _lib.check(rc, entry)
-
-
-def _np(t):
-    return t.detach().double().cpu().numpy()
-
-
-def _assert(name, ok, ratio, i, over, shape):
-    assert ok, f"{name}: {over} elements over the bound (worst {ratio:.3g} at {np.unravel_index(i, shape)})"
-    return ratio
-
-
-def _bits(t):
-    return t.view(torch.int16) if t.element_size() == 2 else t.view(torch.int32)
-
-
-def _exact(name, got, ref_t):
-    """got (device half / fp32) == the fp64 reference rounded to nearest even into got's format, bit for bit."""
-    want = ref_t.to(got.dtype)
-    g = got.cpu()
-    bad = (_bits(g) != _bits(want)) & ~((g == 0) & (want == 0))        # (the sign of a zero is not checked)
-    assert not bool(bad.any()), f"{name}: {int(bad.sum())} elements differ from the rounded fp64 result " \
-                                f"(first at {tuple(int(v) for v in bad.nonzero()[0])})"
-    return 0.0
-
-
-def _sentinel(shape, dtype, dev):
-    return torch.full(shape, float("nan"), dtype=dtype, device=dev)
-
-
-# ---------------------------------------------------------------------------------------------------------------------
-def replay_gather(dev, rec, g):
-    a = _args(rec)
-    n = a["n"]
-    src = torch.randn(n, generator=g)
-    idx = torch.randint(-1, n, (n,), generator=g, dtype=torch.int32)
-    dst = _sentinel((n,), torch.float32, dev)
-    _call(rec["entry"], src.to(dev), idx.to(dev), dst, n)
-    torch.cuda.synchronize()
-    ref = torch.where(idx >= 0, src[idx.clamp(min=0).long()], torch.zeros(()))
-    return {"f32": _exact("gather", dst, ref.double())}
-
-
-def replay_avgpool(dev, rec, g):
-    a = _args(rec)
-    P, H, W = a["planes"], a["H"], a["W"]
-    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
-    if not a["backward"]:
-        x = R.draw((P, H, W), g)
-        y = _sentinel((P, Ho, Wo), torch.float32, dev)
-        _call(rec["entry"], x.to(dev), y, P, H, W, 0)
-        torch.cuda.synchronize()
-        ref, S = O.avgpool3s2(_np(x))
-        terms = 10          # <= 9 taps and the division
-    else:
-        gy = R.draw((P, Ho, Wo), g)
-        y = _sentinel((P, H, W), torch.float32, dev)
-        _call(rec["entry"], gy.to(dev), y, P, H, W, 1)
-        torch.cuda.synchronize()
-        ref, S = O.avgpool3s2_bwd(_np(gy), H, W)
-        terms = 8           # <= 4 quotients (one rounding each) and their sum
-    return {"f32": _assert("avgpool3s2", *B.check_bound(_np(y), ref, B.bound_sum(ref, S, "f32", terms)), ref.shape)}
-
-
-def replay_xexpand(dev, rec, g):
-    a = _args(rec)
-    N, Cin, H, W, Wout, KW, s, p, pm = (a[k] for k in "N Cin H W Wout KW stride_w pad_w pad_mode".split())
-    Cx = a.get("Cx", 64)
-    x = torch.randn(N, Cin, H, W, generator=g)
-    ref = O.xexpand(_np(x), Wout, KW, s, p, pm, Cx)
-    out = {}
-    for fmt, dtype, dt in DTYPES:
-        y = _sentinel((N, H, Wout, Cx), dtype, dev)
-        args = (N, Cin, H, W, Wout, KW, s, p, pm) + ((Cx,) if "Cx" in a else ()) + (dt,)
-        _call(rec["entry"], x.to(dev), y, *args)
-        torch.cuda.synchronize()
-        out[fmt] = _exact(f"{fmt} xexpand", y, torch.from_numpy(ref))
-    return out
-
-
-def replay_xexpand_bwd(dev, rec, g):
-    a = _args(rec)
-    N, Cin, H, W, Wout, KW, s, p, pm = (a[k] for k in "N Cin H W Wout KW stride_w pad_w pad_mode".split())
-    dxe = R.draw((N, H, Wout, 64), g)
-    ref, cnt = O.xexpand_bwd(_np(dxe), Cin, W, KW, s, p, pm)
-    S, _ = O.xexpand_bwd(np.abs(_np(dxe)), Cin, W, KW, s, p, pm)
-    out = {}
-    for fmt, dtype, dt in DTYPES:
-        din = _sentinel((N, Cin, H, W), torch.float32, dev)
-        _call(rec["entry"], dxe.to(dev, dtype), din, N, Cin, H, W, Wout, KW, s, p, pm, dt)
-        torch.cuda.synchronize()
-        bnd = B.bound_sum(ref, S, "f32", int(cnt.max()))
-        out[fmt] = _assert(f"{fmt} xexpand_bwd", *B.check_bound(_np(din), ref, bnd), ref.shape)
-    return out
-
-
-def replay_fold(dev, rec, g):
-    a = _args(rec)
-    N, H, W, C, ph, pw = (a[k] for k in "N H W C pad_h pad_w".split())
-    dxpad = R.draw((N, H + 2 * ph, W + 2 * pw, C), g)
-    ref, cnt = O.fold_reflect(_np(dxpad), ph, pw)
-    S, _ = O.fold_reflect(np.abs(_np(dxpad)), ph, pw)
-    out = {}
-    for fmt, dtype, dt in DTYPES:
-        dx = _sentinel((N, H, W, C), dtype, dev)
-        _call(rec["entry"], dxpad.to(dev, dtype), dx, N, H, W, C, ph, pw, dt)
-        torch.cuda.synchronize()
-        bnd = B.bound_sum(ref, S, fmt, int(cnt.max()))
-        out[fmt] = _assert(f"{fmt} fold_reflect", *B.check_bound(_np(dx), ref, bnd), ref.shape)
-    return out
-
-
-def replay_thin_grad(dev, rec, g):
-    a = _args(rec)
-    N, Cout, H, W = a["N"], a["Cout"], a["H"], a["W"]
-    gz = torch.randn(N, Cout, H, W, generator=g)
-    npix = N * H * W
-    want = torch.zeros(N, H, W, 8, dtype=torch.float64)
-    want[..., :Cout] = gz.double().permute(0, 2, 3, 1)
-    chain = -(-npix // 256) + 8         # a thread's pixels, then the 256-lane tree
-    ref = gz.double().sum((0, 2, 3)).numpy()
-    S = gz.double().abs().sum((0, 2, 3)).numpy()
-    out = {}
-    for fmt, dtype, dt in DTYPES:
-        runs = []
-        for _ in range(2):
-            g64 = _sentinel((N, H, W, 64), dtype, dev)
-            g8 = _sentinel((N, H, W, 8), dtype, dev)
-            db = _sentinel((Cout,), torch.float32, dev)
-            _call(rec["entry"], gz.to(dev), g64, g8, db, N, Cout, H, W, dt)
-            torch.cuda.synchronize()
-            runs.append(db.cpu())
-        _exact(f"{fmt} g8", g8, want)
-        _exact(f"{fmt} g64 (channels < 8)", g64[..., :8], want)
-        assert not bool(g64[..., 8:].ne(0).any()), f"{fmt}: g64 channels >= 8 are not zero"
-        assert torch.equal(_bits(runs[0]), _bits(runs[1])), f"{fmt}: dbias differs between two runs"
-        out[fmt] = _assert(f"{fmt} dbias", *B.check_bound(_np(runs[0]), ref, B.bound_rw(ref, S, "f32", chain, 0)),
-                           ref.shape)
-    return out
-
-
-def replay_flow_up(dev, rec, g):
-    a = _args(rec)
-    N, h, w, ld, off = a["N"], a["h"], a["w"], a["ld"], a["c_off"]
-    x = R.draw((N, 2, h, w), g, 4.0)
-    wt = R.draw((2, 2, 4, 4), g, 0.5)
-    bias = R.draw((2,), g) if a["bias"] else None
-    ref, S = O.flow_upsample(_np(x), _np(wt), None if bias is None else _np(bias))
-    ref, S = ref.transpose(0, 2, 3, 1), S.transpose(0, 2, 3, 1)
-    out = {}
-    for fmt, dtype, dt in DTYPES:
-        buf = R.draw((N, 2 * h, 2 * w, ld), g).to(dev, dtype)
-        before = buf.clone()
-        _call(rec["entry"], x.to(dev), wt.to(dev), None if bias is None else bias.to(dev), buf, N, h, w, ld, off, dt)
-        torch.cuda.synchronize()
-        keep = torch.ones(ld, dtype=torch.bool)
-        keep[off:off + 2] = False
-        assert torch.equal(buf[..., keep], before[..., keep]), f"{fmt}: flow up-sampler wrote outside its channels"
-        got = _np(buf[..., off:off + 2])
-        out[fmt] = _assert(f"{fmt} flow_upsample", *B.check_bound(got, ref, B.bound_sum(ref, S, fmt, 9)), ref.shape)
-    return out
-
-
-def replay_head_finish(dev, rec, g):
-    a = _args(rec)
-    N, H, W, Cout, KH, CT, pad, acts, mul = (a[k] for k in "N H W Cout KH CT pad_h acts mul".split())
-    T = R.draw((N, H, W, CT), g, 0.5)
-    bias = R.draw((Cout,), g, 0.5) if a["bias"] else None
-    ref, _, S = O.head_finish(_np(T), None if bias is None else _np(bias), Cout, KH, pad, acts, mul)
-    y = _sentinel((N, Cout, H, W), torch.float32, dev)
-    _call(rec["entry"], T.to(dev), None if bias is None else bias.to(dev), y, N, H, W, Cout, KH, CT, pad, acts, mul)
-    torch.cuda.synchronize()
-    bnd = B.bound_act(ref, O.act_slope(ref, acts, mul, Cout), S, KH + 1)
-    return {"f32": _assert("head_finish", *B.check_bound(_np(y), ref, bnd), ref.shape)}
-
-
-def replay_head_finish_bwd(dev, rec, g):
-    from ir2rgb_amd import _lib
-    a = _args(rec)
-    N, H, W, Cout, KH, CT, pad, acts, mul = (a[k] for k in "N H W Cout KH CT pad_h acts mul".split())
-    pre = torch.randn(N, Cout, H, W, generator=g, dtype=torch.float64) * 2
-    o64 = np.empty(pre.shape)
-    for co in range(Cout):
-        nb = O.nibble(acts, co)
-        p = pre[:, co].numpy()
-        o64[:, co] = np.tanh(p) if nb == 1 else (1 / (1 + np.exp(-p)) if nb == 2 else p * mul)
-    outv = torch.from_numpy(o64).float()
-    gout = torch.randn(N, Cout, H, W, generator=g)
-    ref, dbias, S, Sb = O.head_finish_bwd(_np(gout), _np(outv), Cout, KH, CT, pad, acts, mul)
-    rows = _lib.lib().ir2rgb_head_finish_bwd_rows(N, H, W)
-    chain = -(-N * H * W // (rows * 256)) + 256 + -(-rows // 32) + 32
-    out = {}
-    for fmt, dtype, dt in DTYPES:
-        runs = []
-        for _ in range(2):
-            dT = _sentinel((N, H, W, CT), dtype, dev)
-            db = _sentinel((Cout,), torch.float32, dev)
-            part = torch.empty(rows * 8, dtype=torch.float32, device=dev)
-            _call(rec["entry"], gout.to(dev), outv.to(dev), dT, db, part, N, H, W, Cout, KH, CT, pad, acts, mul, dt)
-            torch.cuda.synchronize()
-            runs.append(db.cpu())
-        assert torch.equal(_bits(runs[0]), _bits(runs[1])), f"{fmt}: dbias differs between two runs"
-        assert not bool(dT[..., Cout * KH:].ne(0).any()), f"{fmt}: dT channels >= Cout*KH are not zero"
-        r1 = _assert(f"{fmt} dT", *B.check_bound(_np(dT), ref, B.bound_rw(ref, S, fmt, 3, 6)), ref.shape)
-        r2 = _assert(f"{fmt} dbias", *B.check_bound(_np(runs[0]), dbias, B.bound_rw(dbias, Sb, "f32", chain, 6)),
-                     dbias.shape)
-        out[fmt] = max(r1, r2)
-    return out
-
-
-# warp_blend: flows drawn so that the fp64 sampling coordinates lie >= 0.02 from a cell edge, plus a band of pixels
-# (about 3 %) that sample beyond the border, where the clamp is active and the flow gradient must be zero
-def _warp_inputs(N, Cp, H, W, g):
-    def flow_1d(n, shape):
-        base = torch.arange(n, dtype=torch.float64).view([1] * (len(shape) - 1) + [n]).expand(shape)
-        cell = (base + torch.randint(-6, 7, shape, generator=g)).clamp(0, n - 2)
-        t = cell + 0.02 + 0.96 * torch.rand(shape, generator=g, dtype=torch.float64)
-        out_band = torch.rand(shape, generator=g) < 0.03
-        beyond = torch.where(torch.rand(shape, generator=g) < 0.5, -0.05 - 2 * torch.rand(shape, generator=g, dtype=torch.float64),
-                             n - 1 + 0.05 + 2 * torch.rand(shape, generator=g, dtype=torch.float64))
-        t = torch.where(out_band, beyond, t)
-        return ((t + 0.5) * (n - 1) / n - base).float()
-    fx = flow_1d(W, (N, H, W))
-    fy = flow_1d(H, (N, W, H)).transpose(1, 2)
-    flow = torch.stack([fx, fy], 1).contiguous()
-    raw = R.draw((N, 3, H, W), g)
-    prev = R.draw((N, Cp, H, W), g)
-    w = torch.rand(N, 1, H, W, generator=g).to(torch.bfloat16).float()
-    return raw, prev, flow, w
-
-
-def _ambiguous(r, H, W):
-    dx, dy = B.coord_delta(W), B.coord_delta(H)
-    ix, iy = r["ix"], r["iy"]
-    ax = (np.abs(ix - np.round(ix)) <= dx)
-    ay = (np.abs(iy - np.round(iy)) <= dy)
-    return ax | ay
-
-
-def replay_warp_fwd(dev, rec, g):
-    a = _args(rec)
-    N, Cp, H, W = a["N"], a["Cp"], a["H"], a["W"]
-    raw, prev, flow, w = _warp_inputs(N, Cp, H, W, g)
-    r = O.warp_blend(_np(raw), _np(prev), _np(flow), _np(w))
-    dx, dy = B.coord_delta(W), B.coord_delta(H)
-    y = _sentinel((N, 3, H, W), torch.float32, dev)
-    wo = _sentinel((N, 3, H, W), torch.float32, dev) if a["warp_out"] else None
-    _call(rec["entry"], raw.to(dev), prev.to(dev), flow.to(dev), w.to(dev), y, wo, N, Cp, H, W)
-    torch.cuda.synchronize()
-    bnd = B.C_AR * B.U32 * r["S_out"] + r["dout_dix"][:, :] * dx + r["dout_diy"] * dy + B.ETA["f32"]
-    ratio = _assert("warp_blend out", *B.check_bound(_np(y), r["out"], bnd), bnd.shape)
-    if wo is not None:
-        bw = B.C_AR * B.U32 * r["S_warp"] + r["dwarp_dix"] * dx + r["dwarp_diy"] * dy + B.ETA["f32"]
-        ratio = max(ratio, _assert("warp_blend warp", *B.check_bound(_np(wo), r["warp"], bw), bw.shape))
-    return {"f32": ratio}
-
-
-def replay_warp_bwd(dev, rec, g):
-    a = _args(rec)
-    N, Cp, H, W = a["N"], a["Cp"], a["H"], a["W"]
-    raw, prev, flow, w = _warp_inputs(N, Cp, H, W, g)
-    gout = R.draw((N, 3, H, W), g)
-    args = [_np(t) for t in (raw, prev, flow, w)]
-    r = O.warp_blend(*args, gout=_np(gout))
-    dx, dy = B.coord_delta(W), B.coord_delta(H)
-    graw = _sentinel((N, 3, H, W), torch.float32, dev)
-    gflow = _sentinel((N, 2, H, W), torch.float32, dev)
-    gw = _sentinel((N, 1, H, W), torch.float32, dev)
-    _call(rec["entry"], gout.to(dev), raw.to(dev), prev.to(dev), flow.to(dev), w.to(dev), graw, gflow, gw, N, Cp, H, W)
-    torch.cuda.synchronize()
-    r1 = _assert("graw", *B.check_bound(_np(graw), r["graw"], B.U32 * np.abs(r["graw"]) + B.ETA["f32"]), r["graw"].shape)
-    bgw = B.C_AR * B.U32 * r["S_gw"] + r["dgw_dix"] * dx + r["dgw_diy"] * dy + B.ETA["f32"]
-    r2 = _assert("gw", *B.check_bound(_np(gw), r["gw"], bgw), bgw.shape)
-    bgf = B.C_AR * B.U32 * r["S_gflow"] + np.stack([r["dgflow_x_diy"] * dy, r["dgflow_y_dix"] * dx], 1) + B.ETA["f32"]
-    got = _np(gflow)
-    amb = np.broadcast_to(_ambiguous(r, H, W)[:, None], got.shape)
-    err = np.abs(got - r["gflow"])
-    if amb.any():       # one-sided values: the cell on either side of the edge, the clamp on or off
-        for kw in ({"keep_clamped_grad": True},):
-            alt = O.warp_blend(*args, gout=_np(gout), **kw)["gflow"]
-            err = np.where(amb, np.minimum(err, np.abs(got - alt)), err)
-        for sx_, sy_ in ((-1, 0), (1, 0), (0, -1), (0, 1)):
-            f2 = args[2].copy()
-            f2[:, 0] += 2 * sx_ * dx
-            f2[:, 1] += 2 * sy_ * dy
-            alt = O.warp_blend(args[0], args[1], f2, args[3], gout=_np(gout))["gflow"]
-            err = np.where(amb, np.minimum(err, np.abs(got - alt)), err)
-    ratio = err / bgf
-    i = int(np.argmax(ratio))
-    assert np.isfinite(got).all() and ratio.max() <= 1.0, \
-        f"gflow: {int((ratio > 1).sum())} elements over the bound (worst {ratio.max():.3g} at {np.unravel_index(i, got.shape)})"
-    clamped = ~((r["ix"] > 0) & (r["ix"] < W - 1))
-    assert clamped.sum() > 0 and not np.any(got[:, 0][clamped & ~amb[:, 0]]), "flow gradient not zero where clamped"
-    print(f"\n  warp_blend_bwd: {int(amb[:, 0].sum())} pixels in the ambiguity band, {int(clamped.sum())} clamped in x")
-    return {"f32": max(r1, r2, float(ratio.max()))}
-
-
-# FlowNet2's fused warp -> diff -> channel norm: pixel-space flows drawn >= 0.02 from a cell edge (xf = x + dx is one
-# fp32 rounding, far inside coord_delta), some beyond the border (corners clamped)
-def _pixel_flow(N, H, W, g):
-    def comp(n, shape):
-        base = torch.arange(n, dtype=torch.float64).view([1] * (len(shape) - 1) + [n]).expand(shape)
-        cell = base + torch.randint(-8, 9, shape, generator=g)
-        t = cell + 0.02 + 0.96 * torch.rand(shape, generator=g, dtype=torch.float64)
-        return (t - base).float()
-    return torch.stack([comp(W, (N, H, W)), comp(H, (N, W, H)).transpose(1, 2)], 1).contiguous()
-
-
-def replay_warp_diff_norm(dev, rec, g):
-    a = _args(rec)
-    N, C, H, W = a["N"], a["C"], a["H"], a["W"]
-    img1, img2 = R.draw((N, C, H, W), g), R.draw((N, C, H, W), g)
-    flow = _pixel_flow(N, H, W, g)
-    v, dvx, dvy, S = O.resample2d(_np(img2), _np(flow))
-    d = _np(img1) - v
-    ev = B.C_AR * B.U32 * S + dvx * B.coord_delta(W) + dvy * B.coord_delta(H)
-    ed = ev + B.U32 * (np.abs(d) + np.abs(_np(img1)))
-    outs = {k: (_sentinel((N, C, H, W), torch.float32, dev) if a[k] else None) for k in ("warped", "diff")}
-    norm = _sentinel((N, 1, H, W), torch.float32, dev) if a["norm"] else None
-    _call(rec["entry"], img1.to(dev), img2.to(dev), flow.to(dev), outs["warped"], outs["diff"], norm, N, C, H, W)
-    torch.cuda.synchronize()
-    ratio = 0.0
-    if outs["warped"] is not None:
-        ratio = _assert("warped", *B.check_bound(_np(outs["warped"]), v, ev + B.ETA["f32"]), v.shape)
-    if outs["diff"] is not None:
-        ratio = max(ratio, _assert("diff", *B.check_bound(_np(outs["diff"]), d, ed + B.ETA["f32"]), d.shape))
-    if norm is not None:
-        # |d norm| <= sum_c |d_c| / norm * e_c <= sum_c e_c, and the squares, sum and sqrt: (C + 2) roundings of norm
-        nr = np.sqrt((d * d).sum(1, keepdims=True))
-        bn = ed.sum(1, keepdims=True) + (C + 2) * B.U32 * nr + B.ETA["f32"]
-        ratio = max(ratio, _assert("norm", *B.check_bound(_np(norm), nr, bn), nr.shape))
-    return {"f32": ratio}
-
-
-def replay_channelnorm(dev, rec, g):
-    a = _args(rec)
-    N, C, H, W = a["N"], a["C"], a["H"], a["W"]
-    x = torch.randn(N, C, H, W, generator=g)
-    ref = np.sqrt((_np(x) ** 2).sum(1, keepdims=True))
-    y = _sentinel((N, 1, H, W), torch.float32, dev)
-    _call(rec["entry"], x.to(dev), y, N, C, H, W, a["norm_deg"])
-    torch.cuda.synchronize()
-    bnd = (C + 2) * B.U32 * ref + B.ETA["f32"]
-    return {"f32": _assert("channelnorm", *B.check_bound(_np(y), ref, bnd), ref.shape)}
-
-
-# ---------------------------------------------------------------------------------------------------------------------
-# grouped losses
-def _loss_tensors(rec, g, dtype, dev):
-    """Per item: (a, b, mask) on the device and their fp64 copies.  Half operands are drawn exact in both formats."""
-    items = []
-    for it in rec["items"]:
-        n = it["n"]
-        if it["kind"] == 0:
-            a, b, m = R.draw((n,), g), R.draw((n,), g), None
-            items.append((a.to(dev, dtype), b.to(dev, dtype), None, _np(a), _np(b), None))
-            continue
-        a = R.draw((n,), g)
-        b = R.draw((n,), g) if it["b"] else None
-        m = (torch.rand(n // it["chw"] * it["hw"], generator=g) < 0.8).float() * \
-            torch.rand(n // it["chw"] * it["hw"], generator=g).to(torch.bfloat16).float() if it["kind"] == 2 else None
-        items.append((a.to(dev), None if b is None else b.to(dev), None if m is None else m.to(dev),
-                      _np(a), None if b is None else _np(b), None if m is None else _np(m)))
-    return items
-
-
-def _loss_array(rec, ts, grads=None):
-    from ir2rgb_amd import _lib
-    arr = (_lib.LossItem * len(rec["items"]))()
-    for i, (it, t) in enumerate(zip(rec["items"], ts)):
-        e = arr[i]
-        e.a, e.b, e.mask = t[0].data_ptr(), (t[1].data_ptr() if t[1] is not None else None), \
-            (t[2].data_ptr() if t[2] is not None else None)
-        e.ga = grads[i].data_ptr() if grads is not None and grads[i] is not None else None
-        e.n, e.hw, e.chw, e.weight, e.target, e.kind, e.slot = (it["n"], it["hw"], it["chw"], it["weight"], it["target"],
-                                                                 it["kind"], it["slot"])
-    return arr
-
-
-LOSS_BLOCKS = 512       # blocks of one loss launch (losses.hip), split over the items in proportion to n
-
-
-def loss_chain(rec, i):
-    """Longest fp32 chain of item i's slot: a lane's elements of its block slice (kind 0: 8 per uint4, four uint4 per
-    trip), the wave / block tree (6 + 3), the finish pass (a thread's blocks, then 8 levels)."""
-    ns = [it["n"] for it in rec["items"]]
-    total = float(sum(ns))
-    it = rec["items"][i]
-    nb = min(int((LOSS_BLOCKS - len(ns)) * it["n"] / total) + 1, -(-it["n"] // 2048))
-    if it["kind"] == 0:
-        per = -(-(it["n"] // 8) // nb)
-        lane = -(-per // 1024) * 4 * 8
-    else:
-        lane = -(-(-(-it["n"] // nb)) // 256)
-    return lane + 9 + 2 + 8
-
-
-def replay_loss_fwd(dev, rec, g):
-    from ir2rgb_amd import _lib
-    nslots = max(it["slot"] for it in rec["items"]) + 1
-    out = {}
-    for fmt, dtype, dt in DTYPES:
-        if fmt != "bf16" and not any(it["kind"] == 0 for it in rec["items"]):
-            continue        # the dtype only applies to the half operands of kind 0
-        ts = _loss_tensors(rec, g, dtype, dev)
-        ref = np.zeros(4)
-        S = np.zeros(4)
-        chain = 0
-        for i, (it, t) in enumerate(zip(rec["items"], ts)):
-            term, s = O.loss_term(it["kind"], t[3], t[4], t[5], it["target"], it["hw"], it["chw"])
-            ref[it["slot"]] += it["weight"] / it["n"] * term.sum()
-            S[it["slot"]] += abs(it["weight"]) / it["n"] * s.sum()
-            chain = max(chain, loss_chain(rec, i))
-        runs = []
-        for _ in range(2):
-            res = _sentinel((4,), torch.float32, dev)
-            part = torch.empty(_lib.lib().ir2rgb_loss_partial_elems(), dtype=torch.float32, device=dev)
-            arr = _loss_array(rec, ts)
-            rc = _lib.lib().ir2rgb_loss_multi_fwd(arr, len(rec["items"]), dt, part, res, _lib.current_stream(res))
-            _lib.check(rc, "loss_multi_fwd")
-            torch.cuda.synchronize()
-            runs.append(res.cpu())
-        assert torch.equal(_bits(runs[0]), _bits(runs[1])), f"{fmt}: loss slots differ between two runs"
-        assert torch.isnan(runs[0][nslots:]).all(), f"{fmt}: a slot beyond the last named one was written"
-        got = _np(runs[0][:nslots])
-        out[fmt] = _assert(f"{fmt} slots", *B.check_bound(got, ref[:nslots], B.bound_rw(ref[:nslots], S[:nslots], "f32",
-                                                                                          chain, 4)), (nslots,))
-    return out
-
-
-def replay_loss_bwd(dev, rec, g):
-    from ir2rgb_amd import _lib
-    out = {}
-    for fmt, dtype, dt in DTYPES:
-        if fmt != "bf16" and not any(it["kind"] == 0 for it in rec["items"]):
-            continue
-        ts = _loss_tensors(rec, g, dtype, dev)
-        gout = torch.randn(4, generator=g)
-        grads = [(torch.full_like(t[0], float("nan")) if it["ga"] else None) for it, t in zip(rec["items"], ts)]
-        arr = _loss_array(rec, ts, grads)
-        rc = _lib.lib().ir2rgb_loss_multi_bwd(arr, len(rec["items"]), dt, gout.to(dev), _lib.current_stream(ts[0][0]))
-        _lib.check(rc, "loss_multi_bwd")
-        torch.cuda.synchronize()
-        worst = 0.0
-        for it, t, ga in zip(rec["items"], ts, grads):
-            if ga is None:
-                continue
-            if it["kind"] == 0:     # sign(a - b) * half(gout * (weight / n)) exactly, the scale formed in fp32
-                gs = np.float32(gout[it["slot"]].item()) * (np.float32(it["weight"]) / np.float32(it["n"]))
-                want = torch.from_numpy(np.sign(t[3] - t[4])) * torch.tensor(float(gs)).to(dtype).double()
-                _exact(f"{fmt} L1 gradient", ga, want)
-                continue
-            gs = gout[it["slot"]].item() * it["weight"] / it["n"]
-            ref = O.loss_grad(it["kind"], t[3], t[4], t[5], it["target"], it["hw"], it["chw"], gs)
-            bnd = 4 * B.U32 * np.abs(ref) + B.ETA["f32"]
-            worst = max(worst, _assert(f"{fmt} kind {it['kind']} gradient", *B.check_bound(_np(ga), ref, bnd), ref.shape))
-        out[fmt] = worst
-    return out
-
-
-# ---------------------------------------------------------------------------------------------------------------------
-# Adam: one table with one tensor per recorded (n, alignment) class; each array in a pool of its own, at a 16-byte
-# offset (aligned) or a 4-byte one (not), with guard floats on both sides that must stay untouched
-GUARD = 8
-
-
-def _pool(n, aligned, fill, dev):
-    off = GUARD if aligned else GUARD + 1
-    pool = torch.full((n + 2 * GUARD + 4,), 777.0, dtype=torch.float32)
-    pool[off:off + n] = fill
-    pool = pool.to(dev)
-    return pool, off
-
-
-def replay_adam(dev, rec, g):
-    from ir2rgb_amd import _lib
-    E = _lib.lib().ir2rgb_adam_chunk_elems()
-    lr, b1, b2, eps = rec["lr"], rec["beta1"], rec["beta2"], rec["eps"]
-    b1f, b2f = float(np.float32(b1)), float(np.float32(b2))
-    worst = 0.0
-    for step in (1, 14):
-        rows, blocks, pools, host = [], [], [], []
-        for i, (n, aligned, _) in enumerate(rec["tensors"]):
-            p = torch.randn(n, generator=g) * 0.05
-            gr = torch.randn(n, generator=g) * 0.01
-            m = torch.zeros(n) if step == 1 else torch.randn(n, generator=g) * 0.01
-            v = torch.zeros(n) if step == 1 else torch.rand(n, generator=g) * 1e-4
-            arrs = [_pool(n, aligned, t, dev) for t in (p, gr, m, v)]
-            ptrs = [pl.data_ptr() + 4 * off for pl, off in arrs]
-            assert all(q % 16 == 0 for q in ptrs) == bool(aligned)
-            rows.append(ptrs + [n])
-            blocks += [(i, c) for c in range(-(-n // E))]
-            pools.append(arrs)
-            host.append((p, gr, m, v))
-        table = torch.tensor(rows, dtype=torch.int64, device=dev)
-        blk = torch.tensor(blocks, dtype=torch.int32, device=dev)
-        rc = _lib.lib().ir2rgb_adam_step(table, blk, len(blocks), lr, b1, b2, eps, step, _lib.current_stream(table))
-        _lib.check(rc, "adam_step")
-        torch.cuda.synchronize()
-        for (n, aligned, _), arrs, (p, gr, m, v) in zip(rec["tensors"], pools, host):
-            got = []
-            for pl, off in arrs:
-                h = pl.cpu()
-                guard = torch.cat([h[:off], h[off + n:]])
-                assert torch.all(guard == 777.0), f"n={n} aligned={aligned}: a pool guard was overwritten"
-                got.append(h[off:off + n].double().numpy())
-            p1, m1, v1, upd, Sm, ss, den = O.adam(*(t.double().numpy() for t in (p, gr, m, v)), lr, b1f, b2f, eps, step)
-            bm = 4 * B.U32 * Sm + B.ETA["f32"]
-            bv = 4 * B.U32 * v1 + B.ETA["f32"]
-            bp = B.U32 * np.abs(p1) + 16 * B.U32 * upd + ss * bm / den + B.ETA["f32"]
-            for name, gv, rv, bb in (("m", got[2], m1, bm), ("v", got[3], v1, bv), ("p", got[0], p1, bp)):
-                worst = max(worst, _assert(f"step {step} n={n} aligned={aligned} {name}",
-                                           *B.check_bound(gv, rv, bb), rv.shape))
-            assert np.array_equal(got[1], gr.double().numpy()), "the gradient was written"
-    return {"f32": worst}
-
-
-REPLAY = {
-    "ir2rgb_gather_f32": replay_gather,
-    "ir2rgb_avgpool3s2": replay_avgpool,
-    "ir2rgb_xexpand": replay_xexpand,
-    "ir2rgb_xexpand_cx": replay_xexpand,
-    "ir2rgb_xexpand_bwd": replay_xexpand_bwd,
-    "ir2rgb_fold_reflect": replay_fold,
-    "ir2rgb_thin_grad_expand": replay_thin_grad,
-    "ir2rgb_flow_upsample_slice": replay_flow_up,
-    "ir2rgb_head_finish": replay_head_finish,
-    "ir2rgb_head_finish_bwd": replay_head_finish_bwd,
-    "ir2rgb_warp_blend_fwd": replay_warp_fwd,
-    "ir2rgb_warp_blend_bwd": replay_warp_bwd,
-    "ir2rgb_warp_diff_norm_fwd": replay_warp_diff_norm,
-    "ir2rgb_channelnorm_fwd": replay_channelnorm,
-    "ir2rgb_loss_multi_fwd": replay_loss_fwd,
-    "ir2rgb_loss_multi_bwd": replay_loss_bwd,
-    "ir2rgb_adam_step": replay_adam,
-}
-REPLAYED = [r for r in OPS if r["entry"] in REPLAY]
+REPLAYED = [r for r in WG.op_entries() if r["entry"] in RO.REPLAY]
+TABLE = replay.Table()
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("rec", REPLAYED, ids=_ids(REPLAYED))
+@pytest.mark.parametrize("rec", REPLAYED, ids=replay.ids(REPLAYED))
 def test_window_op_launch(dev, rec):
-    t0 = time.perf_counter()
-    worst = REPLAY[rec["entry"]](dev, rec, _gen(rec))
-    dt = time.perf_counter() - t0
-    TABLE.append((WG.launch_id(rec), worst, dt))
-    print(f"\n{WG.launch_id(rec)}: worst err/bound " + " ".join(f"{k} {v:.3f}" for k, v in worst.items()) + f" ({dt:.1f} s)")
+    TABLE.run(WG.launch_id(rec), RO.REPLAY[rec["entry"]], dev, rec, replay.gen(rec))
 
 
 def teardown_module(module):
-    if TABLE:
-        print("\nper-launch worst err/bound:")
-        for name, worst, t in TABLE:
-            print("  " + " ".join(f"{k} {v:7.4f}" for k, v in worst.items()) + f"  {t:6.1f} s  {name}")
-        fam = {}
-        for name, worst, _ in TABLE:
-            f = name.split("-")[0]
-            fam[f] = max(fam.get(f, 0.0), max(worst.values()))
-        print("per family: " + ", ".join(f"{k} {v:.4f}" for k, v in sorted(fam.items())))
+    TABLE.report()
