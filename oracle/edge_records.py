@@ -1,6 +1,6 @@
 """The edge records (test-only data, nothing here touches a device): hand-written tables in the format of
-tests/window_geometries.json at small and ragged shapes, for the replays of oracle/replay_ops.py (EDGE) and
-oracle/replay_kernels.bn_case (EDGE_BN).
+tests/window_geometries.json at small and ragged shapes, for the replays of oracle/replay_ops.py (EDGE) and of
+oracle/replay_kernels.py: bn_case (EDGE_BN), replay_forward (EDGE_CONV) and replay_wgrad (EDGE_WGRAD).
 
 The window's own geometries (512 x 1024, widths a multiple of 128, H far above 2 * pad) are the least likely to expose
 an indexing bug.  A record is ``entry``, then ``args`` with booleans standing for pointers, or the ``items`` / ``tensors``
@@ -21,6 +21,49 @@ EDGE_BN is chosen from the dispatch in ir2rgb_bn_bwd and pointwise.hip:
 * ir2rgb_bn_finalize_apply: the odd row-half split and the 8-row unroll, pixel counts around the 32-row pass and the
   128-pixel chunk, 0 / 1 / 2 residuals, every activation -- and bit-identity with the two-launch path ("two_launch").
 * ir2rgb_bn_apply: 8 .. 64 channels, 1 .. 257 pixels.
+
+EDGE_CONV ("kind": "conv", entries "fwd_ws" / "fwd") is chosen from the forward dispatch.  Each record names its
+``form`` (CONV_FORMS) and states by hand the ``kernel`` that runs, whether a ``workspace`` is wanted and the ``tile`` of a
+statistics row; tests/test_edge_conv_cpu.py holds the library's host queries against all three.
+
+* tile_pixels (conv_mfma.hip): 64-, 128- and 256-pixel tiles, each with a ragged last pixel tile and a ragged channel
+  tile (Cout 72 / 136 / 200 / 1000); both sides of 256 tiles of 128 pixels (P = 3968 / 3969 at Cout = 1024) and of 256
+  tiles of 256 pixels with >= 40 K-steps (P = 7936 / 8001, 4x4 at Cin = 192).
+* launch_conv: every fixed tap template at stride 2 on 9 x 11, the runtime-tap form (5x5, 3x1, 7x7 = IR2RGB_MAX_TAPS),
+  the THIN forms (Cout <= 32 with 4x4 and 1x7) and Cout = 33 beside them.
+* the epilogue of conv_igemm_body: scalar stores (Cout % 4 != 0), 8-byte stores (Cout % 8 != 0), the staged form, fp32
+  output, every activation, bias and statistics present and absent, stats_per_sample with tiles cut inside a sample.
+* make_plan's channel slices ("fwd": conv2d_fwd_view): ldx > Cin at ci_off 8 / 64, ldy > Cout at co_off 8 / 100 / 192,
+  an odd co_off with Cout % 4 != 0.  The replay asserts that nothing outside the slice is written.
+* borders: reflection with pad < H <= 2 * pad per axis, Hout / Wout / the whole output of one pixel, zero padding
+  larger than the image, a tile that spans two samples.
+* make_plan's sub-pixel classes and ir2rgb_conv2d_fwd_ws: 3x3 (output_padding 0 / 1 / mixed) and 4x4 at stride 2,
+  4x1 at stride (2, 1) (two classes), odd outputs (classes of different Hsub / Wsub), a 1 x 1 input, per-class
+  workgroup counts of 1 and 2 (the (nwg + 7) & ~7 padding blocks), thin Cout, tp_all = 64, 64 because wg128 <= 320,
+  and 128; a transposed layer with a single class (stride 1, and the 1 x 1 output) runs conv_igemm_kernel.
+* conv_dot_ok: Cin 512 / 1024, 1x1 / 4x4, P = 1, 3, 5, 18 and 8195 (over the 8192-wave cap), a channel-slice input;
+  with statistics the same descriptor runs conv_igemm_kernel (``named`` keeps what the query, which sees the descriptor
+  alone, answers).
+* conv3x3p_plan (conv3x3_patch.hip): variants 1 .. 4, each at padding 0, 1 and 2 (2 also reflected: two pixels deep),
+  pad_mode 0 / 1 / 2, odd Hout, 200 tiles against 199 (conv_igemm_kernel); variants 3 and 4 through the workspace of
+  "fwd_ws".
+* conv1x7_thin_plan: Cin 64 / 128, Cout 1 .. 32 (1 and 3 inside ldy = 4: the plan wants ldy % 4 == 0), W = 4, 5, 127,
+  129, 514 segments on 512 workgroups; with a bias or statistics the general kernel.
+* conv7x1_col_plan: Cout 64 / 128, H = 4, 7, 9, W = 1, 31, 33, N = 2, a channel slice, 540 tiles on 512 workgroups.
+
+EDGE_WGRAD (entry "wgrad"; ``splits`` = workspace slabs of the plain call, 0 = written directly) from wgrad_mfma.hip.
+replay_wgrad runs every record plain and accumulating; the accumulating call of a nine-tap record takes the one-tap
+kernel (wgrad_impl), so each of those records covers both.
+
+* plan: tpb = 2 with an odd tap count (3x3 at Cb <= 64) against tpb = 1, Ca / Cb of 8 .. 200, Q = 35 < 64 and
+  Q % 64 != 0, a geometry the cost model splits (16 and 8 slabs) and ones it cannot (< 8 K-steps), stride 2 on odd
+  sizes, transposed stride 2 with output_padding 0 / 1, reflection with pad < H <= 2 * pad, N = 3.
+* launch_wgrad_finish: <= 16 taps (tiled), 25 / 49 taps (the gather form), > 64 splits (wide).
+* plan9: Win = 64 / 128 / 192, H = 2 and odd H, ksplit == 1 (Q / 64 < 16: direct write) and > 1 (wgrad_sum_kernel),
+  pad_mode 0 / 1, N = 2, 128 -> 192 channels.
+* plan_line / launch_line: 7x1 at stride 1 (column kernel) and 2 (line kernel), 4x1 at stride 2 (column) and 1 (line),
+  1x7, 3x3 / stride 2 with tl = 1, 2, 128 (also transposed) and tl = 4 (the one-tap kernel); Wq % 64 != 0, fewer than
+  8 K-steps, a short last split, 65 splits, reflection on the taps' axis with pad < H <= 2 * pad.
 """
 from oracle.replay_ops import ARGS
 
@@ -246,3 +289,313 @@ def _records():
 
 
 EDGE_BN = _records()
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Convolution forward and weight gradient.  ``kernel``, ``workspace``, ``tile`` / ``splits`` and ``form`` are the
+# expectation, written by hand from the dispatch code; tests/test_edge_conv_cpu.py holds the library's host queries
+# against them.
+IGEMM, CLASSES, DOT = "conv_igemm_kernel", "conv_igemm_classes_kernel", "conv_dot_kernel"
+PATCH, THIN7, COL7 = "conv3x3_patch_kernel", "conv1x7_thin_kernel", "conv7x1_col_kernel"
+
+CONV_FORMS = (
+    "tile:64", "tile:128", "tile:256", "tile:127-tiles", "tile:255-tiles",
+    "taps:3x3", "taps:4x4", "taps:7x1", "taps:1x7", "taps:4x1", "taps:2x2", "taps:2x1", "taps:1x2", "taps:1x1",
+    "taps:runtime", "thin:4x4", "thin:1x7", "thin:33",
+    "store:scalar", "store:vector", "store:f32", "act", "stats:per-sample",
+    "slice:in", "slice:out", "slice:odd",
+    "border:reflect-deep", "border:one-pixel", "border:overpad", "border:two-samples",
+    "classes:64", "classes:64-capped", "classes:128", "classes:two", "classes:1x1-input", "classes:thin",
+    "transposed:one-class",
+    "dot", "dot:capped", "dot:slice", "dot:stats",
+    "patch:1", "patch:2", "patch:3", "patch:4", "patch:adjoint", "patch:200-tiles", "patch:199-tiles",
+    "thin1x7", "thin1x7:slice", "thin1x7:wrap", "thin1x7:bias",
+    "col7x1", "col7x1:wrap",
+)
+WGRAD_FORMS = (
+    "onetap:tpb2", "onetap:tpb1", "onetap:split", "onetap:stride2", "onetap:transposed", "onetap:reflect-deep",
+    "onetap:gather-finish", "onetap:tl4",
+    "nine:direct", "nine:split",
+    "line:col7", "line:line7", "line:col4", "line:line4", "line:1x7", "line:3x3s2", "line:3x3s2-transposed",
+    "line:one-split", "line:short-last-split", "line:wide-finish", "line:reflect-deep",
+)
+
+
+def _pair(v):
+    return (v, v) if isinstance(v, int) else tuple(v)
+
+
+def geometry(N, Cin, H, W, Cout, k, stride=1, pad=0, pad_mode=0, transposed=0, output_padding=0, act=0, out_f32=0, ldx=0,
+             ci_off=0, ldy=0, co_off=0, sps=0):
+    """A descriptor in the manifest's format (every field of oracle.window.DESC_FIELDS), Hout / Wout filled in."""
+    (kh, kw), (sh, sw), (ph, pw) = _pair(k), _pair(stride), _pair(pad)
+    oh, ow = _pair(output_padding)
+    if transposed:
+        Ho, Wo = (H - 1) * sh - 2 * ph + kh + oh, (W - 1) * sw - 2 * pw + kw + ow
+    else:
+        Ho, Wo = (H + 2 * ph - kh) // sh + 1, (W + 2 * pw - kw) // sw + 1
+    return {"N": N, "Hin": H, "Win": W, "Cin": Cin, "Hout": Ho, "Wout": Wo, "Cout": Cout, "kh": kh, "kw": kw, "stride_h": sh,
+            "stride_w": sw, "pad_h": ph, "pad_w": pw, "pad_mode": pad_mode, "transposed": transposed, "dtype": 1, "act": act,
+            "out_f32": out_f32, "ldx": ldx, "ci_off": ci_off, "ldy": ldy, "co_off": co_off, "stats_per_sample": sps}
+
+
+def conv(form, kernel, tile, *geo, entry="fwd_ws", bias=False, stats=False, workspace=False, named=None, seed=None, **kw):
+    """A forward record.  ``tile``: the pixels of a statistics row -- an integer for the implicit-GEMM kernels
+    (tile_pixels), (rows, columns) for the patch and column kernels.  ``named``: what ir2rgb_conv2d_kernel_name answers
+    where the launch's bias / statistics arguments, which the query does not see, send it to another kernel."""
+    assert form in CONV_FORMS, form
+    rec = {"kind": "conv", "entry": entry, "desc": geometry(*geo, **kw), "kernel": kernel, "bias": bias, "stats": stats,
+           "workspace": workspace, "form": form, "tile": tile}
+    if named is not None:
+        rec["named"] = named
+    if seed is not None:
+        rec["seed"] = seed
+    return rec
+
+
+def wgrad(form, kernel, splits, *geo, **kw):
+    """A weight-gradient record.  ``splits``: the slabs of the plain call's workspace (0: written directly)."""
+    assert form in WGRAD_FORMS, form
+    return {"kind": "conv", "entry": "wgrad", "desc": geometry(*geo, **kw), "kernel": kernel, "form": form,
+            "splits": splits}
+
+
+def _tiles():
+    return [
+        # 64-pixel tiles: P = 65, 77, 99 and channel tiles of 72, 136 (128 + 8), 200 (128 + 72)
+        conv("tile:64", IGEMM, 64, 1, 64, 5, 13, 72, 1, stats=True),
+        conv("tile:64", IGEMM, 64, 1, 64, 7, 11, 136, 3, pad=1, pad_mode=1, bias=True, stats=True),
+        conv("tile:64", IGEMM, 64, 1, 128, 9, 11, 200, 3, pad=1, stats=True),
+        # Cout = 1000 / 1024: eight channel tiles, 128-pixel tiles from 32 of them on (P = 3969: the last holds one pixel)
+        conv("tile:128", IGEMM, 128, 1, 64, 126, 126, 1000, 2, stride=2, bias=True, stats=True),
+        conv("tile:127-tiles", IGEMM, 64, 1, 64, 62, 64, 1024, 1, stats=True),
+        # 48 K-steps (>= 40) and P = 8001: 32 256-pixel tiles, the last of 65 pixels; P = 7936: 31 of them, so 128
+        conv("tile:256", IGEMM, 256, 1, 192, 66, 130, 1000, 4, bias=True, stats=True),
+        conv("tile:255-tiles", IGEMM, 128, 1, 192, 65, 131, 1024, 4, stats=True),
+    ]
+
+
+def _taps():
+    out = []
+    fixed = ((3, 3), (4, 4), (7, 1), (1, 7), (4, 1), (2, 2), (2, 1), (1, 2), (1, 1))
+    for i, (kh, kw) in enumerate(fixed):      # stride 2 on 9 x 11, alternately zero and reflection padding
+        out.append(conv(f"taps:{kh}x{kw}", IGEMM, 64, 1 + i % 2, 64, 9, 11, (40, 72, 136)[i % 3], (kh, kw), stride=2,
+                        pad=(kh // 2, kw // 2), pad_mode=i % 2, bias=i % 2 == 0, stats=True))
+    out.append(conv("taps:runtime", IGEMM, 64, 1, 64, 9, 11, 72, 5, stride=2, pad=2, pad_mode=1, stats=True))
+    out.append(conv("taps:runtime", IGEMM, 64, 2, 64, 9, 11, 40, (3, 1), stride=(2, 1), pad=(1, 0), bias=True))
+    out.append(conv("taps:runtime", IGEMM, 64, 1, 64, 9, 11, 136, 7, pad=3, pad_mode=1, stats=True))   # IR2RGB_MAX_TAPS
+    out.append(conv("thin:4x4", IGEMM, 64, 1, 64, 9, 11, 32, 4, stride=2, pad=1, bias=True, stats=True))
+    out.append(conv("thin:33", IGEMM, 64, 1, 64, 9, 11, 33, 4, stride=2, pad=1, bias=True, stats=True))
+    out.append(conv("thin:1x7", IGEMM, 64, 2, 64, 5, 9, 3, (1, 7), pad=(0, 3), pad_mode=1, bias=True))
+    out.append(conv("thin:1x7", IGEMM, 64, 1, 128, 5, 9, 32, (1, 7), pad=(0, 3), pad_mode=1, stats=True))
+    return out
+
+
+def _epilogue():
+    out = []
+    for i, Cout in enumerate((3, 5, 130)):    # scalar stores; 130: the second channel tile holds two channels
+        out.append(conv("store:scalar", IGEMM, 64, 2, 64, 5, 7, Cout, 3, pad=1, bias=i != 1, stats=i != 0))
+    for i, Cout in enumerate((4, 12, 36)):    # 8-byte stores straight from the registers (Cout % 8 != 0)
+        out.append(conv("store:vector", IGEMM, 64, 2, 64, 5, 7, Cout, 3, pad=1, pad_mode=1, bias=i != 1, stats=i != 0))
+    for Cout in (1, 5, 8, 40):
+        out.append(conv("store:f32", IGEMM, 64, 1, 64, 5, 7, Cout, 3, pad=1, out_f32=1, bias=Cout != 8, stats=Cout == 40))
+    for act in (1, 2, 3):
+        for Cout in (5, 72):
+            out.append(conv("act", IGEMM, 64, 1, 64, 5, 7, Cout, 3, pad=1, act=act, bias=True, stats=Cout == 72))
+    # tiles cut inside a sample: 77 pixels = 64 + 13 per sample; 1325 = 10 * 128 + 45 per sample at TP = 128
+    out.append(conv("stats:per-sample", IGEMM, 64, 3, 64, 7, 11, 72, 3, pad=1, sps=1, stats=True))
+    out.append(conv("stats:per-sample", IGEMM, 64, 3, 64, 7, 11, 5, 3, pad=1, sps=1, bias=True, stats=True))
+    out.append(conv("stats:per-sample", IGEMM, 128, 3, 64, 25, 53, 1024, 1, sps=1, stats=True))
+    return out
+
+
+def _slices():
+    f = dict(entry="fwd")
+    return [
+        conv("slice:in", IGEMM, 64, 2, 64, 5, 7, 72, 3, pad=1, ldx=136, ci_off=8, bias=True, **f),
+        conv("slice:in", IGEMM, 64, 1, 64, 5, 7, 40, 3, pad=1, pad_mode=1, ldx=192, ci_off=64, stats=True, **f),
+        conv("slice:out", IGEMM, 64, 2, 64, 5, 7, 72, 3, pad=1, ldy=200, co_off=8, bias=True, stats=True, **f),
+        conv("slice:out", IGEMM, 64, 1, 64, 5, 7, 40, 3, pad=1, ldy=172, co_off=100, **f),          # not staged: co_off % 8
+        conv("slice:out", IGEMM, 64, 1, 64, 5, 7, 136, 1, ldx=72, ci_off=8, ldy=328, co_off=192, bias=True, **f),
+        conv("slice:odd", IGEMM, 64, 2, 64, 5, 7, 3, 3, pad=1, ldy=7, co_off=1, bias=True, **f),
+        conv("slice:odd", IGEMM, 64, 1, 64, 5, 7, 5, 3, pad=1, out_f32=1, ldy=9, co_off=3, stats=True, **f),
+    ]
+
+
+def _borders():
+    out = []
+    for H, W in ((4, 7), (6, 4), (7, 6), (4, 4)):           # 7x7 reflection: pad < H <= 2 * pad
+        out.append(conv("border:reflect-deep", IGEMM, 64, 2, 64, H, W, 40, 7, pad=3, pad_mode=1, stats=True))
+    out.append(conv("border:reflect-deep", IGEMM, 64, 1, 64, 2, 2, 72, 3, pad=1, pad_mode=1, bias=True))
+    out.append(conv("border:one-pixel", IGEMM, 64, 2, 64, 3, 9, 40, 3, stats=True))                   # Hout = 1
+    out.append(conv("border:one-pixel", IGEMM, 64, 1, 64, 10, 2, 40, 4, stride=2, pad=1, bias=True))   # Wout = 1
+    out.append(conv("border:one-pixel", IGEMM, 64, 1, 64, 1, 1, 72, 1, bias=True, stats=True))
+    out.append(conv("border:overpad", IGEMM, 64, 1, 64, 1, 2, 40, 3, pad=2, bias=True, stats=True))
+    out.append(conv("border:overpad", IGEMM, 64, 2, 64, 2, 2, 72, 7, pad=3))
+    out.append(conv("border:two-samples", IGEMM, 64, 3, 64, 5, 9, 72, 3, pad=1, pad_mode=1, bias=True, stats=True))
+    return out
+
+
+def _classes():
+    t = dict(transposed=1, stride=2)
+    return [
+        # 9 x 13 / 10 x 14 outputs: classes of 35, 30, 28, 24 pixels -- one workgroup each, seven padding blocks behind it
+        conv("classes:64", CLASSES, 64, 1, 64, 5, 7, 72, 3, pad=1, bias=True, stats=True, **t),
+        conv("classes:64", CLASSES, 64, 2, 64, 5, 7, 136, 3, pad=1, output_padding=1, stats=True, **t),
+        conv("classes:64", CLASSES, 64, 1, 128, 5, 3, 40, 4, pad=1, bias=True, act=3, **t),
+        conv("classes:64", CLASSES, 64, 2, 64, 5, 7, 72, 3, pad=1, output_padding=(0, 1), out_f32=1, **t),
+        conv("classes:two", CLASSES, 64, 1, 64, 5, 7, 72, (4, 1), transposed=1, stride=(2, 1), pad=(1, 0), bias=True, stats=True),
+        conv("classes:1x1-input", CLASSES, 64, 1, 64, 1, 1, 72, 3, pad=1, output_padding=1, bias=True, stats=True, **t),
+        conv("classes:1x1-input", IGEMM, 64, 1, 64, 1, 1, 72, 3, pad=1, bias=True, **t),      # one output pixel: one class
+        conv("classes:thin", CLASSES, 64, 2, 64, 5, 7, 3, 3, pad=1, output_padding=1, bias=True, **t),
+        conv("classes:thin", CLASSES, 64, 1, 64, 5, 7, 32, 4, pad=1, stats=True, **t),
+        # Cout = 1024: 65 x 65 -> 34 * 8 = 272 workgroups of 128 pixels (<= 320: 64); 71 x 73 -> 41 * 8 = 328 (128)
+        conv("classes:64-capped", CLASSES, 64, 1, 64, 33, 33, 1024, 3, pad=1, stats=True, **t),
+        conv("classes:128", CLASSES, 128, 1, 64, 36, 37, 1024, 3, pad=1, bias=True, stats=True, **t),
+        conv("transposed:one-class", IGEMM, 64, 2, 64, 5, 7, 72, 3, transposed=1, pad=1, bias=True, stats=True),
+        conv("transposed:one-class", IGEMM, 64, 1, 64, 5, 7, 40, 4, transposed=1, pad=1),
+    ]
+
+
+def _dots():
+    f = dict(out_f32=1)
+    return [
+        conv("dot", DOT, 64, 1, 512, 1, 1, 1, 1, bias=True, **f),                           # P = 1
+        conv("dot", DOT, 64, 1, 1024, 1, 3, 1, 1, **f),                                     # P = 3
+        conv("dot", DOT, 64, 1, 1024, 2, 6, 1, 4, pad=1, bias=True, act=1, **f),            # P = 5
+        conv("dot", DOT, 64, 2, 512, 2, 2, 1, 4, pad=2, bias=True, **f),                    # P = 18
+        conv("dot:capped", DOT, 64, 1, 512, 55, 149, 1, 1, bias=True, **f),                # P = 8195 > 8192 waves
+        conv("dot:capped", DOT, 64, 1, 512, 56, 150, 1, 4, pad=1, **f),
+        conv("dot:slice", DOT, 64, 2, 512, 3, 3, 1, 4, pad=2, ldx=520, ci_off=8, bias=True, entry="fwd", **f),
+        conv("dot:stats", IGEMM, 64, 1, 1024, 2, 6, 1, 4, pad=1, bias=True, act=1, stats=True, named=DOT, **f),
+        conv("dot:stats", IGEMM, 64, 1, 512, 1, 3, 1, 1, stats=True, named=DOT, **f),
+    ]
+
+
+def _patches():
+    s = dict(bias=True, stats=True)
+    return [
+        # variant 1 (2 x 64 pixels x 64 channels): 2 * 12 * 3 * 3 = 216 tiles, Hout = 23 odd, Wout = 190 = 2 * 64 + 62
+        conv("patch:1", PATCH, (2, 64), 2, 256, 23, 190, 192, 3, pad=1, pad_mode=1, **s),
+        conv("patch:1", PATCH, (2, 64), 2, 256, 25, 192, 192, 3, pad=0, stats=True),
+        conv("patch:1", PATCH, (2, 64), 2, 256, 21, 188, 192, 3, pad=2, bias=True),
+        conv("patch:adjoint", PATCH, (2, 64), 2, 128, 24, 192, 192, 3, pad=1, pad_mode=2, **s),
+        # Cout = 128, Wout = 250: 25 * 4 * 2 = 200 tiles at Hout = 50
+        conv("patch:200-tiles", PATCH, (2, 64), 1, 256, 50, 250, 128, 3, pad=1, **s),
+        # Cout = 64, Wout = 64: one tile per row pair -- 200 at Hout = 399, 199 at Hout = 397 (the general kernel)
+        conv("patch:200-tiles", PATCH, (2, 64), 1, 256, 399, 64, 64, 3, pad=1, pad_mode=1, stats=True),
+        conv("patch:199-tiles", IGEMM, 64, 1, 256, 397, 64, 64, 3, pad=1, pad_mode=1, **s),
+        # variant 2 (2 x 128 x 128): 25 * 1 * 8 = 200 tiles
+        conv("patch:2", PATCH, (2, 128), 1, 256, 49, 120, 1024, 3, pad=1, pad_mode=1, **s),
+        conv("patch:adjoint", PATCH, (2, 128), 1, 128, 50, 128, 1024, 3, pad=1, pad_mode=2, stats=True),
+        # ... without padding, and with two reflected pixels on each side of the 2 x 128 tile
+        conv("patch:2", PATCH, (2, 128), 1, 256, 51, 122, 1024, 3, pad=0, stats=True),
+        conv("patch:2", PATCH, (2, 128), 1, 256, 47, 118, 1024, 3, pad=2, pad_mode=1, **s),
+        # the split forms (Cin >= 512, a workspace): variant 4 (4 rows) at Hout = 11, variant 3 at Hout = 10 (12 / 10 > 1.13)
+        conv("patch:4", PATCH, (2, 64), 3, 512, 11, 64, 768, 3, pad=1, workspace=True, **s),
+        conv("patch:3", PATCH, (2, 64), 3, 512, 10, 64, 1024, 3, pad=1, pad_mode=1, workspace=True, **s),
+        # ... both at padding 0 and 2 (Hout = 11 / 10 again), the latter reflected two pixels deep
+        conv("patch:4", PATCH, (2, 64), 3, 512, 13, 66, 768, 3, pad=0, workspace=True, stats=True),
+        conv("patch:4", PATCH, (2, 64), 3, 512, 9, 62, 768, 3, pad=2, pad_mode=1, workspace=True, **s),
+        conv("patch:3", PATCH, (2, 64), 3, 512, 12, 66, 1024, 3, pad=0, workspace=True, bias=True),
+        conv("patch:3", PATCH, (2, 64), 3, 512, 8, 62, 1024, 3, pad=2, pad_mode=1, workspace=True, **s),
+        conv("patch:3", PATCH, (2, 64), 3, 512, 8, 62, 1024, 3, pad=2, workspace=True, stats=True),
+    ]
+
+
+def _thin1x7():
+    k = dict(k=(1, 7), pad=(0, 3), pad_mode=1, out_f32=1)
+    out = []
+    for i, W in enumerate((4, 5, 127, 129)):
+        Cin, Cout = (64, 128)[i % 2], (4, 8, 32, 4)[i]
+        out.append(conv("thin1x7", THIN7, 64, 1 + i % 2, Cin, 3, W, Cout, **k))
+    # (the plan wants 16-byte pixel rows, ldy % 4 == 0: one or three channels only inside a wider buffer)
+    out.append(conv("thin1x7:slice", THIN7, 64, 1, 64, 3, 4, 1, ldy=4, entry="fwd", **k))
+    out.append(conv("thin1x7", THIN7, 64, 1, 64, 2, 9, 32, **k))
+    out.append(conv("thin1x7:slice", THIN7, 64, 2, 128, 3, 9, 3, ldy=4, entry="fwd", **k))
+    out.append(conv("thin1x7:slice", THIN7, 64, 1, 64, 3, 5, 4, ldx=72, ci_off=8, ldy=12, co_off=8, entry="fwd", **k))
+    # 257 * 2 = 514 segments on 512 workgroups; its general-kernel plan (the statistics rows) has 260 tiles of 128
+    out.append(conv("thin1x7:wrap", THIN7, 128, 1, 64, 257, 129, 4, **k))
+    out.append(conv("thin1x7:bias", IGEMM, 64, 1, 64, 3, 5, 4, bias=True, named=THIN7, **k))
+    out.append(conv("thin1x7:bias", IGEMM, 64, 2, 128, 3, 127, 32, stats=True, named=THIN7, **k))
+    return out
+
+
+def _col7x1():
+    k = dict(k=(7, 1), pad=(3, 0), pad_mode=1)
+    out = []
+    i = 0
+    for H in (4, 7, 9):
+        for W in (1, 31, 33):
+            out.append(conv("col7x1", COL7, (8, 32), 1 + i % 2, 64, H, W, (64, 128)[i % 2], bias=i % 3 == 0,
+                            stats=i % 4 != 3, **k))
+            i += 1
+    out.append(conv("col7x1", COL7, (8, 32), 2, 64, 9, 33, 128, ldx=72, ci_off=8, ldy=132, co_off=4, entry="fwd", bias=True, **k))
+    out.append(conv("col7x1:wrap", COL7, (8, 32), 3, 64, 44, 929, 64, bias=True, stats=True, **k))   # 3 * 6 * 30 = 540 tiles
+    return out
+
+
+EDGE_CONV = (_tiles() + _taps() + _epilogue() + _slices() + _borders() + _classes() + _dots() + _patches() + _thin1x7()
+             + _col7x1())
+
+ONETAP, NINE, LINE, COL = "conv_wgrad_kernel", "conv_wgrad3x3_kernel", "conv_wgrad_line_kernel", "conv_wgrad_col_kernel"
+
+
+def _onetap():
+    out = []
+    # 3x3 with Cb = 64: tap pairs (five, the last half-empty); Cb = 72: one tap per workgroup.  Q = 35 < 64, 99, 231
+    out.append(wgrad("onetap:tpb2", ONETAP, 1, 1, 64, 5, 7, 72, 3, pad=1))
+    out.append(wgrad("onetap:tpb2", ONETAP, 1, 3, 8, 7, 11, 8, 3, pad=1, pad_mode=1))
+    out.append(wgrad("onetap:tpb2", ONETAP, 1, 1, 24, 9, 11, 200, (4, 1), pad=(1, 0)))
+    for Cin, Cout in ((72, 24), (136, 200), (200, 136), (72, 8)):
+        out.append(wgrad("onetap:tpb1", ONETAP, 1, 1, Cin, 9, 11, Cout, 3, pad=1, pad_mode=int(Cin == 72)))
+    out.append(wgrad("onetap:tpb1", ONETAP, 1, 2, 8, 5, 7, 8, 1))
+    # Q = 4096 (64 K-steps), one tile, 64 elements: sixteen splits of four K-steps cost least; at Q = 448 (seven) none is allowed
+    out.append(wgrad("onetap:split", ONETAP, 16, 1, 8, 64, 64, 8, 1))
+    out.append(wgrad("onetap:split", ONETAP, 8, 2, 72, 33, 31, 24, 3, pad=1))
+    out.append(wgrad("onetap:stride2", ONETAP, 1, 1, 72, 9, 11, 24, 3, stride=2, pad=1))
+    out.append(wgrad("onetap:stride2", ONETAP, 1, 3, 64, 9, 11, 72, 4, stride=2, pad=1))
+    out.append(wgrad("onetap:stride2", ONETAP, 1, 2, 128, 17, 9, 128, 3, stride=2, pad=1))
+    for op in (0, 1):
+        out.append(wgrad("onetap:transposed", ONETAP, 1, 2, 72, 5, 7, 24, 3, transposed=1, stride=2, pad=1, output_padding=op))
+    out.append(wgrad("onetap:transposed", ONETAP, 1, 1, 64, 5, 7, 136, 4, transposed=1, stride=2, pad=1))
+    out.append(wgrad("onetap:reflect-deep", ONETAP, 1, 2, 24, 3, 4, 8, 5, pad=2, pad_mode=1))          # 25 taps
+    out.append(wgrad("onetap:gather-finish", ONETAP, 1, 1, 8, 4, 6, 8, 7, pad=3, pad_mode=1))          # 49 > WF_MAX_TAPS
+    out.append(wgrad("onetap:gather-finish", ONETAP, 1, 2, 72, 7, 5, 24, 5, pad=2))
+    return out
+
+
+def _nine():
+    return [
+        wgrad("nine:direct", NINE, 0, 1, 64, 2, 64, 64, 3, pad=1, pad_mode=1),          # H = 2: every row a border row
+        wgrad("nine:direct", NINE, 0, 1, 128, 3, 128, 192, 3, pad=1),                   # Q / 64 = 6 < 16
+        wgrad("nine:direct", NINE, 0, 2, 64, 3, 64, 128, 3, pad=1, pad_mode=1),
+        wgrad("nine:split", NINE, 3, 2, 128, 5, 192, 192, 3, pad=1, pad_mode=1),        # 30 K-steps: three splits of ten
+        wgrad("nine:split", NINE, 2, 1, 64, 9, 128, 64, 3, pad=1),                      # 18 K-steps: two of nine
+    ]
+
+
+def _lines():
+    return [
+        # 7x1: W = 70 is a whole segment and one of six pixels; 18 K-steps in two splits
+        wgrad("line:col7", COL, 2, 1, 64, 9, 70, 64, (7, 1), pad=(3, 0), pad_mode=1),
+        wgrad("line:line7", LINE, 1, 2, 64, 9, 5, 128, (7, 1), stride=(2, 1), pad=(3, 0), pad_mode=1),
+        wgrad("line:col4", COL, 1, 1, 128, 10, 7, 64, (4, 1), stride=(2, 1), pad=(1, 0)),
+        wgrad("line:line4", LINE, 2, 2, 64, 9, 5, 64, (4, 1), pad=(1, 0)),
+        wgrad("line:1x7", LINE, 1, 1, 64, 5, 5, 64, (1, 7), pad=(0, 3), pad_mode=1),    # pad < W <= 2 * pad
+        wgrad("line:1x7", LINE, 4, 2, 128, 9, 70, 64, (1, 7), pad=(0, 3)),           # 36 K-steps, two tiles: four of nine
+        wgrad("line:one-split", COL, 1, 1, 64, 3, 5, 64, (7, 1), pad=(3, 0)),           # three K-steps
+        wgrad("line:short-last-split", COL, 2, 1, 64, 19, 5, 64, (7, 1), pad=(3, 0)),   # 19 K-steps: ten and nine
+        wgrad("line:wide-finish", COL, 65, 1, 64, 130, 200, 64, (7, 1), pad=(3, 0), pad_mode=1),   # 520 K-steps of 8
+        wgrad("line:reflect-deep", COL, 1, 2, 64, 4, 5, 64, (7, 1), pad=(3, 0), pad_mode=1),
+        wgrad("line:reflect-deep", COL, 1, 1, 64, 6, 9, 128, (7, 1), pad=(3, 0), pad_mode=1),
+        # 3x3 / stride 2: tl = (Cout / 64) * (Cin / 64) of 1, 2 and 128 take the line kernel, 4 the one-tap kernel
+        wgrad("line:3x3s2", LINE, 1, 1, 64, 9, 11, 64, 3, stride=2, pad=1),
+        wgrad("line:3x3s2", LINE, 1, 2, 64, 10, 7, 128, 3, stride=2, pad=1),
+        wgrad("line:3x3s2", LINE, 1, 1, 512, 17, 9, 1024, 3, stride=2, pad=1),
+        wgrad("line:3x3s2-transposed", LINE, 1, 1, 1024, 9, 5, 512, 3, transposed=1, stride=2, pad=1, output_padding=1),
+        wgrad("line:3x3s2-transposed", LINE, 1, 2, 64, 5, 7, 64, 3, transposed=1, stride=2, pad=1),
+        wgrad("onetap:tl4", ONETAP, 1, 1, 128, 9, 11, 128, 3, stride=2, pad=1),
+    ]
+
+
+EDGE_WGRAD = _onetap() + _nine() + _lines()
