@@ -1,6 +1,6 @@
 """The edge records (test-only data, nothing here touches a device): hand-written tables in the format of
-tests/window_geometries.json at small and ragged shapes, for the replays of oracle/replay_ops.py (EDGE) and of
-oracle/replay_kernels.py: bn_case (EDGE_BN), replay_forward (EDGE_CONV) and replay_wgrad (EDGE_WGRAD).
+tests/window_geometries.json at small and ragged shapes, for the replays of oracle/replay_ops.py (EDGE, which ends
+with EDGE_FLOW) and of oracle/replay_kernels.py: bn_case (EDGE_BN), replay_forward (EDGE_CONV) and replay_wgrad (EDGE_WGRAD).
 
 The window's own geometries (512 x 1024, widths a multiple of 128, H far above 2 * pad) are the least likely to expose
 an indexing bug.  A record is ``entry``, then ``args`` with booleans standing for pointers, or the ``items`` / ``tensors``
@@ -10,6 +10,31 @@ records do, chosen on the CPU so that the fp64 reference alone has clamped pixel
 
 EDGE is chosen from the kernels' code: tile tails, pad < H <= 2 * pad (both mirrors of a reflection land near the far
 border), one-pixel planes, N > 1, every threshold between two code paths.
+
+EDGE_FLOW (the FlowNet2 operators) is chosen from correlation.hip, correlation_mfma.hip, resample2d.hip and
+channelnorm.hip.  A record names its ``form`` (FLOW_FORMS) by hand; for the forward cost volume corr_form restates the
+dispatch of ir2rgb_correlation_fwd and tests/test_edge_flow_cpu.py holds the two against each other.  Keys beside the
+arguments: ``offset`` {tensor: elements} (a misaligned base pointer), ``far`` [fx, fy] (added to every flow vector),
+``scale`` (of the channel norm's input), ``modes`` (the out modes of the half-precision cost volume).
+
+* corr_fwd_lds (fast parameters (20, 1, 20, 1, 2), C % 8 == 0), one thing varied from (1, 16, 5, 24): C = 8 / 16 / 24
+  (two / one / none of the three prologue stages is the no-op form), 32 (the ring exactly full) and 40 (its first
+  wrap); W = 8 (one live lane in 16), 128, 136 (a second x chunk of one lane); H = 1 (20 of 21 workgroups skip the
+  pipeline), 2, 3 and 41 (the middle row has all 21 tj rows valid); N = 2, 3; a grid that is a multiple of 8 (the XCD
+  renumbering) beside ones that are not.
+* corr_fwd_tile (C % 8 != 0): C = 1, 3, 5, 7 (lane quarters and channel halves that own no channel), 9, 17; W = 8 and
+  136, H = 1 and 41, N = 2.
+* corr_fwd_generic: the fast parameters at W % 8 != 0 and with in1 or out one element off alignment; k = 3 at stride1 =
+  2 with an odd extent (the ceil), pad = 0, pad < md, pad > md, md % stride2 != 0, stride2 = 1, N = 2, a one-pixel output.
+* corr_bwd_kernel: the fast parameters, k = 3, pad on both sides of md, stride2 = 1 and 3.
+* corr_mfma_kernel (both dtypes and both out modes per record): C = 128 / 256, W = 1 (parity 1 owns no pixel), 2 and
+  the widths around the 16-pixel blocks of a parity (31 .. 33, 63, 65, 127, 128), H = 1 (the lower-half workgroups only
+  zero-flush), 2, 3, 21 and 41 (all 21 rows valid, five wraps of the 4-row ring), N * H odd and even (the XCD
+  renumbering), channel-slice views of a, b and out, slope 1 / 0.1 / 0.
+* resample2d: one-row, one-column, one-pixel planes, N > 1, and ``far`` records whose pixels all land on one border
+  column / row (the atomics' long chain, both corners of an axis on one pixel, the truncation weights below zero).
+* channelnorm_bwd: the forward's shapes (each with an all-zero pixel) and an input of 1e-8, where the 1e-9 of the
+  denominator is a tenth of the norm.
 
 EDGE_BN is chosen from the dispatch in ir2rgb_bn_bwd and pointwise.hip:
 
@@ -214,7 +239,120 @@ ADAM_NS = (1, 2, 3, 5, 8191, 8192, 8193, 16387)
 ADAM = {"kind": "op", "entry": "ir2rgb_adam_step", "lr": 0.0002, "beta1": 0.5, "beta2": 0.999, "eps": 1e-08,
         "nblocks": 2 * sum(-(-n // 8192) for n in ADAM_NS), "tensors": [[n, al, 1] for n in ADAM_NS for al in (False, True)]}
 
-EDGE = _heads() + _warps() + _pools() + _xexpands() + _small() + _losses() + [ADAM]
+# ---------------------------------------------------------------------------------------------------------------------
+# FlowNet2 operators
+FAST = dict(pad_size=20, kernel_size=1, max_displacement=20, stride1=1, stride2=2)
+FLOW_FORMS = (
+    "lds:ng1", "lds:ng2", "lds:ng3", "lds:ng4", "lds:wrap", "lds:ng2+xcd", "tile:c<8", "tile", "generic:w%8",
+    "generic:unaligned", "generic:params",
+    "bwd:fast", "bwd:k3", "bwd:pad<md", "bwd:pad>md", "bwd:s2",
+    "mfma:kc4", "mfma:kc8", "mfma:w", "mfma:h", "mfma:n", "mfma:slice", "mfma:slope",
+    "resample", "resample:far", "channelnorm_bwd", "channelnorm_bwd:tiny",
+)
+
+
+def corr_form(N, C, H, W, pad, k, md, s1, s2, aligned=True):
+    """The kernel ir2rgb_correlation_fwd launches (correlation.hip:453-468) and, for corr_fwd_lds, how many 8-channel
+    stages its 4-stage ring sees and whether the grid is renumbered over the XCDs (a multiple of 8 workgroups)."""
+    fast = k == 1 and s1 == 1 and pad == md and s2 == 2 and md // s2 == 10 and md == 20 and W % 8 == 0 and aligned and C > 0
+    if not fast:
+        if (k, s1, pad, md, s2) == (1, 1, 20, 20, 2) and C > 0:
+            return "generic:w%8" if W % 8 else "generic:unaligned"
+        return "generic:params"
+    if C % 8 == 0 and N * C * H * W * 4 < 2 ** 31:
+        ng = C // 8
+        xcd = "+xcd" if (N * H * 21 * -(-W // 128)) % 8 == 0 else ""
+        return (f"lds:ng{ng}" if ng <= 4 else "lds:wrap") + xcd
+    return "tile:c<8" if C < 8 else "tile"
+
+
+def flow(entry, form, seed=None, offset=None, far=None, scale=None, modes=None, **kw):
+    assert form in FLOW_FORMS, form
+    rec = op(entry, seed, **kw)
+    rec["form"] = form
+    for key, v in (("offset", offset), ("far", far), ("scale", scale), ("modes", modes)):
+        if v is not None:
+            rec[key] = v
+    return rec
+
+
+def _corr_fwd():
+    e = "ir2rgb_correlation_fwd"
+    out = []
+    lds = [(1, 8, 5, 24, "lds:ng1"), (1, 16, 5, 24, "lds:ng2"), (1, 24, 5, 24, "lds:ng3"), (1, 32, 5, 24, "lds:ng4"),
+           (1, 40, 5, 24, "lds:wrap"),
+           (1, 16, 5, 8, "lds:ng2"), (1, 16, 5, 128, "lds:ng2"), (1, 16, 5, 136, "lds:ng2"),
+           (1, 16, 1, 24, "lds:ng2"), (1, 16, 2, 24, "lds:ng2"), (1, 16, 3, 24, "lds:ng2"), (1, 16, 41, 24, "lds:ng2"),
+           (2, 16, 5, 24, "lds:ng2"), (3, 16, 5, 24, "lds:ng2"),
+           (2, 16, 2, 136, "lds:ng2+xcd")]                  # 2 * 2 * 21 * 2 = 168 workgroups
+    tile = [(1, C, 5, 24, "tile:c<8" if C < 8 else "tile") for C in (1, 3, 5, 7, 9, 17)] + \
+           [(1, 9, 5, 8, "tile"), (1, 9, 5, 136, "tile"), (1, 9, 1, 24, "tile"), (1, 9, 41, 24, "tile"), (2, 9, 5, 24, "tile")]
+    for N, C, H, W, form in lds + tile + [(1, 4, 5, 7, "generic:w%8"), (1, 4, 5, 12, "generic:w%8")]:
+        out.append(flow(e, form, N=N, C=C, H=H, W=W, **FAST))
+    for name in ("in1", "out"):
+        out.append(flow(e, "generic:unaligned", offset={name: 1}, N=1, C=8, H=5, W=24, **FAST))
+    for N, C, H, W, pad, k, md, s1, s2 in (
+            (1, 3, 7, 9, 3, 3, 3, 2, 3),        # k = 3, stride1 = 2: ceil(5 / 2) x ceil(7 / 2) outputs
+            (1, 3, 9, 8, 0, 1, 2, 1, 1),        # pad = 0
+            (1, 3, 8, 9, 1, 1, 3, 1, 1),        # pad < md
+            (1, 3, 5, 6, 4, 1, 2, 1, 2),        # pad > md
+            (1, 3, 5, 6, 3, 1, 3, 1, 2),        # md % stride2 != 0
+            (1, 3, 5, 6, 2, 1, 2, 1, 1),        # stride2 = 1
+            (2, 3, 5, 6, 2, 1, 2, 1, 2),        # N = 2
+            (1, 2, 1, 1, 1, 1, 1, 1, 1)):       # one output pixel
+        out.append(flow(e, "generic:params", N=N, C=C, H=H, W=W, pad_size=pad, kernel_size=k, max_displacement=md,
+                        stride1=s1, stride2=s2))
+    return out
+
+
+def _corr_bwd():
+    e = "ir2rgb_correlation_bwd"
+    out = [flow(e, "bwd:fast", N=N, C=C, H=H, W=W, **FAST) for N, C, H, W in ((1, 2, 3, 5), (2, 3, 5, 8))]
+    for form, pad, k, md, s2 in (("bwd:k3", 2, 3, 2, 2), ("bwd:pad<md", 1, 1, 2, 2), ("bwd:pad>md", 3, 1, 2, 2),
+                                 ("bwd:s2", 3, 1, 3, 1), ("bwd:s2", 3, 1, 3, 3)):
+        out.append(flow(e, form, N=1, C=2, H=6, W=7, pad_size=pad, kernel_size=k, max_displacement=md, stride1=1, stride2=s2))
+    return out
+
+
+def _corr_mfma():
+    def rec(form, N=1, C=128, H=3, W=8, a=None, b=None, o=(512, 32), slope=0.1):
+        (lda, offa), (ldb, offb) = a or (C, 0), b or (C, 0)
+        return flow("ir2rgb_correlation_nhwc_half", form, modes=[0, 1], lda=lda, offa=offa, ldb=ldb, offb=offb, out_mode=1,
+                    ldo=o[0], offo=o[1], slope=slope, N=N, C=C, H=H, W=W, dtype=1)
+    out = [rec("mfma:kc4"), rec("mfma:kc8", C=256)]
+    out += [rec("mfma:w", H=2, W=W, C=(128, 256)[i % 2]) for i, W in enumerate((1, 2, 31, 32, 33, 63, 65, 127, 128))]
+    out += [rec("mfma:h", H=H) for H in (1, 2, 21, 41)]
+    out += [rec("mfma:n", N=2), rec("mfma:n", N=3), rec("mfma:n", N=2, H=1), rec("mfma:n", N=3, H=2, W=33)]
+    out += [rec("mfma:slice", a=(192, 64)), rec("mfma:slice", b=(200, 8)), rec("mfma:slice", C=256, b=(320, 64), W=33),
+            rec("mfma:slice", C=256, a=(320, 64), b=(328, 8), o=(448, 7), N=2, W=31),
+            rec("mfma:slice", o=(441, 0), W=33), rec("mfma:slice", o=(448, 7))]
+    out += [rec("mfma:slope", slope=1.0, W=33), rec("mfma:slope", slope=0.0, W=33)]
+    return out
+
+
+RESAMPLE_SHAPES = ((1, 3, 1, 5), (2, 2, 3, 7), (1, 1, 9, 1), (1, 1, 1, 1), (3, 3, 17, 33))
+FAR = ([100.0, 0.0], [0.0, -100.0])             # every pixel beyond the right border / above the top one
+
+
+def _resamples():
+    out = []
+    for e in ("ir2rgb_resample2d_fwd", "ir2rgb_resample2d_bwd"):
+        out += [flow(e, "resample", N=N, C=C, H=H, W=W, kernel_size=1) for N, C, H, W in RESAMPLE_SHAPES]
+        out += [flow(e, "resample:far", far=far, N=1, C=2, H=8, W=64, kernel_size=1) for far in FAR]
+    return out
+
+
+def _channelnorm_bwds():
+    e = "ir2rgb_channelnorm_bwd"
+    out = [flow(e, "channelnorm_bwd", N=N, C=C, H=H, W=W, norm_deg=2)
+           for N, C, H, W in ((1, 3, 1, 5), (2, 2, 3, 7), (1, 1, 9, 1), (3, 3, 17, 33), (2, 3, 2, 6), (1, 2, 1, 4))]
+    out.append(flow(e, "channelnorm_bwd:tiny", scale=1e-8, N=2, C=3, H=3, W=7, norm_deg=2))
+    return out
+
+
+EDGE_FLOW = _corr_fwd() + _corr_bwd() + _corr_mfma() + _resamples() + _channelnorm_bwds()
+
+EDGE = _heads() + _warps() + _pools() + _xexpands() + _small() + _losses() + [ADAM] + EDGE_FLOW
 
 # ---------------------------------------------------------------------------------------------------------------------
 # BatchNorm

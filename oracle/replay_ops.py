@@ -1,9 +1,9 @@
-"""fp64 replays of the non-convolution entry points (test-only): heads, warp blend, FlowNet2 glue, pooling, layout
-helpers, grouped losses, Adam.
+"""fp64 replays of the non-convolution entry points (test-only): heads, warp blend, FlowNet2 glue and operators (cost
+volume, pixel-space warp, channel norm, with their gradients), pooling, layout helpers, grouped losses, Adam.
 
 REPLAY maps an entry point to ``replay_*(dev, rec, g)``: ``rec`` a ``"kind": "op"`` record in the format of
-tests/window_geometries.json, ``g`` its generator (oracle.replay.gen).  References are oracle/window_ops_ref.py's, bounds
-oracle/bounds.py's, fixed before anything runs.  Entries that take a dtype run in bf16 and f16 from one fp64 reference
+tests/window_geometries.json, ``g`` its generator (oracle.replay.gen).  References are oracle/window_ops_ref.py's and
+oracle/flow_ops_ref.py's, bounds oracle/bounds.py's, fixed before anything runs.  Entries that take a dtype run in bf16 and f16 from one fp64 reference
 on operands exact in both formats.  Every element is compared, and what a launch must leave alone is checked too:
 channels outside a slice, dT channels >= Cout*KH (zero), loss slots no term names, the pool bytes around each Adam
 tensor.  Bias gradients and loss slots must repeat bit for bit.  Each replay returns {format: worst err/bound}.
@@ -14,6 +14,7 @@ import torch
 
 from oracle import bounds as B
 from oracle import conv_ref as R
+from oracle import flow_ops_ref as F
 from oracle import window_ops_ref as O
 from oracle.replay import DTYPES, assert_bound, bits, call, exact, np64, sentinel
 
@@ -32,11 +33,12 @@ ARGS = {    # argument names of the header's prototypes, without the stream
     "ir2rgb_xexpand_bwd": "dxe din N Cin H W Wout KW stride_w pad_w pad_mode dtype",
     "ir2rgb_warp_diff_norm_fwd": "img1 img2 flow warped diff norm N C H W",
     "ir2rgb_channelnorm_fwd": "inp out N C H W norm_deg",
-}
-
-# "op" entries of the window that REPLAY does not hold, and the test that covers them at the window's geometry
-COVERED_ELSEWHERE = {
-    "ir2rgb_correlation_nhwc_half": "tests/test_ops_gpu.py::test_correlation_nhwc_half_full_size",
+    "ir2rgb_correlation_fwd": "in1 in2 out N C H W pad_size kernel_size max_displacement stride1 stride2",
+    "ir2rgb_correlation_bwd": "in1 in2 gout gin1 gin2 N C H W pad_size kernel_size max_displacement stride1 stride2",
+    "ir2rgb_correlation_nhwc_half": "a lda offa b ldb offb out out_mode ldo offo slope N C H W dtype",
+    "ir2rgb_resample2d_fwd": "img flow out N C H W kernel_size",
+    "ir2rgb_resample2d_bwd": "img flow gout gimg gflow N C H W kernel_size",
+    "ir2rgb_channelnorm_bwd": "inp out gout gin N C H W norm_deg",
 }
 
 
@@ -361,6 +363,192 @@ def replay_channelnorm(dev, rec, g):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# FlowNet2 operators (references: oracle/flow_ops_ref.py).  Record keys beside the arguments: ``offset`` {tensor name:
+# elements} moves a tensor's base pointer off its allocation's alignment; ``far`` [fx, fy] is added to every flow vector
+# (all pixels sample beyond one border); ``scale`` multiplies the channel norm's input; ``modes`` lists the out modes of
+# the half-precision cost volume to run (default: the recorded one).
+def _at(t, rec, name, dev):
+    """``t`` on the device, its first element ``rec["offset"][name]`` elements into a fresh allocation."""
+    off = rec.get("offset", {}).get(name, 0)
+    buf = torch.empty(t.numel() + off, dtype=t.dtype, device=dev)
+    v = buf[off:].view(t.shape)
+    v.copy_(t)
+    return v
+
+
+def _twice(name, launch, outs):
+    """launch() -> tuple of output tensors, run twice into re-filled buffers: the named outputs must repeat bit for bit."""
+    first = launch()
+    torch.cuda.synchronize()
+    again = launch()
+    torch.cuda.synchronize()
+    for k, a, b in zip(outs, first, again):
+        if k is not None:
+            assert torch.equal(bits(a.contiguous()), bits(b.contiguous())), f"{name}: {k} differs between two runs"
+    return first
+
+
+def corr_geometry(a):
+    return tuple(a[k] for k in "pad_size kernel_size max_displacement stride1 stride2".split())
+
+
+def replay_corr_fwd(dev, rec, g):
+    from oracle.edge_records import corr_form
+    a = named_args(rec)
+    N, C, H, W = a["N"], a["C"], a["H"], a["W"]
+    pad, k, md, s1, s2 = corr_geometry(a)
+    f1, f2 = torch.randn(N, C, H, W, generator=g), torch.randn(N, C, H, W, generator=g)
+    ref, S = F.correlation(np64(f1), np64(f2), pad, k, md, s1, s2)
+    d1, d2 = _at(f1, rec, "in1", dev), f2.to(dev)
+
+    def launch():
+        out = _at(torch.full(ref.shape, float("nan")), rec, "out", dev)
+        call(rec["entry"], d1, d2, out, N, C, H, W, pad, k, md, s1, s2)
+        return (out,)
+    out, = _twice("correlation_fwd", launch, ("out",))
+    form = corr_form(N, C, H, W, pad, k, md, s1, s2, not rec.get("offset")).split(":")[0]
+    bnd = B.bound_sum(ref, S, "f32", k * k * C + 2)
+    return {form: assert_bound(f"correlation_fwd ({form})", *B.check_bound(np64(out), ref, bnd), ref.shape)}
+
+
+def replay_corr_bwd(dev, rec, g):
+    a = named_args(rec)
+    N, C, H, W = a["N"], a["C"], a["H"], a["W"]
+    pad, k, md, s1, s2 = corr_geometry(a)
+    oc, oh, ow = F.correlation_out_shape(H, W, pad, k, md, s1, s2)
+    f1, f2 = torch.randn(N, C, H, W, generator=g), torch.randn(N, C, H, W, generator=g)
+    gout = torch.randn(N, oc, oh, ow, generator=g)
+    r1, r2, S1, S2, L1, L2 = F.correlation_bwd(np64(f1), np64(f2), np64(gout), pad, k, md, s2)
+    d1, d2, dg = f1.to(dev), f2.to(dev), gout.to(dev)
+
+    def launch():
+        g1, g2 = sentinel(f1.shape, torch.float32, dev), sentinel(f1.shape, torch.float32, dev)
+        call(rec["entry"], d1, d2, dg, g1, g2, N, C, H, W, pad, k, md, s1, s2)
+        return g1, g2
+    g1, g2 = _twice("correlation_bwd", launch, ("gin1", "gin2"))
+    ra = assert_bound("gin1", *B.check_bound(np64(g1), r1, B.bound_sum(r1, S1, "f32", L1 + 2)), r1.shape)
+    rb = assert_bound("gin2", *B.check_bound(np64(g2), r2, B.bound_sum(r2, S2, "f32", L2 + 2)), r2.shape)
+    return {"f32": max(ra, rb)}
+
+
+def leaky(x, slope):
+    return np.where(x > 0, x, x * slope)
+
+
+def replay_corr_mfma(dev, rec, g):
+    a = named_args(rec)
+    N, C, H, W = a["N"], a["C"], a["H"], a["W"]
+    lda, offa, ldb, offb, ldo, offo, slope = (a[k] for k in "lda offa ldb offb ldo offo slope".split())
+    f1, f2 = R.draw((N, C, H, W), g), R.draw((N, C, H, W), g)
+    ref, S = F.correlation(np64(f1), np64(f2), 20, 1, 20, 1, 2)
+    out = {}
+    for fmt, dtype, dt in DTYPES:
+        bufs = []
+        for f, ld, off in ((f1, lda, offa), (f2, ldb, offb)):       # NaN in every channel outside the slice
+            t = torch.full((N, H, W, ld), float("nan"), dtype=dtype)
+            t[..., off:off + C] = f.permute(0, 2, 3, 1).to(dtype)
+            bufs.append(t.to(dev))
+        before = [t.clone() for t in bufs]
+        for mode in rec.get("modes", [a["out_mode"]]):
+            def launch():
+                o = sentinel((N, 441, H, W), torch.float32, dev) if mode == 0 else \
+                    sentinel((N, H, W, ldo), dtype, dev)
+                call(rec["entry"], bufs[0], lda, offa, bufs[1], ldb, offb, o, mode, ldo, offo, slope, N, C, H, W, dt)
+                return (o,)
+            o, = _twice(f"{fmt} out_mode {mode}", launch, ("out",))
+            if mode == 0:
+                got, want, ofmt = np64(o), ref, "f32"
+            else:
+                keep = torch.ones(ldo, dtype=torch.bool)
+                keep[offo:offo + 441] = False
+                assert bool(torch.isnan(o[..., keep]).all()), f"{fmt}: the cost volume wrote outside its channels"
+                got, want, ofmt = np64(o[..., offo:offo + 441].permute(0, 3, 1, 2)), leaky(ref, slope), fmt
+            out[f"{fmt}/out{mode}"] = assert_bound(f"{fmt} out_mode {mode}", *B.check_bound(got, want, B.bound(want, S, ofmt, C + 2)),
+                                                   want.shape)
+        for t, b0 in zip(bufs, before):
+            assert torch.equal(bits(t), bits(b0)), f"{fmt}: an input buffer was written"
+    return out
+
+
+def _resample_inputs(rec, g):
+    a = named_args(rec)
+    N, C, H, W = a["N"], a["C"], a["H"], a["W"]
+    img = torch.randn(N, C, H, W, generator=g)
+    flow = _pixel_flow(N, H, W, g)
+    if "far" in rec:
+        flow = (flow + torch.tensor(rec["far"], dtype=torch.float32).view(1, 2, 1, 1)).contiguous()
+    return a, img, flow
+
+
+def replay_resample_fwd(dev, rec, g):
+    a, img, flow = _resample_inputs(rec, g)
+    N, C, H, W = img.shape
+    v, dvx, dvy, S = F.resample2d(np64(img), np64(flow))
+    ev = B.C_AR * B.U32 * S + dvx * B.coord_delta(W) + dvy * B.coord_delta(H)
+    di, df = img.to(dev), flow.to(dev)
+
+    def launch():
+        out = sentinel(img.shape, torch.float32, dev)
+        call(rec["entry"], di, df, out, N, C, H, W, a["kernel_size"])
+        return (out,)
+    out, = _twice("resample2d_fwd", launch, ("out",))
+    return {"f32": assert_bound("warped", *B.check_bound(np64(out), v, ev + B.ETA["f32"]), v.shape)}
+
+
+def resample_bwd_bounds(r, C, H, W):
+    """(gimg bound, gflow bound) of a flow_ops_ref.resample2d_bwd result: L contributions of up to three roundings each
+    (the two weight products, times gout) and their additions in any order; 8 products per channel (4 per component, two
+    roundings each) in a chain of 4 C, and the derivative in the other coordinate times its fp32 error."""
+    bi = B.bound_sum(r["gimg"], r["S_gimg"], "f32", r["L"][:, None] + 3)
+    bf = B.gamma(8 * C + 2) * r["S_gflow"] + np.stack([r["dgx_dy"] * B.coord_delta(H), r["dgy_dx"] * B.coord_delta(W)], 1) \
+        + B.ETA["f32"]
+    return bi, bf
+
+
+def replay_resample_bwd(dev, rec, g):
+    a, img, flow = _resample_inputs(rec, g)
+    N, C, H, W = img.shape
+    gout = torch.randn(N, C, H, W, generator=g)
+    r = F.resample2d_bwd(np64(img), np64(flow), np64(gout))
+    bi, bf = resample_bwd_bounds(r, C, H, W)
+    di, df, dg = img.to(dev), flow.to(dev), gout.to(dev)
+
+    def launch():
+        gimg, gflow = sentinel(img.shape, torch.float32, dev), sentinel(flow.shape, torch.float32, dev)
+        call(rec["entry"], di, df, dg, gimg, gflow, N, C, H, W, a["kernel_size"])
+        return gimg, gflow
+    gimg, gflow = _twice("resample2d_bwd", launch, (None, "gflow"))      # (gimg: float atomics, any order)
+    return {"gimg": assert_bound("gimg", *B.check_bound(np64(gimg), r["gimg"], bi), bi.shape),
+            "gflow": assert_bound("gflow", *B.check_bound(np64(gflow), r["gflow"], bf), bf.shape)}
+
+
+def channelnorm_bwd_inputs(rec, g):
+    """x (pixel (0, 0, 0) all zero, times the record's ``scale``), out = the fp32-rounded fp64 norm, gout."""
+    a = named_args(rec)
+    N, C, H, W = a["N"], a["C"], a["H"], a["W"]
+    x = torch.randn(N, C, H, W, generator=g) * rec.get("scale", 1.0)
+    x[0, :, 0, 0] = 0
+    out = torch.from_numpy(F.channelnorm(np64(x))).float()
+    return a, x, out, torch.randn(N, 1, H, W, generator=g)
+
+
+def replay_channelnorm_bwd(dev, rec, g):
+    a, x, out, gout = channelnorm_bwd_inputs(rec, g)
+    N, C, H, W = x.shape
+    ref, _ = F.channelnorm_bwd(np64(x), np64(out), np64(gout))
+    dx, do, dg = x.to(dev), out.to(dev), gout.to(dev)
+
+    def launch():
+        gin = sentinel(x.shape, torch.float32, dev)
+        call(rec["entry"], dx, do, dg, gin, N, C, H, W, a["norm_deg"])
+        return (gin,)
+    gin, = _twice("channelnorm_bwd", launch, ("gin",))
+    assert not bool(gin[0, :, 0, 0].ne(0).any()), "the gradient of an all-zero pixel is not zero"
+    bnd = 3 * B.U32 * np.abs(ref) + B.ETA["f32"]        # one fp32 product, a double division, one cast
+    return {"f32": assert_bound("channelnorm_bwd", *B.check_bound(np64(gin), ref, bnd), ref.shape)}
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # grouped losses
 def _loss_tensors(rec, g, dtype, dev):
     """Per item: (a, b, mask) on the device and their fp64 copies.  Half operands are drawn exact in both formats."""
@@ -549,4 +737,10 @@ REPLAY = {
     "ir2rgb_loss_multi_fwd": replay_loss_fwd,
     "ir2rgb_loss_multi_bwd": replay_loss_bwd,
     "ir2rgb_adam_step": replay_adam,
+    "ir2rgb_correlation_fwd": replay_corr_fwd,
+    "ir2rgb_correlation_bwd": replay_corr_bwd,
+    "ir2rgb_correlation_nhwc_half": replay_corr_mfma,
+    "ir2rgb_resample2d_fwd": replay_resample_fwd,
+    "ir2rgb_resample2d_bwd": replay_resample_bwd,
+    "ir2rgb_channelnorm_bwd": replay_channelnorm_bwd,
 }

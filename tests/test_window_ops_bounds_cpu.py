@@ -7,8 +7,6 @@ flow gradient, count_include_pad pooling, a loss mean over a rounded n, Adam wit
 un-updated n % 4 tail, swapped up-sampler taps -- and the bounds of oracle/bounds.py must reject each one, while the
 unfaulted reference rounded to the output format passes.
 """
-import os
-
 import numpy as np
 import pytest
 import torch
@@ -19,7 +17,6 @@ from oracle import window as WG
 from oracle import window_ops_ref as O
 from oracle.replay import passes, rnd
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 OPS = WG.op_entries()
 
 
@@ -49,19 +46,14 @@ def test_every_entry_point_is_classified():
 
 
 def test_every_op_record_is_replayed_or_covered():
+    """Every op entry of the window has a replay (none is covered elsewhere any more)."""
     entries = {r["entry"] for r in OPS}
     assert entries, "the manifest holds no op records"
-    missing = sorted(e for e in entries if e not in G.REPLAY and e not in G.COVERED_ELSEWHERE)
-    assert not missing, "op entries neither in oracle/replay_ops.py's REPLAY nor in COVERED_ELSEWHERE: " + \
-        ", ".join(missing)
-    assert not set(G.REPLAY) & set(G.COVERED_ELSEWHERE)
-    for e in entries & set(G.REPLAY):
+    missing = sorted(e for e in entries if e not in G.REPLAY)
+    assert not missing, "op entries not in oracle/replay_ops.py's REPLAY: " + ", ".join(missing)
+    for e in entries:
         if "args" in next(r for r in OPS if r["entry"] == e):
             assert e in G.ARGS, e
-    for test in G.COVERED_ELSEWHERE.values():
-        path, name = test.split("::")
-        with open(os.path.join(os.path.dirname(HERE), path)) as f:
-            assert f"def {name}(" in f.read(), test
 
 
 def test_argument_names_match_the_prototypes():

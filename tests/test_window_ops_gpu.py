@@ -6,7 +6,7 @@ before anything runs.  Entries that take a dtype run in bf16 and f16 from one fp
 formats.  Every element is compared, and what a launch must leave alone is checked too: channels outside a slice, dT
 channels >= Cout*KH (zero), loss slots no term names, the pool bytes around each Adam tensor.  Bias gradients and loss
 slots must repeat bit for bit.
-Run with -s to see the worst err/bound table.  Entries replayed elsewhere are listed in replay_ops.COVERED_ELSEWHERE.
+Run with -s to see the worst err/bound table.
 """
 import pytest
 
