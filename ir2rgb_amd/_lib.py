@@ -203,6 +203,23 @@ def on_device(tensor):
     return torch.cuda.device_of(tensor)
 
 
+def launch(name, anchor, *args):
+    """Entry ``name`` (``ir2rgb_...``, stream last) with ``args`` on torch's current stream of ``anchor``'s device, made
+    current for the call; a non-zero return raises (``check``) under the entry's own name."""
+    with on_device(anchor):
+        rc = getattr(lib(), name)(*args, current_stream(anchor))
+    if rc:
+        check(rc, name[7:])
+
+
+def query(name, *args):
+    """The count a host-only entry (``ir2rgb_*_elems / _rows / _blocks / _bytes``) answers; a negative one raises."""
+    n = getattr(lib(), name)(*args)
+    if n < 0:
+        check(int(n), name[7:])
+    return n
+
+
 def require_device(*tensors, dtype=None):
     """Turn the reference's silent assumptions (CUDA device, dtype, contiguity) into errors."""
     import torch

@@ -22,7 +22,6 @@ from torch.autograd import Function
 from . import _lib
 from . import conv as C
 from . import layers as L
-from . import streamcheck as SC
 from . import stageplan
 
 _DT = C._TORCH2DT
@@ -43,10 +42,7 @@ def bn_bwd(gz, y, scale, shift, mean, invstd, act, out=None, params=None):
     group of the same layer: this group's are added to them in the kernel (act | 32)."""
     n, ch, h, w = y.shape
     npix = n * h * w
-    lib = _lib.lib()
-    nblk = lib.ir2rgb_bn_bwd_blocks(npix, ch)
-    if nblk < 0:
-        _lib.check(nblk, "bn_bwd_blocks")
+    nblk = _lib.query("ir2rgb_bn_bwd_blocks", npix, ch)
     dev = y.device
     if params is not None:
         dgamma, dbeta = params
@@ -59,10 +55,7 @@ def bn_bwd(gz, y, scale, shift, mean, invstd, act, out=None, params=None):
         dgamma, dbeta = buf[:ch], buf[ch:2 * ch]
         ppartial = buf.data_ptr() + 8 * ch
     gy = out if out is not None else torch.empty_like(y, memory_format=torch.channels_last)
-    with _lib.on_device(y):
-        rc = lib.ir2rgb_bn_bwd(gz, y, scale, shift, mean, invstd, gy, dgamma, dbeta,
-                               ppartial, npix, ch, act, _DT[y.dtype], _lib.current_stream(y))
-    _lib.check(rc, "bn_bwd")
+    _lib.launch("ir2rgb_bn_bwd", y, gz, y, scale, shift, mean, invstd, gy, dgamma, dbeta, ppartial, npix, ch, act, _DT[y.dtype])
     return gy, dgamma, dbeta
 
 
@@ -74,10 +67,7 @@ def thin_grad_expand(gz, dtype):
     g64 = C.empty_nhwc(n, 64, h, w, dtype, gz.device)
     g8 = C.empty_nhwc(n, 8, h, w, dtype, gz.device)
     dbias = torch.empty(cout, dtype=torch.float32, device=gz.device)
-    with _lib.on_device(gz):
-        rc = _lib.lib().ir2rgb_thin_grad_expand(gz, g64, g8, dbias, n, cout, h, w, _DT[dtype],
-                                                _lib.current_stream(gz))
-    _lib.check(rc, "thin_grad_expand")
+    _lib.launch("ir2rgb_thin_grad_expand", gz, gz, g64, g8, dbias, n, cout, h, w, _DT[dtype])
     return g64, g8, dbias
 
 
@@ -86,20 +76,14 @@ def fold_reflect(dxpad, pad_h, pad_w=None):
     n, ch, hp, wp = dxpad.shape
     h, w = hp - 2 * pad_h, wp - 2 * pad_w
     dx = C.empty_nhwc(n, ch, h, w, dxpad.dtype, dxpad.device)
-    with _lib.on_device(dxpad):
-        rc = _lib.lib().ir2rgb_fold_reflect(dxpad, dx, n, h, w, ch, pad_h, pad_w, _DT[dxpad.dtype],
-                                            _lib.current_stream(dxpad))
-    _lib.check(rc, "fold_reflect")
+    _lib.launch("ir2rgb_fold_reflect", dxpad, dxpad, dx, n, h, w, ch, pad_h, pad_w, _DT[dxpad.dtype])
     return dx
 
 
 def xexpand_bwd(dxe, cin, w, kw, stride_w, pad_w, pad_mode):
     n, _, h, wout = dxe.shape
     din = torch.empty((n, cin, h, w), dtype=torch.float32, device=dxe.device)
-    with _lib.on_device(dxe):
-        rc = _lib.lib().ir2rgb_xexpand_bwd(dxe, din, n, cin, h, w, wout, kw, stride_w, pad_w, pad_mode,
-                                           _DT[dxe.dtype], _lib.current_stream(dxe))
-    _lib.check(rc, "xexpand_bwd")
+    _lib.launch("ir2rgb_xexpand_bwd", dxe, dxe, din, n, cin, h, w, wout, kw, stride_w, pad_w, pad_mode, _DT[dxe.dtype])
     return din
 
 
@@ -125,19 +109,11 @@ def padded_width(c):
     return c if c % 64 == 0 and (c & (c - 1)) == 0 else max(64, 1 << (c - 1).bit_length())
 
 
-def _pad_dim(t, dim, to, value=0.0):
-    if t.shape[dim] == to:
-        return t
-    shape = list(t.shape)
-    shape[dim] = to - t.shape[dim]
-    return torch.cat([t, t.new_full(shape, value)], dim)
-
-
 def _pad_weight_fn(cout_to, cin_to, transposed):
     """Conv2d weight [Cout,Cin,kh,kw] (ConvTranspose2d: [Cin,Cout,kh,kw]) -> zero-padded to the widths the kernels run at."""
     def f(w):
         a, b = (cin_to, cout_to) if transposed else (cout_to, cin_to)
-        return _pad_dim(_pad_dim(w, 0, a), 1, b)
+        return L.pad_dim(L.pad_dim(w, 0, a), 1, b)
     return f
 
 
@@ -168,11 +144,11 @@ class _PaddedBN:
 
     def __init__(self, bn, cp):
         self.bn, self.num_features = bn, cp
-        self.weight = _pad_dim(bn.weight.detach(), 0, cp, 1.0)
-        self.bias = _pad_dim(bn.bias.detach(), 0, cp, 0.0)
+        self.weight = L.pad_dim(bn.weight.detach(), 0, cp, 1.0)
+        self.bias = L.pad_dim(bn.bias.detach(), 0, cp, 0.0)
         self.track_running_stats, self.momentum, self.eps = bn.track_running_stats, bn.momentum, bn.eps
-        self.running_mean = None if bn.running_mean is None else _pad_dim(bn.running_mean, 0, cp, 0.0)
-        self.running_var = None if bn.running_var is None else _pad_dim(bn.running_var, 0, cp, 1.0)
+        self.running_mean = None if bn.running_mean is None else L.pad_dim(bn.running_mean, 0, cp, 0.0)
+        self.running_var = None if bn.running_var is None else L.pad_dim(bn.running_var, 0, cp, 1.0)
         self.num_batches_tracked = bn.num_batches_tracked
 
     def commit(self, training):
@@ -384,11 +360,189 @@ def _fused_act(spec):
     return 1 if spec["fused_leaky"] else (3 if spec.get("fused_relu") else 0)
 
 
+def _group(t, g, G):
+    """Sample group ``g`` of ``G`` in a tensor batched along its first dimension (activations: N / G samples; a
+    convolution's per-sample statistics: rows / G partial rows)."""
+    n = t.shape[0] // G
+    return t[g * n:(g + 1) * n]
+
+
+def _stage_geometry(spec, conv, x, bias, per_sample_stats):
+    """What the stage's convolution launch reads: -> (xin, descriptor, packed weight, bias, weight_fn, sub-spec).  The only
+    place that knows how a first layer (x-im2col of the fp32 image + a (kh x 1) convolution, whose spec is the sub-spec)
+    and a layer at padded widths differ from the plain one.  ``weight_fn`` maps conv.weight to the weight the launch
+    uses (None: the parameter itself); the bias comes back zero-padded to the width the layer runs at."""
+    dt = spec["dtype"]
+    cout, cin = conv.out_channels, conv.in_channels
+    cout_p = cout if spec.get("out_f32", False) else padded_width(cout)
+    cin_p = cin if spec["first"] else padded_width(cin)
+    padded = cout_p != cout or cin_p != cin
+    wfn = _pad_weight_fn(cout_p, cin_p, spec["transposed"]) if padded else None
+    if spec["first"]:
+        kh, kw = conv.kernel_size
+        sub = dict(spec, k=(kh, 1), stride=(spec["stride"][0], 1), pad=(spec["pad"][0], 0))
+        xin = L.xexpand(x, kw, spec["stride"][1], spec["pad"][1], spec["pad_mode"], dt)
+        desc = C.make_desc(tuple(xin.shape), cout_p, sub["k"], sub["stride"], sub["pad"], spec["pad_mode"], dt,
+                           act=_fused_act(spec))
+        wfn = _compose(wfn, L._xexpanded_weight(kw))
+        wp = L.packed_weight(conv, desc, wfn, tag="xexp")
+    else:
+        if x.shape[1] != cin_p:
+            raise ValueError(f"conv stage: input has {x.shape[1]} channels, the layer runs at {cin_p} (autograd.pad_channels)")
+        xin, sub = x, None
+        desc = C.make_desc(tuple(x.shape), cout_p, spec["k"], spec["stride"], spec["pad"], spec["pad_mode"],
+                           dt, spec["transposed"], spec.get("output_padding", 0), act=_fused_act(spec),
+                           out_f32=spec.get("out_f32", False), stats_per_sample=per_sample_stats)
+        wp = L.packed_weight(conv, desc, wfn, tag="wpad" if padded else "w")
+    if padded and bias is not None:
+        bias = L.pad_dim(bias.detach(), 0, cout_p)
+    return xin, desc, wp, bias, wfn, sub
+
+
+def _batchnorm(spec, bn, y, stats, bias, res1, res2, frozen):
+    """BatchNorm + activation (+ residuals) of the convolution output ``y``: -> (z, scale, shift, mean, invstd), the four
+    vectors [C], or [G][C] for a batch of G sample groups."""
+    G = spec.get("groups", 1)
+    n, ch, h, w = y.shape
+    count = n * h * w // G
+    fused = FUSED_BN and not frozen and spec["training"] and ch % 64 == 0
+    if G == 1:
+        if fused and stats.shape[0] <= L.FUSED_BN_MAX_ROWS:
+            # few partial rows (the residual blocks): statistics and apply in one launch
+            return L.bn_finalize_apply(stats, count, bn, y, spec["act"], res1, res2, bias)
+        scale, shift, mean, invstd = L.bn_finalize(stats, count, bn, spec["training"], bias)
+        return L.bn_apply(y, scale, shift, spec["act"], res1, res2), scale, shift, mean, invstd
+    # G independent forwards batched along N (the discriminators see real / generated / raw frames with the same
+    # weights): ONE convolution, then BatchNorm per sample group exactly as G separate calls would run it --
+    # statistics over the group's samples, running statistics advanced group by group
+    if n % G or res1 is not None or res2 is not None:
+        raise ValueError("conv stage: sample groups need N % groups == 0 and no residual inputs")
+    rg = 0 if frozen else stats.shape[0] // G
+    z = torch.empty_like(y, memory_format=torch.channels_last)
+    vec = torch.empty((4, G, ch), dtype=torch.float32, device=y.device)
+    reps = L._STAT_UPDATES        # layers.repeated_forward: an int, or one count per group
+    try:
+        for g in (spec.get("group_order") or range(G)):      # (the order the running statistics advance in)
+            L._STAT_UPDATES = reps[g] if isinstance(reps, tuple) else reps
+            yg, zg = _group(y, g, G), _group(z, g, G)
+            sg = None if frozen else _group(stats, g, G)
+            outs = (vec[0][g], vec[1][g], vec[2][g], vec[3][g])
+            if fused and rg <= L.FUSED_BN_MAX_ROWS:
+                L.bn_finalize_apply(sg, count, bn, yg, spec["act"], None, None, bias, out=zg, outs=outs)
+            else:
+                L.bn_finalize(sg, count, bn, spec["training"], bias, outs=outs)
+                L.bn_apply(yg, outs[0], outs[1], spec["act"], out=zg)
+    finally:
+        L._STAT_UPDATES = reps
+    return z, vec[0], vec[1], vec[2], vec[3]
+
+
+def _bn_grad(gz, y, scale, shift, mean, invstd, act):
+    """BatchNorm + activation backward, per sample group where the vectors are [G][C] (into one gradient tensor for the
+    batch, the parameter gradients summed over the groups): -> (gy, dgamma, dbeta)."""
+    if scale.dim() == 1:
+        return bn_bwd(gz, y, scale, shift, mean, invstd, act)
+    G = scale.shape[0]
+    gy = torch.empty_like(y, memory_format=torch.channels_last)
+    params = None
+    for g in range(G):
+        _, dgamma, dbeta = bn_bwd(_group(gz, g, G), _group(y, g, G), scale[g], shift[g], mean[g], invstd[g], act,
+                                  out=_group(gy, g, G), params=params)
+        params = (dgamma, dbeta)
+    return gy, dgamma, dbeta
+
+
+def _output_grad(ctx, gz, y, scale, shift, mean, invstd):
+    """Back through activation / BatchNorm / the fp32 cast to the convolution output: -> (gz as the residual branches get it,
+    gy for the data gradient, gy for the weight gradient, dbias, dgamma, dbeta)."""
+    spec = ctx.spec
+    hdt = spec["dtype"]
+    if spec.get("out_f32", False):
+        # thin fp32 output (PatchGAN logits): the gradient zero-padded to 64 channels for the MFMA adjoint and to 8 for
+        # the weight-gradient kernel, and its per-channel sum, in one launch
+        g64, g8, dbias = thin_grad_expand(gz, hdt)
+        return gz, g64, g8, dbias, None, None
+    gz = _as_half_nhwc(gz, hdt)
+    if ctx.has_bn:
+        gy, dgamma, dbeta = _bn_grad(gz, y, scale, shift, mean, invstd, spec["act"] | (16 if ctx.frozen else 0))
+        # training mode: BatchNorm removes the per-channel mean, the bias gradient is exactly 0 (None = zeros);
+        # evaluation mode: the layer is affine in the bias, d/dbias = scale * sum g' (the same running statistics for
+        # every sample group)
+        dbias = dbeta * (scale if scale.dim() == 1 else scale[0]) if ctx.frozen else None
+        return gz, gy, gy, dbias, dgamma, dbeta
+    # LeakyReLU / ReLU keep the sign (ReLU: y > 0 <=> pre-activation > 0): mask from the stored output
+    act = 2 if spec["fused_leaky"] else (1 if spec.get("fused_relu") else 0)
+    gy, _, dbias = bn_bwd(gz, y, None, None, None, None, act)
+    return gz, gy, gy, dbias, None, None
+
+
+def _image_grad(ctx, gy, xin):
+    """Input gradient of a first layer (NCHW fp32): the adjoint of the (kh x 1) convolution over the expanded image, then
+    of the x-im2col."""
+    spec, conv = ctx.spec, ctx.conv
+    if spec["pad_mode"] != C.PAD_ZERO:
+        raise NotImplementedError("input gradient of a reflect-padded first layer is never needed")
+    kw = conv.kernel_size[1]
+    dxe = conv_dgrad(gy, conv, ctx.sub, tuple(xin.shape), ctx.wfn, tag="dgrad_xexp")
+    return xexpand_bwd(dxe, ctx.x_shape[1], ctx.x_shape[3], kw, spec["stride"][1], spec["pad"][1], spec["pad_mode"])
+
+
+def _input_grad(ctx, gy, xin, n_full):
+    """Gradient w.r.t. the stage's input.  ``n_full``: the forward's batch size when ``gy`` covers its leading samples only
+    -- the gradient keeps the full batch's shape and the rest of it stays unwritten."""
+    spec, conv = ctx.spec, ctx.conv
+    if spec["first"]:
+        dx = _image_grad(ctx, gy, xin)
+        if n_full is not None:
+            full = dx.new_empty((n_full,) + tuple(dx.shape[1:]))
+            full[:dx.shape[0]].copy_(dx)
+            dx = full
+        return dx
+    wfn = ctx.wfn
+    if gy.shape[1] != ctx.width:       # a gradient widened for the MFMA kernel (thin outputs): zero weight rows to match
+        wfn = _compose(wfn, lambda w: L.pad_dim(w, 0, gy.shape[1]))
+    if n_full is None:
+        return conv_dgrad(gy, conv, spec, ctx.x_shape, wfn)
+    dx = C.empty_nhwc(n_full, ctx.x_shape[1], ctx.x_shape[2], ctx.x_shape[3], gy.dtype, gy.device)
+    conv_dgrad(gy, conv, spec, (gy.shape[0],) + tuple(ctx.x_shape[1:]), wfn, out=dx[:gy.shape[0]])
+    return dx
+
+
+def _weight_grad(ctx, xin, gy):
+    """Gradient of conv.weight, in the parameter's own shape, from the launch's input and the gradient w.r.t. its output."""
+    spec, conv = ctx.spec, ctx.conv
+    cout, cin = conv.out_channels, conv.in_channels
+    if spec["first"]:
+        kh, kw = conv.kernel_size
+
+        def wgrad():
+            gwe = conv_wgrad(xin, gy, None, ctx.sub)                            # [co_p][64][kh][1]
+            gwe = gwe[:cout, :cin * kw, :, 0].reshape(cout, cin, kw, kh)        # [co][ci][kx][ky]
+            return gwe.permute(0, 1, 3, 2).contiguous()
+    elif gy.shape[1] != cout or xin.shape[1] != cin:
+        # the launch ran wider than the parameter (padded widths; a thin gradient zero-padded to 8 channels): the
+        # parameter's gradient is the real corner
+        def wgrad():
+            g = conv_wgrad(xin, gy, None, spec)
+            return (g[:cin, :cout] if spec["transposed"] else g[:cout, :cin]).contiguous()
+    else:
+        wsh = tuple(conv.weight.shape)
+        out, acc, dw = wgrad_destination(conv.weight, wsh)
+        if acc:
+            conv_wgrad(xin, gy, wsh, spec, out=out, accumulate=True)
+            return dw
+
+        def wgrad():            # (conv2d_wgrad hands back the fresh tensor, or its own new view of the sink)
+            return conv_wgrad(xin, gy, wsh, spec, out=out)
+    return wgrad_overlapped(conv, wgrad, xin, gy)
+
+
 class ConvStageFn(Function):
     """z = act(bn(conv(x))) + res1 + res2 on channels_last half tensors (x may be an NCHW fp32 image
     for 'first' stages).  Arguments after ``x``: weight, bias, gamma, beta (fp32 parameters), res1,
     res2, then the non-tensor ``spec`` dict and the conv / bn modules (packed-weight cache, BN
-    buffers)."""
+    buffers).  The plain stage runs from its cached plan (ir2rgb_amd/stageplan.py); everything else through the steps
+    above, which make the same library calls."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, gamma, beta, res1, res2, spec, conv, bn):
@@ -396,79 +550,24 @@ class ConvStageFn(Function):
         if plan is not None:        # the plain stage, host work precomputed (ir2rgb_amd/stageplan.py): same launches
             return plan.forward(ctx, x, bias, res1, res2, conv, bn)
         ctx.plan = None
-        dt = spec["dtype"]
-        first = spec["first"]
-        cout, cin = conv.out_channels, conv.in_channels
-        cout_p = cout if spec.get("out_f32", False) else padded_width(cout)
-        cin_p = cin if first else padded_width(cin)
-        padded = cout_p != cout or cin_p != cin
-        ctx.wfn = wfn = _pad_weight_fn(cout_p, cin_p, spec["transposed"]) if padded else None
-        if first:
-            kh, kw = conv.kernel_size
-            xin = L.xexpand(x, kw, spec["stride"][1], spec["pad"][1], spec["pad_mode"], dt)
-            desc = C.make_desc(tuple(xin.shape), cout_p, (kh, 1), (spec["stride"][0], 1), (spec["pad"][0], 0),
-                               spec["pad_mode"], dt, act=_fused_act(spec))
-            wp = L.packed_weight(conv, desc, _compose(wfn, L._xexpanded_weight(kw)), tag="xexp")
-        else:
-            if x.shape[1] != cin_p:
-                raise ValueError(f"conv stage: input has {x.shape[1]} channels, the layer runs at {cin_p} (autograd.pad_channels)")
-            xin = x
-            desc = C.make_desc(tuple(x.shape), cout_p, spec["k"], spec["stride"], spec["pad"], spec["pad_mode"],
-                               dt, spec["transposed"], spec.get("output_padding", 0), act=_fused_act(spec),
-                               out_f32=spec.get("out_f32", False),
-                               stats_per_sample=bn is not None and spec.get("groups", 1) > 1)
-            wp = L.packed_weight(conv, desc, wfn, tag="wpad" if padded else "w")
-        if padded and bias is not None:
-            bias = _pad_dim(bias.detach(), 0, cout_p)
+        xin, desc, wp, bias, ctx.wfn, ctx.sub = _stage_geometry(spec, conv, x, bias,
+                                                                bn is not None and spec.get("groups", 1) > 1)
         scale = shift = mean = invstd = None
         ctx.frozen = False
-        if bn is not None:
+        if bn is None:
+            y, _ = C.conv2d_fwd(desc, xin, wp, bias)
+            z = y
+        else:
             # the bias of a convolution in front of BatchNorm cancels: it is left out of the activations and
             # handed to the statistics kernel, which needs it for the running mean only (ir2rgb_bn_finalize_ex)
             ctx.frozen = L.bn_frozen(bn, spec["training"])
             y, stats = C.conv2d_fwd(desc, xin, wp, None, want_stats=not ctx.frozen)
-            bnp = _PaddedBN(bn, cout_p) if cout_p != cout else bn
-            G = spec.get("groups", 1)
-            count = desc.N * desc.Hout * desc.Wout
-            fused = FUSED_BN and not ctx.frozen and spec["training"] and cout_p % 64 == 0
-            if G == 1:
-                if fused and stats.shape[0] <= L.FUSED_BN_MAX_ROWS:
-                    # few partial rows (the residual blocks): statistics and apply in one launch
-                    z, scale, shift, mean, invstd = L.bn_finalize_apply(stats, count, bnp, y, spec["act"], res1, res2, bias)
-                else:
-                    scale, shift, mean, invstd = L.bn_finalize(stats, count, bnp, spec["training"], bias)
-                    z = L.bn_apply(y, scale, shift, spec["act"], res1, res2)
-            else:
-                # G independent forwards batched along N (the discriminators see real / generated / raw frames with the same
-                # weights): ONE convolution, then BatchNorm per sample group exactly as G separate calls would run it --
-                # statistics over the group's samples, running statistics advanced group by group
-                if desc.N % G or res1 is not None or res2 is not None:
-                    raise ValueError("conv stage: sample groups need N % groups == 0 and no residual inputs")
-                ng, rg = desc.N // G, (0 if ctx.frozen else stats.shape[0] // G)
-                z = torch.empty_like(y, memory_format=torch.channels_last)
-                vec = torch.empty((4, G, cout_p), dtype=torch.float32, device=y.device)
-                scale, shift, mean, invstd = vec[0], vec[1], vec[2], vec[3]
-                reps = L._STAT_UPDATES        # layers.repeated_forward: an int, or one count per group
-                try:
-                    for g in (spec.get("group_order") or range(G)):      # (the order the running statistics advance in)
-                        L._STAT_UPDATES = reps[g] if isinstance(reps, tuple) else reps
-                        yg, zg = y[g * ng:(g + 1) * ng], z[g * ng:(g + 1) * ng]
-                        sg = None if ctx.frozen else stats[g * rg:(g + 1) * rg]
-                        outs = (scale[g], shift[g], mean[g], invstd[g])
-                        if fused and rg <= L.FUSED_BN_MAX_ROWS:
-                            L.bn_finalize_apply(sg, count // G, bnp, yg, spec["act"], None, None, bias, out=zg, outs=outs)
-                        else:
-                            L.bn_finalize(sg, count // G, bnp, spec["training"], bias, outs=outs)
-                            L.bn_apply(yg, scale[g], shift[g], spec["act"], out=zg)
-                finally:
-                    L._STAT_UPDATES = reps
+            bnp = _PaddedBN(bn, desc.Cout) if desc.Cout != conv.out_channels else bn
+            z, scale, shift, mean, invstd = _batchnorm(spec, bnp, y, stats, bias, res1, res2, ctx.frozen)
             if bnp is not bn:
                 bnp.commit(spec["training"])
-        else:
-            y, _ = C.conv2d_fwd(desc, xin, wp, bias)
-            z = y
         ctx.spec, ctx.conv = spec, conv
-        ctx.x_shape = tuple(x.shape)
+        ctx.x_shape, ctx.width = tuple(x.shape), desc.Cout
         ctx.has_bn = bn is not None
         ctx.has_res = (res1 is not None, res2 is not None)
         ctx.save_for_backward(xin, y, scale, shift, mean, invstd)
@@ -480,10 +579,7 @@ class ConvStageFn(Function):
         if plan is not None:        # (the plan honours the backward flags and inactive sample groups itself)
             return plan.backward(ctx, gz)
         spec, conv = ctx.spec, ctx.conv
-        xin, y, scale, shift, mean, invstd = ctx.saved_tensors
-        hdt = xin.dtype
-        pad_fn = wfn = ctx.wfn
-        cout, cin = conv.out_channels, conv.in_channels
+        xin, y, *bnv = ctx.saved_tensors            # bnv: scale, shift, mean, invstd
         flags = getattr(conv, "_ir2rgb_bwd", 0)
         want_params = not (flags & SKIP_PARAM_GRADS)
         want_dx = ctx.needs_input_grad[0] and not (spec["first"] and (flags & SKIP_INPUT_GRAD))
@@ -496,100 +592,19 @@ class ConvStageFn(Function):
             n_full = y.shape[0]
             na = n_full // G * k
             gz, y, xin = gz[:na], y[:na], xin[:na]
-            if scale is not None and scale.dim() == 2:
-                scale, shift, mean, invstd = scale[:k], shift[:k], mean[:k], invstd[:k]
-        if spec.get("out_f32", False):
-            # thin fp32 output (PatchGAN logits): pad the gradient to 64 channels for the MFMA adjoint
-            cout = y.shape[1]
-            gy, gy_thin, dbias = thin_grad_expand(gz, hdt)      # 64-channel / 8-channel zero-padded halves, sum
-            pad_fn = _compose(wfn, lambda w: torch.cat([w, w.new_zeros((64 - w.shape[0],) + tuple(w.shape[1:]))], 0))
-            dgamma = dbeta = None
-        elif ctx.has_bn:
-            gz = _as_half_nhwc(gz, hdt)
-            act = spec["act"] | (16 if ctx.frozen else 0)
-            if scale.dim() == 1:
-                gy, dgamma, dbeta = bn_bwd(gz, y, scale, shift, mean, invstd, act)
-            else:                       # sample groups: per-group BatchNorm backward into the batch's gradient tensor
-                G = scale.shape[0]
-                ng = y.shape[0] // G
-                gy = torch.empty_like(y, memory_format=torch.channels_last)
-                params = None
-                for g in range(G):
-                    sl = slice(g * ng, (g + 1) * ng)
-                    _, dgamma, dbeta = bn_bwd(gz[sl], y[sl], scale[g], shift[g], mean[g], invstd[g], act, out=gy[sl], params=params)
-                    params = (dgamma, dbeta)
-                if ctx.frozen:
-                    scale = scale[0]    # (evaluation mode: the same running statistics for every group)
-            gy_thin = gy
-            # training mode: BatchNorm removes the per-channel mean, the bias gradient is exactly 0 (None = zeros);
-            # evaluation mode: the layer is affine in the bias, d/dbias = scale * sum g'
-            dbias = dbeta * scale if ctx.frozen else None
-        else:
-            gz = _as_half_nhwc(gz, hdt)
-            # LeakyReLU / ReLU keep the sign (ReLU: y > 0 <=> pre-activation > 0): mask from the stored output
-            act = 2 if spec["fused_leaky"] else (1 if spec.get("fused_relu") else 0)
-            gy, _, dbias = bn_bwd(gz, y, None, None, None, None, act)
-            gy_thin = gy
-            dgamma = dbeta = None
-        dx = None
-        if want_dx:
-            if spec["first"]:
-                kh, kw = conv.kernel_size
-                sub = dict(spec, k=(kh, 1), stride=(spec["stride"][0], 1), pad=(spec["pad"][0], 0))
-                if spec["pad_mode"] != C.PAD_ZERO:
-                    raise NotImplementedError("input gradient of a reflect-padded first layer is never needed")
-                # adjoint of the (kh x 1) convolution over the expanded image, then of the x-im2col
-                n, _, h, wout = xin.shape
-                dxe = conv_dgrad(gy, conv, sub, (n, 64, h, wout), _compose(wfn, L._xexpanded_weight(kw)), tag="dgrad_xexp")
-                dx = xexpand_bwd(dxe, ctx.x_shape[1], ctx.x_shape[3], kw, spec["stride"][1], spec["pad"][1],
-                                 spec["pad_mode"])
-            elif n_full is not None:
-                # the gradient tensor keeps the full batch's shape; the inactive groups' part stays unwritten
-                dx = C.empty_nhwc(n_full, ctx.x_shape[1], ctx.x_shape[2], ctx.x_shape[3], hdt, gy.device)
-                conv_dgrad(gy, conv, spec, (gy.shape[0],) + tuple(ctx.x_shape[1:]), pad_fn, out=dx[:gy.shape[0]])
-            else:
-                dx = conv_dgrad(gy, conv, spec, ctx.x_shape, pad_fn)
-            if n_full is not None and dx.shape[0] != n_full:       # (first layer: NCHW fp32 image gradient)
-                full = dx.new_empty((n_full,) + tuple(dx.shape[1:]))
-                full[:dx.shape[0]].copy_(dx)
-                dx = full
-        gy = gy_thin
+            if bnv[0] is not None and bnv[0].dim() == 2:
+                bnv = [v[:k] for v in bnv]
+        gz, gy, gyw, dbias, dgamma, dbeta = _output_grad(ctx, gz, y, *bnv)
+        dx = _input_grad(ctx, gy, xin, n_full) if want_dx else None
         dw = None
         if not want_params:
             dbias = dgamma = dbeta = None
-        if ctx.needs_input_grad[1] and want_params:
-            if spec["first"]:
-                def first_wgrad():
-                    kh, kw = conv.kernel_size
-                    sub = dict(spec, k=(kh, 1), stride=(spec["stride"][0], 1), pad=(spec["pad"][0], 0))
-                    gwe = conv_wgrad(xin, gy, (gy.shape[1], 64, kh, 1), sub)            # [co_p][64][kh][1]
-                    gwe = gwe[:cout, :cin * kw, :, 0].reshape(cout, cin, kw, kh)        # [co][ci][kx][ky]
-                    return gwe.permute(0, 1, 3, 2).contiguous()
-                dw = wgrad_overlapped(conv, first_wgrad, xin, gy)
-            else:
-                if spec.get("out_f32", False):   # gy holds 8 zero-padded channels: the extra rows are dropped
-                    wsh = (8,) + tuple(conv.weight.shape[1:])
-                    dw = wgrad_overlapped(conv, lambda: conv_wgrad(xin, gy, wsh, spec)[:conv.out_channels].contiguous(),
-                                          xin, gy)
-                elif wfn is not None:   # the layer ran at padded widths: the parameter's gradient is the real corner
-                    def padded_wgrad():
-                        g = conv_wgrad(xin, gy, None, spec)
-                        return (g[:cin, :cout] if spec["transposed"] else g[:cout, :cin]).contiguous()
-                    dw = wgrad_overlapped(conv, padded_wgrad, xin, gy)
-                else:
-                    wsh = tuple(conv.weight.shape)
-                    out, acc, dw = wgrad_destination(conv.weight, wsh)
-                    if acc:
-                        conv_wgrad(xin, gy, wsh, spec, out=out, accumulate=True)
-                    else:
-                        # (conv2d_wgrad hands back the fresh tensor, or its own new view of the sink)
-                        dw = wgrad_overlapped(conv, lambda: conv_wgrad(xin, gy, wsh, spec, out=out), xin, gy)
+        elif ctx.needs_input_grad[1]:
+            dw = _weight_grad(ctx, xin, gyw)
+        if ctx.width != conv.out_channels:      # padded width: reference-shaped parameter gradients
+            dbias, dgamma, dbeta = (None if t is None else t[:conv.out_channels] for t in (dbias, dgamma, dbeta))
         r1 = gz if ctx.has_res[0] else None
         r2 = gz if ctx.has_res[1] else None
-        if wfn is not None:      # reference-shaped parameter gradients
-            dbias = dbias[:cout] if dbias is not None else None
-            dgamma = dgamma[:cout] if dgamma is not None else None
-            dbeta = dbeta[:cout] if dbeta is not None else None
         return dx, dw, (dbias if ctx.needs_input_grad[2] else None), dgamma, dbeta, r1, r2, None, None, None
 
 
@@ -609,12 +624,8 @@ def conv_stage(x, conv, bn, act, pad_mode, dtype, *, first=False, stride=None, p
 
 
 # ---------------------------------------------------------------------------------------------
-# heads and warp-blend: HIP forward; backward INTERIM through torch autograd recompute
+# heads, warp-blend and the small element-wise stages: HIP forward and HIP backward
 # ---------------------------------------------------------------------------------------------
-def _pad_rows(w, rows):
-    return torch.cat([w, w.new_zeros((rows - w.shape[0],) + tuple(w.shape[1:]))], 0) if w.shape[0] < rows else w
-
-
 class HeadFn(Function):
     """Separable 7x7 head(s) on one feature map: HIP forward (1x7 MFMA pass + head_finish) and HIP
     backward (head_finish_bwd -> adjoint 1x7 MFMA convolution + reflect fold for the feature gradient,
@@ -638,35 +649,14 @@ class HeadFn(Function):
         gout = gout.float().contiguous()
         dT = C.empty_nhwc(n, CT, h, w, feat.dtype, feat.device)
         dbias = torch.empty(cout, dtype=torch.float32, device=feat.device)
-        rows = _lib.lib().ir2rgb_head_finish_bwd_rows(n, h, w)
-        if rows < 0:
-            _lib.check(rows, "head_finish_bwd_rows")
-        partial = torch.empty((rows, 8), dtype=torch.float32, device=feat.device)
-        packed_acts = 0
-        for i, a in enumerate(acts):
-            packed_acts |= (a & 15) << (4 * i)
-        with _lib.on_device(feat):
-            rc = _lib.lib().ir2rgb_head_finish_bwd(gout, out, dT, dbias, partial, n, h, w, cout, kh, CT, kh // 2,
-                                                   packed_acts, float(mul), _DT[feat.dtype], _lib.current_stream(feat))
-        _lib.check(rc, "head_finish_bwd")
-        spec = dict(k=(1, kw), stride=(1, 1), pad=(0, kw // 2), pad_mode=C.PAD_REFLECT, transposed=False)
+        partial = torch.empty((_lib.query("ir2rgb_head_finish_bwd_rows", n, h, w), 8), dtype=torch.float32, device=feat.device)
+        _lib.launch("ir2rgb_head_finish_bwd", feat, gout, out, dT, dbias, partial, n, h, w, cout, kh, CT, kh // 2,
+                    L.pack_acts(acts), float(mul), _DT[feat.dtype])
         gfeat = None
         if ctx.needs_input_grad[0]:
-            holder = convs[0]
-            key = ("ysplit_adj", _DT[feat.dtype], cin) + tuple((c.weight._version, c.weight.data_ptr()) for c in convs)
-            cache = holder.__dict__.setdefault("_ir2rgb_packed", {})
-            hit = cache.get("ysplit_adj")
             desc = C.make_desc((n, CT, h, w), cin, (1, kw), 1, (0, kw - 1), C.PAD_ZERO, feat.dtype)
-            if hit is None or hit[0] != key:
-                with torch.no_grad():
-                    wcat = _pad_dim(torch.cat([c.weight.detach().float() for c in convs], 0), 1, cin)
-                    wy = _pad_rows(L._ysplit_weight(wcat), CT).contiguous()      # [64][cin][1][kw] forward weight
-                    cache["ysplit_adj"] = (key, C.pack_weight(desc, wy, adjoint=True))
-                    if SC.ENABLED:
-                        SC.produced(cache["ysplit_adj"][1], "packed head weight (adjoint)")
-            if SC.ENABLED:
-                SC.consumed(cache["ysplit_adj"][1], "packed head weight (adjoint)")
-            dpad, _ = C.conv2d_fwd(desc, dT, cache["ysplit_adj"][1])
+            # the adjoint packing of the [64][cin][1][kw] forward weight
+            dpad, _ = C.conv2d_fwd(desc, dT, L.head_weight(convs, desc, cin, rows=CT, adjoint=True))
             gfeat = fold_reflect(dpad, 0, kw // 2)
         wdesc = C.make_desc(tuple(feat.shape), CT, (1, kw), 1, (0, kw // 2), C.PAD_REFLECT, feat.dtype)
         gw = C.conv2d_wgrad(wdesc, feat, dT)                                       # [64][cin][1][kw]
@@ -702,10 +692,7 @@ class WarpBlendFn(Function):
         gout = gout.float().contiguous()
         graw, gflow, gw = torch.empty_like(raw), torch.empty_like(flow), torch.empty_like(weight)
         n, _, h, w = raw.shape
-        with _lib.on_device(raw):
-            rc = _lib.lib().ir2rgb_warp_blend_bwd(gout, raw, prev, flow, weight, graw, gflow,
-                                                  gw, n, prev.shape[1], h, w, _lib.current_stream(raw))
-        _lib.check(rc, "warp_blend_bwd")
+        _lib.launch("ir2rgb_warp_blend_bwd", raw, gout, raw, prev, flow, weight, graw, gflow, gw, n, prev.shape[1], h, w)
         gprev = None
         if ctx.needs_input_grad[1]:
             from .networks import get_grid
@@ -732,9 +719,7 @@ class AvgPool3s2Fn(Function):
         h, w = x.shape[-2:]
         ctx.shape = tuple(x.shape)
         y = torch.empty(tuple(x.shape[:-2]) + ((h - 1) // 2 + 1, (w - 1) // 2 + 1), dtype=torch.float32, device=x.device)
-        with _lib.on_device(x):
-            rc = _lib.lib().ir2rgb_avgpool3s2(x, y, x.numel() // (h * w), h, w, 0, _lib.current_stream(x))
-        _lib.check(rc, "avgpool3s2")
+        _lib.launch("ir2rgb_avgpool3s2", x, x, y, x.numel() // (h * w), h, w, 0)
         return y
 
     @staticmethod
@@ -742,9 +727,7 @@ class AvgPool3s2Fn(Function):
         g = g.contiguous()
         gx = torch.empty(ctx.shape, dtype=torch.float32, device=g.device)
         h, w = ctx.shape[-2:]
-        with _lib.on_device(g):
-            rc = _lib.lib().ir2rgb_avgpool3s2(g, gx, gx.numel() // (h * w), h, w, 1, _lib.current_stream(g))
-        _lib.check(rc, "avgpool3s2 backward")
+        _lib.launch("ir2rgb_avgpool3s2", g, g, gx, gx.numel() // (h * w), h, w, 1)
         return gx
 
 

@@ -101,7 +101,6 @@ class PackBatch:
     packed tensors are kept alive here and must not be reallocated."""
 
     def __init__(self, jobs):
-        lib = _lib.lib()
         self.keep = [(w, p) for _, w, p, _ in jobs]
         arr = (_lib.PackJob * len(jobs))()
         for j, (desc, w, packed, adjoint) in enumerate(jobs):
@@ -110,49 +109,32 @@ class PackBatch:
             arr[j].desc, arr[j].w, arr[j].wpacked, arr[j].adjoint = desc, w.data_ptr(), packed.data_ptr(), int(bool(adjoint))
         self.dtype = jobs[0][0].dtype
         self.device = jobs[0][1].device
-        nbytes = lib.ir2rgb_conv2d_pack_batch_table_bytes(arr, len(jobs))
-        if nbytes < 0:
-            _lib.check(int(nbytes), "conv2d_pack_batch_table_bytes")
-        host = torch.zeros(int(nbytes), dtype=torch.uint8)
+        nbytes = int(_lib.query("ir2rgb_conv2d_pack_batch_table_bytes", arr, len(jobs)))
+        host = torch.zeros(nbytes, dtype=torch.uint8)
         nblocks = ctypes.c_int(0)
-        n = lib.ir2rgb_conv2d_pack_batch_build(arr, len(jobs), host.data_ptr(), int(nbytes),
-                                               ctypes.byref(nblocks))
-        if n < 0:
-            _lib.check(int(n), "conv2d_pack_batch_build")
+        n = _lib.query("ir2rgb_conv2d_pack_batch_build", arr, len(jobs), host.data_ptr(), nbytes, ctypes.byref(nblocks))
         self.nentries, self.nblocks = int(n), int(nblocks.value)
         self.table = host.to(self.device)
 
     def run(self):
-        with _lib.on_device(self.table):
-            rc = _lib.lib().ir2rgb_conv2d_pack_batch_run(self.table, self.nentries, self.nblocks, self.dtype,
-                                                         _lib.current_stream(self.table))
-        _lib.check(rc, "conv2d_pack_batch_run")
+        _lib.launch("ir2rgb_conv2d_pack_batch_run", self.table, self.table, self.nentries, self.nblocks, self.dtype)
 
 
 def pack_weight(desc, weight, adjoint=False):
     """weight: fp32 torch layout ([Cout,Cin,kh,kw], or [Cin,Cout,kh,kw] for transposed).  adjoint=True:
     ``desc`` is the data-gradient convolution of a stride-1 Conv2d and ``weight`` its forward weight."""
     _lib.require_device(weight, dtype=torch.float32)
-    lib = _lib.lib()
-    n = lib.ir2rgb_conv2d_packed_weight_elems(desc)
-    if n < 0:
-        _lib.check(int(n), "conv2d_packed_weight_elems")
+    n = _lib.query("ir2rgb_conv2d_packed_weight_elems", desc)
     dt = torch.bfloat16 if desc.dtype == BF16 else torch.float16
     packed = torch.empty(n, dtype=dt, device=weight.device)
-    with _lib.on_device(weight):
-        fn = lib.ir2rgb_conv2d_pack_weight_adjoint if adjoint else lib.ir2rgb_conv2d_pack_weight
-        rc = fn(desc, weight, packed, _lib.current_stream(weight))
-    _lib.check(rc, "conv2d_pack_weight")
+    _lib.launch("ir2rgb_conv2d_pack_weight_adjoint" if adjoint else "ir2rgb_conv2d_pack_weight", weight, desc, weight, packed)
     return packed
 
 
 def stats_rows(desc):
     r = getattr(desc, "_stats_rows", None)
     if r is None:
-        r = _lib.lib().ir2rgb_conv2d_stats_rows(desc)
-        if r < 0:
-            _lib.check(r, "conv2d_stats_rows")
-        desc._stats_rows = r
+        r = desc._stats_rows = _lib.query("ir2rgb_conv2d_stats_rows", desc)
     return r
 
 
@@ -160,9 +142,7 @@ def fwd_workspace_bytes(desc):
     """Bytes of workspace ir2rgb_conv2d_fwd_ws wants for ``desc`` (0: none), asked once per descriptor."""
     n = getattr(desc, "_ws_bytes", None)         # (descriptors are built once per layer and shape and never edited)
     if n is None:
-        n = desc._ws_bytes = int(_lib.lib().ir2rgb_conv2d_fwd_workspace_bytes(desc))
-        if n < 0:
-            _lib.check(n, "conv2d_fwd_workspace_bytes")
+        n = desc._ws_bytes = int(_lib.query("ir2rgb_conv2d_fwd_workspace_bytes", desc))
     return n
 
 

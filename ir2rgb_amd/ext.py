@@ -16,11 +16,6 @@ from . import _lib
 _f32 = torch.float32
 
 
-def _p(t):
-
-    return t.data_ptr()
-
-
 class correlation_cuda:
     @staticmethod
     def out_shape(C, H, W, pad_size, kernel_size, max_displacement, stride1, stride2):
@@ -45,11 +40,8 @@ class correlation_cuda:
         if oh <= 0 or ow <= 0:
             raise ValueError("correlation: empty output for these parameters")
         output.resize_(N, oc, oh, ow)
-        with _lib.on_device(input1):
-            rc = _lib.lib().ir2rgb_correlation_fwd(input1, input2, output, N, C, H, W, pad_size,
-                                                   kernel_size, max_displacement, stride1, stride2,
-                                                   _lib.current_stream(input1))
-        _lib.check(rc, "correlation_cuda.forward")
+        _lib.launch("ir2rgb_correlation_fwd", input1, input1, input2, output, N, C, H, W, pad_size, kernel_size,
+                    max_displacement, stride1, stride2)
         return 1
 
     @staticmethod
@@ -64,11 +56,8 @@ class correlation_cuda:
             raise ValueError(f"correlation backward: gradOutput {tuple(gradOutput.shape)} != {(N, oc, oh, ow)}")
         gradInput1.resize_(N, C, H, W)
         gradInput2.resize_(N, C, H, W)
-        with _lib.on_device(input1):
-            rc = _lib.lib().ir2rgb_correlation_bwd(input1, input2, gradOutput, gradInput1,
-                                                   gradInput2, N, C, H, W, pad_size, kernel_size,
-                                                   max_displacement, stride1, stride2, _lib.current_stream(input1))
-        _lib.check(rc, "correlation_cuda.backward")
+        _lib.launch("ir2rgb_correlation_bwd", input1, input1, input2, gradOutput, gradInput1, gradInput2, N, C, H, W,
+                    pad_size, kernel_size, max_displacement, stride1, stride2)
         return 1
 
 
@@ -89,21 +78,15 @@ class resample2d_cuda:
         _lib.require_device(output, dtype=_f32)
         if tuple(output.shape) != (N, C, H, W):
             raise ValueError("resample2d: output has the wrong shape")
-        with _lib.on_device(input1):
-            rc = _lib.lib().ir2rgb_resample2d_fwd(input1, input2, output, N, C, H, W, kernel_size,
-                                                  _lib.current_stream(input1))
-        _lib.check(rc, "resample2d_cuda.forward")
+        _lib.launch("ir2rgb_resample2d_fwd", input1, input1, input2, output, N, C, H, W, kernel_size)
         return 1
 
     @staticmethod
     def backward(input1, input2, gradOutput, gradInput1, gradInput2, kernel_size):
         N, C, H, W = resample2d_cuda._shapes(input1, input2)
         _lib.require_device(gradOutput, gradInput1, gradInput2, dtype=_f32)
-        with _lib.on_device(input1):
-            rc = _lib.lib().ir2rgb_resample2d_bwd(input1, input2, gradOutput, gradInput1,
-                                                  gradInput2, N, C, H, W, kernel_size,
-                                                  _lib.current_stream(input1))
-        _lib.check(rc, "resample2d_cuda.backward")
+        _lib.launch("ir2rgb_resample2d_bwd", input1, input1, input2, gradOutput, gradInput1, gradInput2, N, C, H, W,
+                    kernel_size)
         return 1
 
 
@@ -114,20 +97,14 @@ class channelnorm_cuda:
         N, C, H, W = input1.shape
         if tuple(output.shape) != (N, 1, H, W):
             raise ValueError("channelnorm: output has the wrong shape")
-        with _lib.on_device(input1):
-            rc = _lib.lib().ir2rgb_channelnorm_fwd(input1, output, N, C, H, W, norm_deg,
-                                                   _lib.current_stream(input1))
-        _lib.check(rc, "channelnorm_cuda.forward")
+        _lib.launch("ir2rgb_channelnorm_fwd", input1, input1, output, N, C, H, W, norm_deg)
         return 1
 
     @staticmethod
     def backward(input1, output, gradOutput, gradInput1, norm_deg):
         _lib.require_device(input1, output, gradOutput, gradInput1, dtype=_f32)
         N, C, H, W = input1.shape
-        with _lib.on_device(input1):
-            rc = _lib.lib().ir2rgb_channelnorm_bwd(input1, output, gradOutput, gradInput1, N, C, H, W,
-                                                   norm_deg, _lib.current_stream(input1))
-        _lib.check(rc, "channelnorm_cuda.backward")
+        _lib.launch("ir2rgb_channelnorm_bwd", input1, input1, output, gradOutput, gradInput1, N, C, H, W, norm_deg)
         return 1
 
 
@@ -141,10 +118,5 @@ def warp_diff_norm(img1, img2, flow, want_warped=True, want_diff=True, want_norm
     warped = torch.empty_like(img2) if want_warped else None
     diff = torch.empty_like(img2) if want_diff else None
     norm = img2.new_empty(N, 1, H, W) if want_norm else None
-    null = 0
-    with _lib.on_device(img1):
-        rc = _lib.lib().ir2rgb_warp_diff_norm_fwd(img1, img2, flow, warped if want_warped else null,
-                                                  diff if want_diff else null, norm if want_norm else null,
-                                                  N, C, H, W, _lib.current_stream(img1))
-    _lib.check(rc, "warp_diff_norm")
+    _lib.launch("ir2rgb_warp_diff_norm_fwd", img1, img1, img2, flow, warped, diff, norm, N, C, H, W)
     return warped, diff, norm

@@ -13,25 +13,15 @@ The 2-channel ConvTranspose2d(2,2,4,2,1) flow up-samplers are a small direct ker
 same buffers.  Left on torch (tiny 2..12-channel fp32 tensors): the x4 interpolations and the
 normalisation / concatenation glue of FlowNet2.forward.
 """
-import ctypes
 import os
 
 import torch
-import torch.nn.functional as F
 
 from . import _lib
 from . import conv as C
 from . import layers as L
 
 LEAKY01 = 2  # ir2rgb_conv_desc.act code for LeakyReLU(0.1)
-_DT = {torch.bfloat16: 1, torch.float16: 2}
-
-
-def _p(t):
-
-    # (a plain int: accepted by the fastcall bindings and by ctypes' c_void_p parameters alike; a c_void_p object per
-    # argument cost 0.75 us, ten of them per launch)
-    return t.data_ptr() if t is not None else 0
 
 
 def _up64(c):
@@ -97,14 +87,7 @@ def new_buf(n, ld, h, w, dtype, device):
 
 
 def _pad_cin(cin_to, transposed):
-    def f(w):
-        ci = w.shape[0] if transposed else w.shape[1]
-        if ci == cin_to:
-            return w
-        if transposed:
-            return torch.cat([w, w.new_zeros((cin_to - ci,) + tuple(w.shape[1:]))], 0)
-        return torch.cat([w, w.new_zeros((w.shape[0], cin_to - ci) + tuple(w.shape[2:]))], 1)
-    return f
+    return lambda w: L.pad_dim(w, 0 if transposed else 1, cin_to)
 
 
 def conv(xv, mod, yv, act, *, k=None, stride=None, pad=None, transposed=False, out_f32=False, weight_fn=None, tag="fn"):
@@ -121,7 +104,7 @@ def conv(xv, mod, yv, act, *, k=None, stride=None, pad=None, transposed=False, o
     cout = yv.ch
     oh, ow = yv.hw
     desc = C.ConvDesc(n, h, w, cin, oh, ow, cout, k[0], k[1], stride[0], stride[1], pad[0], pad[1], C.PAD_ZERO,
-                      int(transposed), _DT[dt], act, int(out_f32), xv.ld, xv.off, yv.ld, yv.off)
+                      int(transposed), C._TORCH2DT[dt], act, int(out_f32), xv.ld, xv.off, yv.ld, yv.off)
     fn = _pad_cin(cin, transposed) if weight_fn is None else weight_fn
     wp = L.packed_weight(mod, desc, fn, tag=tag)
     C.conv2d_fwd_view(desc, xv.buf, wp, mod.bias, yv.buf)
@@ -143,10 +126,7 @@ def put_nchw(x_nchw, yv, act=0):
     """NCHW fp32 -> channel slice of an NHWC half buffer (optionally LeakyReLU(0.1))."""
     x = x_nchw.float().contiguous()
     n, c, h, w = x.shape
-    with _lib.on_device(x):
-        rc = _lib.lib().ir2rgb_nchw_f32_to_nhwc_half_slice(x, yv.buf, n, c, h, w, yv.ld, yv.off, act,
-                                                           _DT[yv.buf.dtype], _lib.current_stream(x))
-    _lib.check(rc, "nchw_f32_to_nhwc_half_slice")
+    _lib.launch("ir2rgb_nchw_f32_to_nhwc_half_slice", x, x, yv.buf, n, c, h, w, yv.ld, yv.off, act, C._TORCH2DT[yv.buf.dtype])
 
 
 def corr_nhwc(mod, av, bv, yv, slope):
@@ -160,9 +140,9 @@ def corr_nhwc(mod, av, bv, yv, slope):
         return False
     n = av.n
     h, w = av.hw
-    with _lib.on_device(av.buf):
+    with _lib.on_device(av.buf):        # (explicit, not _lib.launch: "not supported" is an answer here, not an error)
         rc = _lib.lib().ir2rgb_correlation_nhwc_half(av.buf, av.ld, av.off, bv.buf, bv.ld, bv.off, yv.buf, 1, yv.ld,
-                                                     yv.off, float(slope), n, av.ch, h, w, _DT[av.buf.dtype],
+                                                     yv.off, float(slope), n, av.ch, h, w, C._TORCH2DT[av.buf.dtype],
                                                      _lib.current_stream(av.buf))
     if rc == -2:        # IR2RGB_ENOSUP
         return False
@@ -173,10 +153,8 @@ def corr_nhwc(mod, av, bv, yv, slope):
 def flow_up(flow, mod, yv):
     """ConvTranspose2d(2,2,4,2,1) of a 2-channel fp32 flow, written into a 2-channel slice of ``yv.buf``."""
     n, _, h, w = flow.shape
-    with _lib.on_device(flow):
-        rc = _lib.lib().ir2rgb_flow_upsample_slice(flow, mod.weight, mod.bias, yv.buf, n, h, w, yv.ld, yv.off,
-                                                   _DT[yv.buf.dtype], _lib.current_stream(flow))
-    _lib.check(rc, "flow_upsample_slice")
+    _lib.launch("ir2rgb_flow_upsample_slice", flow, flow, mod.weight, mod.bias, yv.buf, n, h, w, yv.ld, yv.off,
+                C._TORCH2DT[yv.buf.dtype])
 
 
 def predict(xv, mod, n, h, w):

@@ -55,9 +55,7 @@ def frame_push(frame, hist0, hist1=None):
         raise ValueError(f"frame_push: frame {tuple(frame.shape)} does not fit the history {tuple(hist0.shape)}")
     if hist1 is not None and tuple(hist1.shape) != (T, C, (H - 1) // 2 + 1, (W - 1) // 2 + 1):
         raise ValueError(f"frame_push: half-resolution history {tuple(hist1.shape)} does not fit {tuple(hist0.shape)}")
-    with _lib.on_device(hist0):
-        rc = _lib.lib().ir2rgb_frame_push_u8(frame, hist0, hist1, T, C, H, W, int(f32), _lib.current_stream(hist0))
-    _lib.check(rc, "frame_push_u8")
+    _lib.launch("ir2rgb_frame_push_u8", hist0, frame, hist0, hist1, T, C, H, W, int(f32))
 
 
 def frame_finish(x, hist, img_u8=None):
@@ -71,9 +69,7 @@ def frame_finish(x, hist, img_u8=None):
         raise ValueError(f"frame_finish: frame {tuple(x.shape)} does not fit the history {tuple(hist.shape)}")
     if img_u8 is not None and tuple(img_u8.shape) != (h, w, 3):
         raise ValueError(f"frame_finish: image {tuple(img_u8.shape)} is not [{h},{w},3]")
-    with _lib.on_device(hist):
-        rc = _lib.lib().ir2rgb_frame_finish_u8(x, hist, img_u8, T, h, w, _lib.current_stream(hist))
-    _lib.check(rc, "frame_finish_u8")
+    _lib.launch("ir2rgb_frame_finish_u8", hist, x, hist, img_u8, T, h, w)
 
 
 class SequenceState:

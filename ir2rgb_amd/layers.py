@@ -10,9 +10,9 @@ A "stage" is what the reference writes as ``[pad, conv, norm, activation]`` modu
 Parameters stay in the fp32 ``nn.Conv2d`` / ``nn.BatchNorm2d`` containers the state_dict
 exposes; the half-precision packed copy the MFMA kernel streams is cached per module and
 refreshed whenever the fp32 weight's version counter moves (optimizer step, load_state_dict).
+The stage as a whole, forward and backward, is ``autograd.ConvStageFn``; this module holds its pieces.
 """
 import contextlib
-import ctypes
 
 import torch
 import torch.nn as nn
@@ -23,13 +23,6 @@ from . import streamcheck as SC
 
 ACT_NONE, ACT_RELU, ACT_LEAKY = 0, 1, 2
 _DT = C._TORCH2DT
-
-
-def _p(t):
-
-    # (a plain int: accepted by the fastcall bindings and by ctypes' c_void_p parameters alike; a c_void_p object per
-    # argument cost 0.75 us, ten of them per launch)
-    return t.data_ptr() if t is not None else 0
 
 
 def _require_gpu(t, what):
@@ -43,9 +36,7 @@ def _require_gpu(t, what):
 def _gather(src, idx, dst):
     if SC.ENABLED:
         SC.consumed(src, "fp32 parameter"), SC.consumed(idx, "gather plan")
-    with _lib.on_device(src):
-        rc = _lib.lib().ir2rgb_gather_f32(src, idx, dst, dst.numel(), _lib.current_stream(src))
-    _lib.check(rc, "gather_f32")
+    _lib.launch("ir2rgb_gather_f32", src, src, idx, dst, dst.numel())
     if SC.ENABLED:
         SC.produced(dst, "rearranged fp32 weight")
     return dst
@@ -232,13 +223,9 @@ def bn_finalize(stats, count, bn, training=True, conv_bias=None, outs=None):
         SC.consumed(bn.running_mean, "BatchNorm running statistics")
         if track:
             SC.produced(bn.running_mean, "BatchNorm running statistics")
-    with _lib.on_device(scale):
-        rc = _lib.lib().ir2rgb_bn_finalize_ex(stats, rows, ch, int(count), bn.weight, bn.bias, conv_bias,
-                                              bn.running_mean if use_running else None,
-                                              bn.running_var if use_running else None, float(momentum),
-                                              float(bn.eps), scale, shift, mean, invstd, _STAT_UPDATES,
-                                              int(frozen), _lib.current_stream(scale))
-    _lib.check(rc, "bn_finalize")
+    _lib.launch("ir2rgb_bn_finalize_ex", scale, stats, rows, ch, int(count), bn.weight, bn.bias, conv_bias,
+                bn.running_mean if use_running else None, bn.running_var if use_running else None, float(momentum),
+                float(bn.eps), scale, shift, mean, invstd, _STAT_UPDATES, int(frozen))
     if track and bn.num_batches_tracked is not None:
         _PENDING_COUNTERS.append((bn.num_batches_tracked, _STAT_UPDATES))
     return scale, shift, mean, invstd
@@ -264,17 +251,12 @@ def bn_finalize_apply(stats, count, bn, y, act, res1=None, res2=None, conv_bias=
         pw, pb, prm, prv, has_rm = bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.running_mean is not None
         momentum, eps, trs = 0.1 if bn.momentum is None else float(bn.momentum), float(bn.eps), bn.track_running_stats
     track = trs and has_rm
-    null = 0
     if SC.ENABLED and track:
         SC.consumed(bn.running_mean, "BatchNorm running statistics")
         SC.produced(bn.running_mean, "BatchNorm running statistics")
-    with _lib.on_device(y):
-        rc = _lib.lib().ir2rgb_bn_finalize_apply(stats, rows, ch, int(count), pw, pb, conv_bias,
-                                                 prm if track else null, prv if track else null, momentum, eps,
-                                                 scale, shift, mean, invstd,
-                                                 _STAT_UPDATES, y, res1, res2, z, n * h * w, act,
-                                                 _DT[y.dtype], _lib.current_stream(y))
-    _lib.check(rc, "bn_finalize_apply")
+    _lib.launch("ir2rgb_bn_finalize_apply", y, stats, rows, ch, int(count), pw, pb, conv_bias,
+                prm if track else None, prv if track else None, momentum, eps, scale, shift, mean, invstd,
+                _STAT_UPDATES, y, res1, res2, z, n * h * w, act, _DT[y.dtype])
     if track and bn.num_batches_tracked is not None:
         _PENDING_COUNTERS.append((bn.num_batches_tracked, _STAT_UPDATES))
     return z, scale, shift, mean, invstd
@@ -299,10 +281,7 @@ def flush_bn_counters():
 def bn_apply(x, scale, shift, act=ACT_NONE, res1=None, res2=None, out=None):
     n, ch, h, w = x.shape
     y = out if out is not None else torch.empty_like(x, memory_format=torch.channels_last)
-    with _lib.on_device(x):
-        rc = _lib.lib().ir2rgb_bn_apply(x, scale, shift, res1, res2, y, n * h * w, ch, act,
-                                        _DT[x.dtype], _lib.current_stream(x))
-    _lib.check(rc, "bn_apply")
+    _lib.launch("ir2rgb_bn_apply", x, x, scale, shift, res1, res2, y, n * h * w, ch, act, _DT[x.dtype])
     return y
 
 
@@ -317,9 +296,7 @@ def to_nhwc_half(x, dtype):
     x = x.float().contiguous()
     n, ch, h, w = x.shape
     y = C.empty_nhwc(n, ch, h, w, dtype, x.device)
-    with _lib.on_device(x):
-        rc = _lib.lib().ir2rgb_nchw_f32_to_nhwc_half(x, y, n, ch, h, w, _DT[dtype], _lib.current_stream(x))
-    _lib.check(rc, "nchw_f32_to_nhwc_half")
+    _lib.launch("ir2rgb_nchw_f32_to_nhwc_half", x, x, y, n, ch, h, w, _DT[dtype])
     return y
 
 
@@ -331,9 +308,7 @@ def to_nchw_f32(x):
         return x.float().contiguous()
     n, ch, h, w = x.shape
     y = torch.empty((n, ch, h, w), dtype=torch.float32, device=x.device)
-    with _lib.on_device(x):
-        rc = _lib.lib().ir2rgb_nhwc_half_to_nchw_f32(x, y, n, ch, h, w, _DT[x.dtype], _lib.current_stream(x))
-    _lib.check(rc, "nhwc_half_to_nchw_f32")
+    _lib.launch("ir2rgb_nhwc_half_to_nchw_f32", x, x, y, n, ch, h, w, _DT[x.dtype])
     return y
 
 
@@ -344,13 +319,13 @@ def xexpand(x, kw, stride_w, pad_w, pad_mode, dtype, cx=64):
     n, cin, h, w = x.shape
     wout = (w + 2 * pad_w - kw) // stride_w + 1
     y = C.empty_nhwc(n, cx, h, wout, dtype, x.device)
-    with _lib.on_device(x):
-        rc = _lib.lib().ir2rgb_xexpand_cx(x, y, n, cin, h, w, wout, kw, stride_w, pad_w, pad_mode, cx, _DT[dtype],
-                                          _lib.current_stream(x))
-    _lib.check(rc, "xexpand")
+    _lib.launch("ir2rgb_xexpand_cx", x, x, y, n, cin, h, w, wout, kw, stride_w, pad_w, pad_mode, cx, _DT[dtype])
     return y
 
 
+# ---------------------------------------------------------------------------------------------
+# rearranged weight forms (pure index maps: packed_weight refreshes them by one gather launch)
+# ---------------------------------------------------------------------------------------------
 def _xexpanded_weight(kw, cx=64):
     """[Cout,Cin,kh,kw] -> [Cout,cx,kh,1] with input channel ci*kw+kx (zero padded to cx)."""
     def f(w):
@@ -362,52 +337,54 @@ def _xexpanded_weight(kw, cx=64):
     return f
 
 
+def pad_dim(t, dim, to, value=0.0):
+    """``t`` grown to ``to`` entries along ``dim`` with ``value`` (``t`` itself when it already has them).  On a weight this
+    is a pure index map, as packed_weight's gather plan wants of a rearrangement."""
+    if t.shape[dim] == to:
+        return t
+    shape = list(t.shape)
+    shape[dim] = to - t.shape[dim]
+    return torch.cat([t, t.new_full(shape, value)], dim)
+
+
 def _ysplit_weight(w):
-    """[Cout,Cin,kh,kw] -> [pad24(Cout*kh),Cin,1,kw]: output channel co*kh+ky holds row ky of the kernel."""
+    """[Cout,Cin,kh,kw] -> [pad8(Cout*kh),Cin,1,kw]: output channel co*kh+ky holds row ky of the kernel."""
     co, ci, kh, kw = w.shape
     v = w.permute(0, 2, 1, 3).reshape(co * kh, ci, 1, kw)
-    pad = (-v.shape[0]) % 8
-    if pad:
-        v = torch.cat([v, v.new_zeros(pad, ci, 1, kw)], 0)
-    return v
+    return pad_dim(v, 0, (co * kh + 7) // 8 * 8)
 
 
 # ---------------------------------------------------------------------------------------------
-# stages
+# heads, warp-blend, add
 # ---------------------------------------------------------------------------------------------
-def conv_stage(x, conv, bn, act, pad_mode, *, stride=None, pad=None, transposed=False, output_padding=0,
-               res1=None, res2=None, fused_leaky=False, training=True):
-    """x (channels_last half) -> act(bn(conv(x))) [+ res1 + res2].  ``bn`` may be None."""
-    stride = conv.stride if stride is None else stride
-    pad = conv.padding if pad is None else pad
-    desc = C.make_desc(tuple(x.shape), conv.out_channels, conv.kernel_size, stride, pad, pad_mode, x.dtype, transposed,
-                       output_padding, act=1 if fused_leaky else 0)
-    wp = packed_weight(conv, desc)
-    if bn is None:
-        return C.conv2d_fwd(desc, x, wp, conv.bias)[0]
-    y, stats = C.conv2d_fwd(desc, x, wp, None, want_stats=not bn_frozen(bn, training))
-    scale, shift, _, _ = bn_finalize(stats, desc.N * desc.Hout * desc.Wout, bn, training, conv.bias)
-    return bn_apply(y, scale, shift, act, res1, res2, out=y)
+def pack_acts(acts):
+    """Per-output-channel activation codes as the nibbles of one integer (ir2rgb_head_finish / _bwd)."""
+    packed = 0
+    for i, a in enumerate(acts):
+        packed |= (a & 15) << (4 * i)
+    return packed
 
 
-def first_stage(x_nchw, conv, bn, act, pad_mode, dtype, *, fused_leaky=False, training=True):
-    """Small-Cin first layer on an NCHW fp32 image: x-im2col + (kh x 1) MFMA convolution.
-
-    ReflectionPad2d(3)+Conv7x7 (networks.py:141,:150,:253-255) or Conv4x4 s2 p2 (:680)."""
-    kh, kw = conv.kernel_size
-    sh, sw = conv.stride
-    ph, pw = (3, 3) if pad_mode == C.PAD_REFLECT else conv.padding
-    if conv.in_channels * kw > 64:
-        raise NotImplementedError(f"first layer with {conv.in_channels} input channels x kernel width {kw} > 64")
-    xe = xexpand(x_nchw, kw, sw, pw, pad_mode, dtype)
-    desc = C.make_desc(tuple(xe.shape), conv.out_channels, (kh, 1), (sh, 1), (ph, 0), pad_mode, dtype,
-                       act=1 if fused_leaky else 0)
-    wp = packed_weight(conv, desc, _xexpanded_weight(kw), tag="xexp")
-    if bn is None:
-        return C.conv2d_fwd(desc, xe, wp, conv.bias)[0]
-    y, stats = C.conv2d_fwd(desc, xe, wp, None, want_stats=not bn_frozen(bn, training))
-    scale, shift, _, _ = bn_finalize(stats, desc.N * desc.Hout * desc.Wout, bn, training, conv.bias)
-    return bn_apply(y, scale, shift, act, out=y)
+def head_weight(convs, desc, cin, rows=None, adjoint=False):
+    """Packed row-split weight of the heads ``convs`` (one separable convolution, see head_stage) for ``desc``, cached on the
+    first head under "ysplit" (forward) / "ysplit_adj" (``adjoint``: the feature gradient's operand) and repacked when any
+    head's weight changes.  ``cin``: the feature map's width (zero columns above the heads' own, autograd.padded_width);
+    ``rows``: zero rows up to that many output channels."""
+    tag, what = ("ysplit_adj", "packed head weight (adjoint)") if adjoint else ("ysplit", "packed head weight")
+    key = (tag, desc.dtype, cin) + tuple((c.weight._version, c.weight.data_ptr()) for c in convs)
+    cache = convs[0].__dict__.setdefault("_ir2rgb_packed", {})
+    hit = cache.get(tag)
+    if hit is None or hit[0] != key:
+        with torch.no_grad():
+            wy = _ysplit_weight(pad_dim(torch.cat([c.weight.detach().float() for c in convs], 0), 1, cin))
+            if rows is not None:
+                wy = pad_dim(wy, 0, rows)
+            hit = cache[tag] = (key, C.pack_weight(desc, wy.contiguous(), adjoint=adjoint))
+            if SC.ENABLED:
+                SC.produced(hit[1], what)
+    if SC.ENABLED:
+        SC.consumed(hit[1], what)
+    return hit[1]
 
 
 def head_stage(feat, convs, acts, mul=1.0):
@@ -423,31 +400,10 @@ def head_stage(feat, convs, acts, mul=1.0):
     n, _, h, w = feat.shape
     desc = C.make_desc(tuple(feat.shape), (cout * kh + 7) // 8 * 8, (1, kw), 1, (0, kw // 2), C.PAD_REFLECT, feat.dtype,
                        out_f32=True)
-    holder = convs[0]
-    key = ("ysplit", desc.dtype, feat.shape[1]) + tuple((c.weight._version, c.weight.data_ptr()) for c in convs)
-    cache = holder.__dict__.setdefault("_ir2rgb_packed", {})
-    hit = cache.get("ysplit")
-    if hit is None or hit[0] != key:
-        with torch.no_grad():
-            wcat = torch.cat([c.weight.detach().float() for c in convs], 0)
-            if wcat.shape[1] != feat.shape[1]:      # the feature map runs at a padded width (autograd.padded_width)
-                wcat = torch.cat([wcat, wcat.new_zeros((wcat.shape[0], feat.shape[1] - wcat.shape[1]) + tuple(wcat.shape[2:]))], 1)
-            cache["ysplit"] = (key, C.pack_weight(desc, _ysplit_weight(wcat).contiguous()))
-            if SC.ENABLED:
-                SC.produced(cache["ysplit"][1], "packed head weight")
-    wp = cache["ysplit"][1]
-    if SC.ENABLED:
-        SC.consumed(wp, "packed head weight")
-    t, _ = C.conv2d_fwd(desc, feat, wp, None, want_stats=False)
+    t, _ = C.conv2d_fwd(desc, feat, head_weight(convs, desc, feat.shape[1]), None, want_stats=False)
     bias = torch.cat([c.bias.detach().float() for c in convs], 0).contiguous()
     out = torch.empty((n, cout, h, w), dtype=torch.float32, device=feat.device)
-    packed_acts = 0
-    for i, a in enumerate(acts):
-        packed_acts |= (a & 15) << (4 * i)
-    with _lib.on_device(feat):
-        rc = _lib.lib().ir2rgb_head_finish(t, bias, out, n, h, w, cout, kh, desc.Cout, kh // 2,
-                                           packed_acts, float(mul), _lib.current_stream(feat))
-    _lib.check(rc, "head_finish")
+    _lib.launch("ir2rgb_head_finish", feat, t, bias, out, n, h, w, cout, kh, desc.Cout, kh // 2, pack_acts(acts), float(mul))
     return out
 
 
@@ -458,10 +414,7 @@ def warp_blend(raw, prev, flow, weight, want_warp=False):
     n, _, h, w = raw.shape
     out = torch.empty_like(raw)
     warp = torch.empty_like(raw) if want_warp else None
-    with _lib.on_device(raw):
-        rc = _lib.lib().ir2rgb_warp_blend_fwd(raw, prev, flow, weight, out, warp, n,
-                                              prev.shape[1], h, w, _lib.current_stream(raw))
-    _lib.check(rc, "warp_blend_fwd")
+    _lib.launch("ir2rgb_warp_blend_fwd", raw, raw, prev, flow, weight, out, warp, n, prev.shape[1], h, w)
     return (out, warp) if want_warp else out
 
 

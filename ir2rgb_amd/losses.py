@@ -146,10 +146,7 @@ class _FusedLossFn(Function):
         out = torch.zeros(nslots, dtype=torch.float32, device=dev)
         partial = torch.empty(lib.ir2rgb_loss_partial_elems(), dtype=torch.float32, device=dev)
         arr = _build_items(terms, tensors, None)
-        with _lib.on_device(tensors[0]):
-            rc = lib.ir2rgb_loss_multi_fwd(arr, len(terms), dt, partial.data_ptr(),
-                                           out.data_ptr(), _lib.current_stream(tensors[0]))
-        _lib.check(rc, "loss_multi_fwd")
+        _lib.launch("ir2rgb_loss_multi_fwd", tensors[0], arr, len(terms), dt, partial.data_ptr(), out.data_ptr())
         ctx.terms, ctx.dt = terms, dt
         ctx.save_for_backward(*tensors)
         return out
@@ -174,10 +171,7 @@ class _FusedLossFn(Function):
         if any(g is not None for g in grads):
             gout = gout.contiguous().float()
             arr = _build_items(terms, tensors, grads)
-            with _lib.on_device(gout):
-                rc = _lib.lib().ir2rgb_loss_multi_bwd(arr, len(terms), ctx.dt, gout.data_ptr(),
-                                                      _lib.current_stream(gout))
-            _lib.check(rc, "loss_multi_bwd")
+            _lib.launch("ir2rgb_loss_multi_bwd", gout, arr, len(terms), ctx.dt, gout.data_ptr())
         res = [None] * len(tensors)
         for p, g in zip(pos, grads):
             res[p] = g

@@ -189,11 +189,8 @@ def video_metrics(orig_u8, pred_u8, data_range="reference"):
     N, H, W = orig_u8.shape[:3]
     given = _range(data_range, N, dev)
     out = torch.empty((N, 3), dtype=torch.float64, device=dev)
-    with _lib.on_device(out):
-        stream = _lib.current_stream(out)
-        ws = _workspace(dev, stream, N, H, W)
-        rc = _lib.lib().ir2rgb_video_metrics_u8(orig_u8, pred_u8, given, out, ws, ws.numel() * 8, N, H, W, stream)
-    _lib.check(rc, "video_metrics_u8")
+    ws = _workspace(dev, _lib.current_stream(out), N, H, W)
+    _lib.launch("ir2rgb_video_metrics_u8", out, orig_u8, pred_u8, given, out, ws, ws.numel() * 8, N, H, W)
     return out
 
 

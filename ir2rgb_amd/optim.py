@@ -133,11 +133,8 @@ class FusedAdam:
             self._copied[k] = torch.cuda.Event()
         self._copied[k].record()
         self.step_count += 1
-        with _lib.on_device(self.exp_avg):
-            rc = _lib.lib().ir2rgb_adam_step(self._rows_dev.data_ptr(), self._blocks.data_ptr(),
-                                             self._blocks.shape[0], self.lr, self.betas[0], self.betas[1], self.eps,
-                                             self.step_count, _lib.current_stream(self.exp_avg))
-        _lib.check(rc, "adam_step")
+        _lib.launch("ir2rgb_adam_step", self.exp_avg, self._rows_dev.data_ptr(), self._blocks.data_ptr(),
+                    self._blocks.shape[0], self.lr, self.betas[0], self.betas[1], self.eps, self.step_count)
         # the kernel wrote the parameters behind autograd's back: bump their version counters so that
         # caches keyed on them (the packed MFMA weights of ir2rgb_amd.layers) are refreshed
         torch.autograd.graph.increment_version(self.params)

@@ -56,10 +56,7 @@ class StagePlan:
         self.fused = bool(fused_bn and cout % 64 == 0 and self.rows // G <= L.FUSED_BN_MAX_ROWS)
         self.act = spec["act"]
         self.ws_bytes = C.fwd_workspace_bytes(d)
-        nblk = _lib.lib().ir2rgb_bn_bwd_blocks(self.npix, cout)
-        if nblk < 0:
-            _lib.check(nblk, "bn_bwd_blocks")
-        self.nblk = nblk
+        self.nblk = _lib.query("ir2rgb_bn_bwd_blocks", self.npix, cout)
         self.dgrads = {}           # built at the first backward, per active batch size: dgrad_geometry + (workspace bytes,)
         self.wdesc = self.wshape = self.wgrad_ws = None
 
@@ -125,11 +122,8 @@ class StagePlan:
         self.wdesc = d = C.make_desc(self.x_shape, self.cout, spec["k"], spec["stride"], spec["pad"], spec["pad_mode"], self.tdtype,
                                      bool(spec["transposed"]), spec.get("output_padding", 0))
         self.wshape = (d.Cin, d.Cout, d.kh, d.kw) if d.transposed else (d.Cout, d.Cin, d.kh, d.kw)
-        lib = _lib.lib()
-        n, na = lib.ir2rgb_conv2d_wgrad_workspace_elems(d), lib.ir2rgb_conv2d_wgrad_acc_workspace_elems(d)
-        if n < 0 or na < 0:
-            _lib.check(int(min(n, na)), "conv2d_wgrad_workspace_elems")
-        self.wgrad_ws = (n, na)
+        self.wgrad_ws = (_lib.query("ir2rgb_conv2d_wgrad_workspace_elems", d),
+                         _lib.query("ir2rgb_conv2d_wgrad_acc_workspace_elems", d))
 
     def backward(self, ctx, gz):
         A = _autograd()

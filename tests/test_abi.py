@@ -89,6 +89,14 @@ def test_fastcall_bindings_cover_the_prototypes_and_agree_with_ctypes(built_lib)
         fast.ir2rgb_bn_bwd(*args[:11], 1 << 40, 0, 1, None)
 
 
+def test_query_returns_the_count_and_raises_under_the_entry_name(built_lib):
+    """_lib.query: the raw entry's answer, and a ValueError naming the entry for a channel count ir2rgb_bn_bwd_blocks
+    refuses up front (csrc/backward.hip: C < 64)."""
+    assert _lib.query("ir2rgb_bn_bwd_blocks", 2048, 1024) == _lib.lib().ir2rgb_bn_bwd_blocks(2048, 1024) > 0
+    with pytest.raises(ValueError, match="bn_bwd_blocks"):
+        _lib.query("ir2rgb_bn_bwd_blocks", 100, 63)
+
+
 def test_out_shape_matches_oracle(built_lib):
     from ir2rgb_amd.ext import correlation_cuda
     from oracle import ops

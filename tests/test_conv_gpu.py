@@ -294,7 +294,7 @@ def test_head_1x7_pass_row_segment_kernel(dev, dtype, N, Cin, H, W, Cout):
 @pytest.mark.parametrize("N,H,W,Cout", [(1, 40, 100, 128), (2, 9, 33, 64), (1, 64, 128, 64), (1, 5, 31, 128), (1, 256, 96, 128)])
 def test_first_layer_7x1_pass_column_tile_kernel(dev, dtype, N, H, W, Cout):
     """conv7x1_col_kernel (the 7x1 pass of the generators' first layers, reference networks.py:141,:150,:253-255 as
-    layers.first_stage evaluates them: 64 x-expanded channels, reflection pad 3 in y): against torch's fp32 convolution on
+    autograd.ConvStageFn evaluates them: 64 x-expanded channels, reflection pad 3 in y): against torch's fp32 convolution on
     the same half-rounded operands, with bias, with BatchNorm partial sums; ragged tiles on both axes, images lower than a
     tile, more tiles than persistent workgroups (256 x 96: 96 tiles... and 40 x 100), operands in NaN bands, outputs in canary bands."""
     from ir2rgb_amd import conv as C

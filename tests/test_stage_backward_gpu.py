@@ -486,3 +486,19 @@ def test_bn_backward_kernels_vs_autograd(dev, dtype, tol, C, H, W, act):
     _, dg2, db2 = A.bn_bwd(gz, y, scale, shift, mean, invstd, act, params=(dgamma.clone(), dbeta.clone()))
     torch.testing.assert_close(dg2, 2 * dgamma, rtol=1e-6, atol=1e-6)
     torch.testing.assert_close(db2, 2 * dbeta, rtol=1e-6, atol=1e-6)
+
+
+def test_launch_helper_refuses_and_launches(dev):
+    """_lib.launch: an argument set the library refuses before any launch (npix=100, ch=63 on a 64-float tensor, as in
+    test_abi.py) raises under the entry's own name; a valid launch of ir2rgb_bn_apply writes what layers.bn_apply does."""
+    from ir2rgb_amd import _lib, conv as C, layers as L
+    t = torch.zeros(64, device=dev)
+    with pytest.raises(ValueError, match="bn_bwd"):
+        _lib.launch("ir2rgb_bn_bwd", t, t, t, t, t, t, t, t, t, t, t, 100, 63, 0, 1)
+    g = torch.Generator().manual_seed(3)
+    x = torch.randn(1, 64, 2, 3, generator=g).to(dev).half().contiguous(memory_format=torch.channels_last)
+    scale, shift = torch.randn(64, generator=g).to(dev), torch.randn(64, generator=g).to(dev)
+    want = L.bn_apply(x, scale, shift, L.ACT_RELU)
+    got = torch.full_like(want, float("nan"))
+    assert _lib.launch("ir2rgb_bn_apply", x, x, scale, shift, None, None, got, 6, 64, L.ACT_RELU, C.F16) is None
+    assert C.is_nhwc(got) and torch.equal(got.view(torch.int16), want.view(torch.int16))
