@@ -462,6 +462,32 @@ int ir2rgb_video_metrics_tile(int which);
 int ir2rgb_video_metrics_u8(const uint8_t *orig, const uint8_t *pred, const double *range, double *out, void *workspace,
                             long workspace_bytes, int N, int H, int W, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Frame scaling (frame_scale.hip): the loader's Image.resize(..., BICUBIC), crop and flip (reference
+ * data/transform.py:64-113) on uint8 frames, equal to Pillow's 8-bit resampler byte for byte.
+ *   src [N][Hs][Ws][C] uint8, C in {1, 3}  --scale-->  [new_h][new_w]  --crop-->  rows [crop_y, crop_y + Hc),
+ *   columns [crop_x, crop_x + Wc)  --flip (0 / 1): columns mirrored-->  dst uint8 [N][Hc][Wc][C] (dst_f32 0) or fp32
+ *   [N][C][Hc][Wc] = (float(v) / 255 - 0.5) / 0.5 with correctly rounded operations (dst_f32 1), the value
+ *   ir2rgb_frame_push_u8 files for that byte.
+ * Tables (device, int32), one pair per axis that changes size, computed on the host in double in Pillow's operation
+ * order (ir2rgb_amd/transform.py: resample_coeffs): bounds [out][2] = {xmin, xmax}, coef [out][ksize] with 22
+ * fraction bits, ksize = 2 * ceil(2 * max(in / out, 1)) + 1.  An axis whose size does not change takes NULL tables and
+ * ksize 0: that pass copies.  Per pass out = clamp((2^21 + sum_{x < xmax} px[xmin + x] * coef[x]) >> 22, 0, 255) in
+ * int32; the horizontal pass runs first and is rounded to uint8.  Two launches, integers only but for the fp32 store.
+ * The workspace is the caller's: ir2rgb_frame_scale_workspace_bytes(...) bytes (negative for invalid sizes) -- the
+ * horizontally scaled source rows that the kept output rows read, kept columns only.  It is fully written before it
+ * is read.  Rows of Wc * C bytes that are a multiple of 4 with 4-byte aligned workspace and dst take dword accesses in
+ * the vertical pass, everything else the scalar form.  No buffer may alias another.
+ * IR2RGB_EINVAL: NULL src / dst / workspace, sizes or crop window out of range, workspace too small, tables missing,
+ * given for an unchanged axis, or of another ksize; IR2RGB_EALIGN: tables or an fp32 dst off a 4-byte boundary.
+ * ------------------------------------------------------------------------------------------ */
+long ir2rgb_frame_scale_workspace_bytes(int N, int C, int Hs, int Ws, int new_h, int new_w, int crop_y, int crop_x, int Hc,
+                                        int Wc);
+int ir2rgb_frame_scale_u8(const uint8_t *src, void *dst, uint8_t *workspace, long workspace_bytes, const int *xbounds,
+                          const int *xcoef, int xksize, const int *ybounds, const int *ycoef, int yksize, int N, int C, int Hs,
+                          int Ws, int new_h, int new_w, int crop_y, int crop_x, int Hc, int Wc, int flip, int dst_f32,
+                          void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,7 +6,8 @@ first use and its absence is an error (there is no CPU fallback).
 """
 __version__ = "0.1.0"
 
-__all__ = ["VideoTranslator", "VideoScore", "video_metrics", "ssim_reference"]
+__all__ = ["VideoTranslator", "VideoScore", "video_metrics", "ssim_reference", "FrameScaler", "img_params", "resample_coeffs",
+           "resize_reference"]
 
 
 def __getattr__(name):
@@ -17,4 +18,7 @@ def __getattr__(name):
     if name in ("VideoScore", "video_metrics", "ssim_reference"):
         from . import metrics
         return getattr(metrics, name)
+    if name in ("FrameScaler", "img_params", "resample_coeffs", "resize_reference"):
+        from . import transform
+        return getattr(transform, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -18,7 +18,10 @@ batch statistics.  What this module adds is what a frame loop needs around that 
 * one HIP-graph replay per frame: after two eager steps at a shape, every step that is not the first of its sequence is
   one captured graph (push, coarser pyramid levels, every scale's generator with its two branch streams, finish per
   scale) working on the static histories.  The first step of a sequence stays eager (``use_raw_only`` and the history
-  initialisation differ there); ``reset()`` keeps the graph.
+  initialisation differ there); ``reset()`` keeps the graph;
+* camera-size frames: with ``source_size`` (or a ``FrameScaler``) uint8 frames of the camera's size are scaled, cropped and
+  flipped on the device exactly as the reference's loader does with Pillow (ir2rgb_amd.transform, csrc/frame_scale.hip)
+  into the staging buffer ``ir2rgb_frame_push_u8`` reads; the two launches are part of the captured step.
 
 There is no CPU path: a CPU device raises, as everywhere in this package.
 """
@@ -134,11 +137,19 @@ class VideoTranslator:
     they do in the reference (its modules are never put into eval mode).  ``"running"`` puts the generators into
     ``.eval()``: the frozen-statistics kernels, nothing advances.  Either mode is set on the modules handed in.
 
+    ``source_size=(Hs, Ws)``: uint8 frames of that size (``push``, ``translate``, ``evaluate`` and their ``real_rgb`` /
+    ``targets``) are first brought to the network's size by ``ir2rgb_amd.transform.FrameScaler`` -- Pillow's bicubic
+    ``resize`` to ``(height, width)``, or, with ``scale_opt`` (the reference's ``dataset_scale`` / ``dataset_crop`` /
+    ``load_size`` / ``fine_size`` / ``is_train`` / ``flip`` options, drawn once here, ``scale_rng`` as in
+    ``transform.img_params``), the scale, crop and flip the reference's loader would apply; ``scaler=`` hands in a
+    ``FrameScaler`` built elsewhere (the translator works on a ``clone()`` of it: same tables, a workspace of its own).  Either way its result size must be ``(height, width)``.  Frames that already have the
+    network's size, and every fp32 frame, are taken as before.
+
     Nothing requires grad and no parameter or packed weight is written.  Returned tensors are the caller's own (copies of
     the static buffers the graph works on)."""
 
     def __init__(self, device, height, width, netG=None, checkpoint_dir=None, which_epoch="latest", first_frame="zeros",
-                 norm_stats="batch", use_graph=True, **opt):
+                 norm_stats="batch", use_graph=True, source_size=None, scaler=None, scale_opt=None, scale_rng=None, **opt):
         device = torch.device(device)
         if device.type != "cuda":
             raise ValueError("VideoTranslator runs on an AMD GPU only (ir2rgb_amd has no CPU fallback)")
@@ -180,7 +191,33 @@ class VideoTranslator:
             g.compute_dtype = o["compute_dtype"]
             g.train(norm_stats == "batch")
         self.seq = SequenceState(self.tG)
+        self.scaler = self.scaler_rgb = None
+        if scaler is not None or source_size is not None:
+            self._set_scaler(scaler, source_size, scale_opt, scale_rng)
+        elif scale_opt is not None:
+            raise ValueError("VideoTranslator: scale_opt needs source_size")
         self._alloc()
+
+    def _set_scaler(self, scaler, source_size, scale_opt, scale_rng):
+        from .transform import FrameScaler
+        C = self.opt["input_nc"]
+        if scaler is None:
+            src_hw = (int(source_size[0]), int(source_size[1]))
+            if scale_opt is not None:
+                scaler = FrameScaler.from_options(self.device, src_hw, C, rng=scale_rng, **scale_opt)
+            else:
+                scaler = FrameScaler(self.device, src_hw, C, new_size=(self.W, self.H))
+        elif scale_opt is not None or (source_size is not None and tuple(source_size) != scaler.src_hw):
+            raise ValueError("VideoTranslator: give scaler, or source_size with scale_opt, not both")
+        if scaler.channels != C or scaler.device != self.device:
+            raise ValueError(f"VideoTranslator: the scaler takes {scaler.channels}-channel frames on {scaler.device}, "
+                             f"input_nc={C} on {self.device} needed")
+        if scaler.out_hw != (self.H, self.W):
+            raise ValueError(f"VideoTranslator: the scaler's result is {scaler.out_hw}, the network takes {(self.H, self.W)}")
+        # private copies (the tables are shared, the workspaces are not): the captured step holds the address of its
+        # scaler's workspace, and nothing the caller does with the scaler handed in may touch that buffer
+        self.scaler = scaler.clone()
+        self.scaler_rgb = self.scaler if C == 3 else scaler.with_channels(3)
 
     @staticmethod
     def _build_generators(o):
@@ -207,6 +244,8 @@ class VideoTranslator:
         self.hist_B = [torch.zeros((self.tG - 1, 3, h, w), dtype=torch.float32, device=dev) for h, w in sizes]
         self.stage = {"u8": torch.zeros((self.H, self.W, C), dtype=torch.uint8, device=dev),
                       "f32": torch.zeros((C, self.H, self.W), dtype=torch.float32, device=dev)}
+        if self.scaler is not None:     # a camera-size frame waits here; the step scales it into stage["u8"]
+            self.stage["cam"] = torch.zeros((*self.scaler.src_hw, C), dtype=torch.uint8, device=dev)
         self.image = torch.zeros((self.H, self.W, 3), dtype=torch.uint8, device=dev)
         self._graphs = {}               # staging kind -> CUDAGraph of one non-first step
         self._eager_steps = 0
@@ -252,6 +291,8 @@ class VideoTranslator:
             if frame.dim() == 2:
                 frame = frame.unsqueeze(-1)
             want = (self.H, self.W, channels)
+            if self.scaler is not None and tuple(frame.shape) == (*self.scaler.src_hw, channels):
+                want = tuple(frame.shape)                   # camera size: scaled on the device before it is used
         elif frame.dtype == torch.float32:
             want = (channels, self.H, self.W)
         else:
@@ -260,21 +301,30 @@ class VideoTranslator:
             raise ValueError(f"{what}: shape {tuple(frame.shape)} given, {want} expected")
         return frame.to(self.device).contiguous()
 
+    def _camera_size(self, frame):
+        return self.scaler is not None and frame.dtype == torch.uint8 and tuple(frame.shape[:2]) == self.scaler.src_hw
+
+    def _rgb_frame(self, frame, what):
+        """An RGB frame (first real frames, targets) at the network's size: camera-size uint8 frames are scaled."""
+        frame = self._as_frame(frame, 3, what)
+        return self.scaler_rgb(frame) if self._camera_size(frame) else frame
+
     def push(self, ir_u8, real_rgb_u8=None):
-        """One input frame (uint8 [H,W,C]; a normalised fp32 [C,H,W] tensor is taken too).  Returns the translated frame
-        as a uint8 [H,W,3] device tensor, or None while fewer than tG input frames have been pushed.  With
-        ``first_frame="real"`` the first tG-1 calls of a sequence also take that frame's real RGB image."""
+        """One input frame (uint8 [H,W,C], or [Hs,Ws,C] with ``source_size``; a normalised fp32 [C,H,W] tensor is taken
+        too).  Returns the translated frame as a uint8 [H,W,3] device tensor, or None while fewer than tG input frames have
+        been pushed.  With ``first_frame="real"`` the first tG-1 calls of a sequence also take that frame's real RGB image."""
         with torch.no_grad():
             frame = self._as_frame(ir_u8, self.opt["input_nc"], "push")
             warming = self.seq.warming
             if self.first_frame == "real" and warming and not self.seq.started:
                 if real_rgb_u8 is None:
                     raise ValueError("first_frame='real': the first tG-1 frames of a sequence need real_rgb_u8")
-                self._push_levels(self._as_frame(real_rgb_u8, 3, "push(real_rgb_u8)"), self.hist_B)
+                self._push_levels(self._rgb_frame(real_rgb_u8, "push(real_rgb_u8)"), self.hist_B)
+            camera = self._camera_size(frame)
             if not self.seq.push():
-                self._push_levels(frame, self.hist_A)
+                self._push_levels(self.scaler(frame, out=self.stage["u8"]) if camera else frame, self.hist_A)
                 return None
-            kind = "u8" if frame.dtype == torch.uint8 else "f32"
+            kind = "cam" if camera else ("u8" if frame.dtype == torch.uint8 else "f32")
             self.stage[kind].copy_(frame)
             self._step(kind)
             return self.image.clone()
@@ -291,8 +341,9 @@ class VideoTranslator:
 
     def evaluate(self, frames, targets, real_rgb=None, data_range="reference"):
         """``translate(frames, real_rgb)`` scored against a ground-truth RGB track (reference scripts/ssim_metric.py):
-        output ``k`` is compared with ``targets[tG-1+k]`` -- ``targets`` is indexed like ``frames``, uint8 [H,W,3] each,
-        moved to the device if needed.  -> ``ir2rgb_amd.metrics.VideoScore``; its ``result()`` is the only host
+        output ``k`` is compared with ``targets[tG-1+k]`` -- ``targets`` is indexed like ``frames``, uint8 [H,W,3] each
+        (camera-size ones are scaled like the frames), moved to the device if needed.
+        -> ``ir2rgb_amd.metrics.VideoScore``; its ``result()`` is the only host
         synchronisation.  The scores are enqueued on the current stream after each step; the captured graph is the one
         ``translate`` replays.  ``data_range``: see ``ir2rgb_amd.metrics.video_metrics``."""
         from .metrics import VideoScore
@@ -303,7 +354,7 @@ class VideoTranslator:
             i = self.seq.output_frame(k)
             if i >= len(targets):
                 raise ValueError(f"evaluate: output {k} is scored against targets[{i}], {len(targets)} targets given")
-            score.add(self._as_frame(targets[i], 3, "evaluate(targets)"), out)
+            score.add(self._rgb_frame(targets[i], "evaluate(targets)"), out)
         return score
 
     def inference(self, input_A, input_B=None):
@@ -331,6 +382,9 @@ class VideoTranslator:
     # ------------------------------------------------------------------ one frame
     def _step_body(self, kind, first):
         """push + generate_frame_infer for every scale (generator.py:191-195, :197-215) on the static buffers."""
+        if kind == "cam":
+            self.scaler(self.stage["cam"], out=self.stage["u8"])
+            kind = "u8"
         self._push_levels(self.stage[kind], self.hist_A)
         use_raw_only = self.first_frame == "zeros" and first            # no_first_img and is_first_frame
         feat = flow_feat = None

@@ -7,8 +7,9 @@ bench.py configuration), 50 frames after warm-up, three ways on the same weights
   (c) graph     VideoTranslator(use_graph=True): one HIP-graph replay per frame
 
 Each figure: device events around the 50 frames and one synchronise; the three ways alternate over ``--rounds`` rounds and
-the median round is reported (frames/s, ms/frame).  The two frame-I/O kernels and the score of one frame
-(ir2rgb_amd.metrics.video_metrics) are timed alone beside the bytes they move (computed from the shapes).  Needs the GPU;
+the median round is reported (frames/s, ms/frame).  The two frame-I/O kernels, the score of one frame
+(ir2rgb_amd.metrics.video_metrics) and the two passes of frame scaling (ir2rgb_amd.transform.FrameScaler, 512x640x3 ->
+832x1024 and -> 416x512) are timed alone beside the bytes they move (computed from the shapes).  Needs the GPU;
 prints one JSON document and writes it to ``--out``.
 
     python tools/bench_infer.py --out profiles/inference_512x1024.json
@@ -103,8 +104,39 @@ def kernel_times(dev, H, W, reps=200):
             ("video_metrics_u8 (one frame, three launches)", lambda: M.video_metrics(truth, frame), 2 * 2 * px)):
         us = many(f)
         res[name] = {"us_per_launch": round(us, 2), "bytes_moved": int(byts), "GB_per_s": round(byts / us / 1e3, 1)}
+    res.update(scale_times(dev, many))
     res["note"] = ("bytes_moved counts the in-place history shift (slots read and written) beside the frame itself: "
                    f"{px / 1e6:.2f} MB of bytes and {4 * px / 1e6:.2f} MB of fp32 per full-size frame")
+    return res
+
+
+def scale_times(dev, many, hs=512, ws=640, C=3):
+    """FrameScaler (two launches per call) at the camera size of the KAIST frames: per target size and output form one row
+    with the bytes each pass moves, computed from the shapes -- the horizontal pass reads the source rows the kept output
+    rows need and writes them scaled into the workspace, the vertical pass reads the workspace once (the overlapping taps
+    of neighbouring output rows are re-reads of lines just fetched) and writes the result.  The entry point is called
+    directly (no Python wrapper in the timed loop).  It enqueues both launches, so ``us_per_call`` and ``GB_per_s`` are
+    figures of the pair; the time of each pass comes from a kernel trace of ``--kernels-only`` (scale_h_kernel /
+    scale_v_kernel rows), to be set against ``horizontal_pass_bytes`` / ``vertical_pass_bytes``."""
+    from ir2rgb_amd import _lib
+    from ir2rgb_amd.transform import FrameScaler
+    src = torch.randint(0, 256, (hs, ws, C), dtype=torch.uint8, device=dev)
+    res = {}
+    for H, W in ((832, 1024), (416, 512)):
+        sc = FrameScaler(dev, (hs, ws), C, (W, H))
+        rows = sc.workspace_bytes(1) // (W * C)
+        for normalised in (False, True):
+            out = sc(src, normalised=normalised)
+            h_bytes = rows * ws * C + rows * W * C
+            v_bytes = rows * W * C + H * W * C * (4 if normalised else 1)
+            (xb, xc, xk), (yb, yc, yk) = sc.x_tables, sc.y_tables
+            args = (src, out, sc._ws, sc.workspace_bytes(1), xb, xc, xk, yb, yc, yk, 1, *sc._geom, int(sc.flip), int(normalised),
+                    _lib.current_stream(src))
+            entry = _lib.lib().ir2rgb_frame_scale_u8
+            us = many(lambda: entry(*args))
+            res[f"frame_scale_u8 {hs}x{ws}x{C} -> {H}x{W} ({'fp32 planar' if normalised else 'uint8'}, two launches)"] = {
+                "us_per_call": round(us, 2), "horizontal_pass_bytes": int(h_bytes), "vertical_pass_bytes": int(v_bytes),
+                "bytes_moved": int(h_bytes + v_bytes), "GB_per_s": round((h_bytes + v_bytes) / us / 1e3, 1)}
     return res
 
 
@@ -116,6 +148,8 @@ def main():
     ap.add_argument("--height", type=int, default=512)
     ap.add_argument("--width", type=int, default=1024)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--kernels-only", action="store_true",
+                    help="only the frame-I/O, score and scaling kernels (short: the run to put under a kernel trace)")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_infer.py needs the GPU (there is nothing to measure without one)")
@@ -131,7 +165,7 @@ def main():
                                                 stderr=subprocess.DEVNULL).strip()
     except Exception:  # noqa: BLE001  (a snapshot without history)
         doc["commit"] = None
-    for name, ns in (("one scale, ngf 128", 1), ("two scales, ngf 128 / 64", 2)):
+    for name, ns in (() if a.kernels_only else (("one scale, ngf 128", 1), ("two scales, ngf 128 / 64", 2))):
         netG = build(ns, 128, dev)
         kw = dict(netG=netG, n_scales_spatial=ns, first_layer_gen_filters=128, first_frame="zeros", compute_dtype=torch.bfloat16)
         tr = {"eager": VideoTranslator(dev, H, W, use_graph=False, **kw), "graph": VideoTranslator(dev, H, W, use_graph=True, **kw)}
