@@ -8,17 +8,6 @@
 // Reductions are two-level and deterministic (per-block partial rows, then a finalize kernel).
 #include "common.h"
 
-static __device__ __forceinline__ float h2f(uint16_t h, int dt) {
-    if (dt == IR2RGB_BF16) return __uint_as_float(((uint32_t)h) << 16);
-    _Float16 v = __builtin_bit_cast(_Float16, h);
-    return (float)v;
-}
-static __device__ __forceinline__ uint16_t f2h(float f, int dt) {
-    if (dt == IR2RGB_BF16) { __bf16 h = (__bf16)f; return __builtin_bit_cast(uint16_t, h); }
-    _Float16 h = (_Float16)f;
-    return __builtin_bit_cast(uint16_t, h);
-}
-
 __device__ __forceinline__ void unpack8(const uint4 &v, float *f, int dt) {
     const uint32_t w[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll

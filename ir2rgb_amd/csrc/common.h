@@ -2,6 +2,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
+
+#include <type_traits>
 
 #include "../../include/ir2rgb_hip.h"
 
@@ -13,6 +16,41 @@ static inline int ir2rgb_launch_status() {
 }
 
 static inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
+
+// Calls f with the half element type (checked by the caller) as a compile-time constant, so that a launch site
+// names its kernel and its argument list once:  with_dtype(dtype, [&](auto dt) { K<dt.value><<<...>>>(...); });
+template <class F> static inline void with_dtype(int dtype, F &&f) {
+    if (dtype == IR2RGB_BF16) f(std::integral_constant<int, IR2RGB_BF16>{});
+    else f(std::integral_constant<int, IR2RGB_F16>{});
+}
+
+// An integer environment switch (IR2RGB_CONV3X3P, IR2RGB_CONV3X3P_SPLIT, IR2RGB_CONV_DOT): unset = dflt.  Callers keep
+// the value in a function-local static: the environment is read once per process.
+static inline int env_switch(const char *name, int dflt) {
+    const char *e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
+
+// What every convolution plan resolves first: the dense defaults of the channel-slice views, the byte extents of X and
+// of a half-precision Y (buffer resources want them below 2^31) and whether dtype is one of the two half types.
+struct ConvView {
+    int ldx, ldy;
+    long x_bytes, y_bytes;
+    bool half;
+};
+static inline ConvView conv_view(const ir2rgb_conv_desc *d) {
+    ConvView v{};
+    if (!d) return v;
+    v.ldx = d->ldx > 0 ? d->ldx : d->Cin; v.ldy = d->ldy > 0 ? d->ldy : d->Cout;
+    // (nothing of d is validated yet: the product of five ints fits 128 bits and is clamped to what a long holds)
+    auto bytes = [](int n, int h, int w, int ld) {
+        const __int128 b = (__int128)n * h * w * ld * 2, lim = (__int128)1 << 62;
+        return (long)(b > lim ? lim : b < -lim ? -lim : b);
+    };
+    v.x_bytes = bytes(d->N, d->Hin, d->Win, v.ldx); v.y_bytes = bytes(d->N, d->Hout, d->Wout, v.ldy);
+    v.half = d->dtype == IR2RGB_BF16 || d->dtype == IR2RGB_F16;
+    return v;
+}
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
@@ -39,6 +77,18 @@ static inline FastDiv make_fastdiv(unsigned d) {
     return f;
 }
 #ifdef __HIPCC__
+// half <-> float with the element type as a run-time value (the pointwise kernels)
+static __device__ __forceinline__ float h2f(uint16_t h, int dt) {
+    if (dt == IR2RGB_BF16) return __uint_as_float(((uint32_t)h) << 16);
+    _Float16 v = __builtin_bit_cast(_Float16, h);
+    return (float)v;
+}
+static __device__ __forceinline__ uint16_t f2h(float f, int dt) {
+    if (dt == IR2RGB_BF16) { __bf16 h = (__bf16)f; return __builtin_bit_cast(uint16_t, h); }
+    _Float16 h = (_Float16)f;
+    return __builtin_bit_cast(uint16_t, h);
+}
+
 __device__ __forceinline__ unsigned fdiv(unsigned n, FastDiv f) {
     if (f.sh == 32) return n;
     const unsigned t = __umulhi(f.m, n);

@@ -9,5 +9,5 @@ struct T7Geom {
     long nseg;                    // N * H * nsx
     unsigned x_bytes, w_bytes;
 };
-bool conv1x7_thin_plan(const ir2rgb_conv_desc *d, T7Geom *g);
+bool conv1x7_thin_plan(const ir2rgb_conv_desc *d, const ConvView &v, T7Geom *g);
 int conv1x7_thin_launch(const T7Geom &g, int dtype, int cin, const void *x, const void *wp, void *y, hipStream_t s);

@@ -163,21 +163,17 @@ conv1x7_thin_kernel(const uint16_t *__restrict__ X, const uint16_t *__restrict__
 // ----------------------------------------------------------------------------------------
 // host side (called from conv_mfma.hip)
 // ----------------------------------------------------------------------------------------
-bool conv1x7_thin_plan(const ir2rgb_conv_desc *d, T7Geom *g) {
+bool conv1x7_thin_plan(const ir2rgb_conv_desc *d, const ConvView &v, T7Geom *g) {
     if (d->transposed || d->kh != 1 || d->kw != 7 || d->stride_h != 1 || d->stride_w != 1) return false;
     if (d->pad_h != 0 || d->pad_w != 3 || d->pad_mode != 1 || !d->out_f32 || d->act != 0 || d->stats_per_sample) return false;
     if (d->Cout < 1 || d->Cout > 32 || (d->Cin != 64 && d->Cin != 128) || d->Win < 4 || d->Hout != d->Hin || d->Wout != d->Win) return false;
-    if (d->dtype != IR2RGB_BF16 && d->dtype != IR2RGB_F16) return false;
-    const int ldx = d->ldx > 0 ? d->ldx : d->Cin, ldy = d->ldy > 0 ? d->ldy : d->Cout;
-    if ((ldx & 7) || (d->ci_off & 7) || (ldy & 3) || (d->co_off & 3)) return false;
-    const long xb = (long)d->N * d->Hin * d->Win * ldx * 2;
-    if (xb >= (1L << 31)) return false;
+    if (!v.half || (v.ldx & 7) || (d->ci_off & 7) || (v.ldy & 3) || (d->co_off & 3) || v.x_bytes >= (1L << 31)) return false;
     *g = T7Geom{};
     g->N = d->N; g->H = d->Hin; g->W = d->Win; g->Cout = d->Cout;
-    g->ldx = ldx; g->ci_off = d->ci_off; g->ldy = ldy; g->co_off = d->co_off;
+    g->ldx = v.ldx; g->ci_off = d->ci_off; g->ldy = v.ldy; g->co_off = d->co_off;
     g->nsx = (d->Win + 127) / 128;
     g->nseg = (long)d->N * d->Hin * g->nsx;
-    g->x_bytes = (unsigned)xb; g->w_bytes = (unsigned)((long)d->Cout * d->Cin * 7 * 2);
+    g->x_bytes = (unsigned)v.x_bytes; g->w_bytes = (unsigned)((long)d->Cout * d->Cin * 7 * 2);
     return true;
 }
 
@@ -185,14 +181,10 @@ int conv1x7_thin_launch(const T7Geom &g, int dtype, int cin, const void *x, cons
     // 512 workgroups (two rounds of the chip): >= 8 segments each at 512 x 1024, which pays for the register-resident weights
     const long want = g.nseg < 512 ? g.nseg : 512;
     const unsigned grid = (unsigned)(want < 1 ? 1 : want);
-    const uint16_t *X = (const uint16_t *)x, *W = (const uint16_t *)wp;
-    float *Y = (float *)y;
-    if (dtype == IR2RGB_BF16) {
-        if (cin == 128) conv1x7_thin_kernel<IR2RGB_BF16, 128><<<grid, 256, 0, s>>>(X, W, Y, g);
-        else conv1x7_thin_kernel<IR2RGB_BF16, 64><<<grid, 256, 0, s>>>(X, W, Y, g);
-    } else {
-        if (cin == 128) conv1x7_thin_kernel<IR2RGB_F16, 128><<<grid, 256, 0, s>>>(X, W, Y, g);
-        else conv1x7_thin_kernel<IR2RGB_F16, 64><<<grid, 256, 0, s>>>(X, W, Y, g);
-    }
+    with_dtype(dtype, [&](auto dt) {
+        auto launch = [&](auto kernel) { kernel<<<grid, 256, 0, s>>>((const uint16_t *)x, (const uint16_t *)wp, (float *)y, g); };
+        if (cin == 128) launch(conv1x7_thin_kernel<dt.value, 128>);
+        else launch(conv1x7_thin_kernel<dt.value, 64>);
+    });
     return ir2rgb_launch_status();
 }

@@ -13,7 +13,7 @@ struct P3Geom {
 };
 
 // variant: 0 = not applicable, 1 = 2x64 px x 64 cout, 2 = 2x128 px x 128 cout, 3, 4 = split-K forms (allow_split only)
-int conv3x3p_plan(const ir2rgb_conv_desc *d, P3Geom *g, int *npt_out, bool allow_split = false);
+int conv3x3p_plan(const ir2rgb_conv_desc *d, const ConvView &v, P3Geom *g, int *npt_out, bool allow_split);
 long conv3x3p_workspace_bytes(int variant, const P3Geom &g);
 int conv3x3p_launch(int variant, const P3Geom &g, int dtype, const void *x, const void *wp, const float *bias, void *y,
                     float *stats, hipStream_t s, void *workspace, long workspace_bytes);

@@ -580,8 +580,7 @@ conv3x3_patch_kernel(const uint16_t *__restrict__ X, const uint16_t *__restrict_
 // host side (called from conv_mfma.hip)
 // ----------------------------------------------------------------------------------------
 static bool p3_enabled() {
-    static int v = -1;
-    if (v < 0) { const char *e = getenv("IR2RGB_CONV3X3P"); v = e ? atoi(e) : 1; }
+    static const int v = env_switch("IR2RGB_CONV3X3P", 1);
     return v != 0;
 }
 
@@ -596,15 +595,14 @@ static constexpr P3SplitCfg P3_SPLIT_CFGS[2] = {
     {4, 64, 4, 2},    // 4: 4x64 px x  64 cout, 4 multiplying waves (pipelined), two workgroups per tile
 };
 static int p3_split() {
-    static int v = -1;
-    if (v < 0) { const char *e = getenv("IR2RGB_CONV3X3P_SPLIT"); v = e ? atoi(e) : 1; }
+    static const int v = env_switch("IR2RGB_CONV3X3P_SPLIT", 1);
     return v;
 }
 
 // variant: 0 = not applicable, 1 = 2x64 px x 64 cout (8 loader waves), 2 = 2x128 px x 128 cout (4 loader waves),
 // 3, 4 (only with allow_split: the caller supplies a workspace) = P3_SPLIT_CFGS: several workgroups per tile splitting the
 // input channels -- 64 x 64-per-wave tiles for layers that have too few such tiles to fill the chip
-int conv3x3p_plan(const ir2rgb_conv_desc *d, P3Geom *g, int *npt_out, bool allow_split) {
+int conv3x3p_plan(const ir2rgb_conv_desc *d, const ConvView &view, P3Geom *g, int *npt_out, bool allow_split) {
     if (!p3_enabled() || d->transposed || d->kh != 3 || d->kw != 3 || d->stride_h != 1 || d->stride_w != 1) return 0;
     if (d->pad_h != d->pad_w || d->pad_h < 0 || d->pad_h > 2 || d->out_f32) return 0;
     if (d->pad_mode < 0 || d->pad_mode > 2) return 0;
@@ -615,10 +613,10 @@ int conv3x3p_plan(const ir2rgb_conv_desc *d, P3Geom *g, int *npt_out, bool allow
     // beats its zero-padded convolution + fold pass: 54 us against 62 + 19)
     const int min_cin = adj ? 128 : 256;
     if ((d->Cin % 64) || d->Cin < min_cin || (d->Cout % 64) || d->Hin < 4 || d->Win < 4 || d->N < 1) return 0;
-    if (d->dtype != IR2RGB_BF16 && d->dtype != IR2RGB_F16) return 0;
-    const int ldx = d->ldx > 0 ? d->ldx : d->Cin, ldy = d->ldy > 0 ? d->ldy : d->Cout;
+    if (!view.half) return 0;
+    const int ldx = view.ldx, ldy = view.ldy;
     if ((ldx & 7) || (d->ci_off & 7) || (ldy & 7) || (d->co_off & 7)) return 0;   // 16-byte loads and stores
-    const long xb = (long)d->N * d->Hin * d->Win * ldx * 2, wb = (long)d->Cout * d->Cin * 9 * 2;
+    const long xb = view.x_bytes, wb = (long)d->Cout * d->Cin * 9 * 2;
     if (xb >= (1L << 31) || wb >= (1L << 31)) return 0;
     auto waste = [](int n, int t) { return (double)(((n + t - 1) / t) * t) / n; };
     int variant = 0;
@@ -668,59 +666,42 @@ long conv3x3p_workspace_bytes(int variant, const P3Geom &g) {
     return ((tiles * 4 + 4095) & ~4095L) + tiles * c.split * (c.ncw * 4L * 4 * 4 * 64) * 4;
 }
 
-template <int DT, int TCO, int NCW, int PIPE, int SPLIT, int TR>
-static void p3_launch_split(bool adj, unsigned grid, const uint16_t *X, const uint16_t *W, const float *bias, uint16_t *Y,
-                            float *stats, const P3Geom &g, unsigned *tickets, float *partials, hipStream_t s) {
-    if (adj) conv3x3_patch_kernel<DT, 64, TCO, NCW, 4, PIPE, 1, SPLIT, TR><<<grid, (NCW + 4) * 64, 0, s>>>(X, W, bias, Y, stats, g, tickets, partials);
-    else conv3x3_patch_kernel<DT, 64, TCO, NCW, 4, PIPE, 0, SPLIT, TR><<<grid, (NCW + 4) * 64, 0, s>>>(X, W, bias, Y, stats, g, tickets, partials);
-}
-
-template <int DT>
-static void p3_launch_split_variant(int variant, bool adj, unsigned grid, const uint16_t *X, const uint16_t *W, const float *bias,
-                                    uint16_t *Y, float *stats, const P3Geom &g, unsigned *tickets, float *partials, hipStream_t s) {
-    if (variant == 3) p3_launch_split<DT, 128, 4, 1, 2, 2>(adj, grid, X, W, bias, Y, stats, g, tickets, partials, s);
-    else p3_launch_split<DT, 64, 4, 1, 2, 4>(adj, grid, X, W, bias, Y, stats, g, tickets, partials, s);
-}
+// The compiled forms: tile TR x TW pixels x TCO channels, NCW multiplying and NLW staging waves, SPLIT workgroups per tile.
+template <int TW, int TCO, int NCW, int NLW, int PIPE, int ADJ, int SPLIT = 1, int TR = 2> struct P3Form {};
 
 int conv3x3p_launch(int variant, const P3Geom &g, int dtype, const void *x, const void *wp, const float *bias, void *y,
                     float *stats, hipStream_t s, void *workspace, long workspace_bytes) {
-    const uint16_t *X = (const uint16_t *)x, *W = (const uint16_t *)wp;
-    uint16_t *Yp = (uint16_t *)y;
     const int npt = g.N * g.nty * g.ntx;
-    const bool adj = g.pad_mode == 2;
+    unsigned *tickets = nullptr;
+    float *partials = nullptr;
     if (variant >= 3) {
         if (!workspace || workspace_bytes < conv3x3p_workspace_bytes(variant, g) || ((uintptr_t)workspace & 15)) return IR2RGB_EINVAL;
-        const P3SplitCfg &c = P3_SPLIT_CFGS[variant - 3];
-        const long tiles = (long)npt * (g.Cout / c.tco);
-        unsigned *tickets = (unsigned *)workspace;
-        float *partials = (float *)((char *)workspace + ((tiles * 4 + 4095) & ~4095L));
-        const unsigned grid = (unsigned)(tiles * c.split);
-        if (dtype == IR2RGB_BF16) p3_launch_split_variant<IR2RGB_BF16>(variant, adj, grid, X, W, bias, Yp, stats, g, tickets, partials, s);
-        else p3_launch_split_variant<IR2RGB_F16>(variant, adj, grid, X, W, bias, Yp, stats, g, tickets, partials, s);
-        return ir2rgb_launch_status();
+        const long tiles = (long)npt * (g.Cout / P3_SPLIT_CFGS[variant - 3].tco);
+        tickets = (unsigned *)workspace;
+        partials = (float *)((char *)workspace + ((tiles * 4 + 4095) & ~4095L));
     }
-    if (variant == 2) {
-        const unsigned grid = (unsigned)(npt * (g.Cout / 128));
-        if (adj) {
-            if (dtype == IR2RGB_BF16) conv3x3_patch_kernel<IR2RGB_BF16, 128, 128, 8, 4, 0, 1><<<grid, 768, 0, s>>>(X, W, bias, Yp, stats, g);
-            else conv3x3_patch_kernel<IR2RGB_F16, 128, 128, 8, 4, 0, 1><<<grid, 768, 0, s>>>(X, W, bias, Yp, stats, g);
-        } else {
-            // (the fully pipelined form at this tile needs 2 x (MI + NI) fragment registers more than the 168 the 12-wave
-            // workgroup leaves a wave: 8 VGPRs spilled.  PIPE = 2: weights double-buffered, pixel fragments refilled column
-            // by column)
-            if (dtype == IR2RGB_BF16) conv3x3_patch_kernel<IR2RGB_BF16, 128, 128, 8, 4, 2, 0><<<grid, 768, 0, s>>>(X, W, bias, Yp, stats, g);
-            else conv3x3_patch_kernel<IR2RGB_F16, 128, 128, 8, 4, 2, 0><<<grid, 768, 0, s>>>(X, W, bias, Yp, stats, g);
-        }
-    } else {
-        // software-pipelined, forward and reflect-adjoint alike (the adjoint's border operands are prefetched into registers)
-        const unsigned grid = (unsigned)(npt * (g.Cout / 64));
-        if (adj) {
-            if (dtype == IR2RGB_BF16) conv3x3_patch_kernel<IR2RGB_BF16, 64, 64, 4, 8, 1, 1><<<grid, 768, 0, s>>>(X, W, bias, Yp, stats, g);
-            else conv3x3_patch_kernel<IR2RGB_F16, 64, 64, 4, 8, 1, 1><<<grid, 768, 0, s>>>(X, W, bias, Yp, stats, g);
-        } else {
-            if (dtype == IR2RGB_BF16) conv3x3_patch_kernel<IR2RGB_BF16, 64, 64, 4, 8, 1, 0><<<grid, 768, 0, s>>>(X, W, bias, Yp, stats, g);
-            else conv3x3_patch_kernel<IR2RGB_F16, 64, 64, 4, 8, 1, 0><<<grid, 768, 0, s>>>(X, W, bias, Yp, stats, g);
-        }
+    auto launch = [&]<int TW, int TCO, int NCW, int NLW, int PIPE, int ADJ, int SPLIT, int TR>(P3Form<TW, TCO, NCW, NLW, PIPE, ADJ, SPLIT, TR>) {
+        const unsigned grid = (unsigned)((long)npt * (g.Cout / TCO) * SPLIT);
+        with_dtype(dtype, [&](auto dt) {
+            conv3x3_patch_kernel<dt.value, TW, TCO, NCW, NLW, PIPE, ADJ, SPLIT, TR><<<grid, (NCW + NLW) * 64, 0, s>>>(
+                (const uint16_t *)x, (const uint16_t *)wp, bias, (uint16_t *)y, stats, g, tickets, partials);
+        });
+    };
+    // variants 1, 3 and 4 are software-pipelined, forward and reflect-adjoint alike (the adjoint's border operands are
+    // prefetched into registers).  Variant 2: the fully pipelined form at this tile needs 2 x (MI + NI) fragment registers
+    // more than the 168 the 12-wave workgroup leaves a wave (8 VGPRs spilled).  PIPE = 2: weights double-buffered, pixel
+    // fragments refilled column by column
+    constexpr auto form = [](int variant, bool adjoint) { return variant * 2 + (adjoint ? 1 : 0); };
+    switch (form(variant, g.pad_mode == 2)) {
+        case form(1, false): launch(P3Form<64, 64, 4, 8, 1, 0>{}); break;
+        case form(1, true):  launch(P3Form<64, 64, 4, 8, 1, 1>{}); break;
+        case form(2, false): launch(P3Form<128, 128, 8, 4, 2, 0>{}); break;
+        case form(2, true):  launch(P3Form<128, 128, 8, 4, 0, 1>{}); break;
+        case form(3, false): launch(P3Form<64, 128, 4, 4, 1, 0, 2, 2>{}); break;
+        case form(3, true):  launch(P3Form<64, 128, 4, 4, 1, 1, 2, 2>{}); break;
+        case form(4, false): launch(P3Form<64, 64, 4, 4, 1, 0, 2, 4>{}); break;
+        case form(4, true):  launch(P3Form<64, 64, 4, 4, 1, 1, 2, 4>{}); break;
+        default: return IR2RGB_EINVAL;      // conv3x3p_plan makes no other variant
     }
     return ir2rgb_launch_status();
 }

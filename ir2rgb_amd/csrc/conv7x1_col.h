@@ -8,7 +8,7 @@ struct C7Geom {
     int nty, ntx;                 // 8 x 32 pixel tiles per image
     unsigned x_bytes, y_bytes, w_bytes;
 };
-bool conv7x1_col_plan(const ir2rgb_conv_desc *d, C7Geom *g);
+bool conv7x1_col_plan(const ir2rgb_conv_desc *d, const ConvView &v, C7Geom *g);
 int conv7x1_col_tiles(const C7Geom &g);
 int conv7x1_col_launch(const C7Geom &g, int dtype, const void *x, const void *wp, const float *bias, void *y, float *stats,
                        hipStream_t s);

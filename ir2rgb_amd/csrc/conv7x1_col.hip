@@ -179,20 +179,17 @@ conv7x1_col_kernel(const uint16_t *__restrict__ X, const uint16_t *__restrict__ 
 // ----------------------------------------------------------------------------------------
 // host side (called from conv_mfma.hip)
 // ----------------------------------------------------------------------------------------
-bool conv7x1_col_plan(const ir2rgb_conv_desc *d, C7Geom *g) {
+bool conv7x1_col_plan(const ir2rgb_conv_desc *d, const ConvView &v, C7Geom *g) {
     if (d->transposed || d->kh != 7 || d->kw != 1 || d->stride_h != 1 || d->stride_w != 1) return false;
     if (d->pad_h != 3 || d->pad_w != 0 || d->pad_mode != 1 || d->out_f32 || d->act != 0 || d->stats_per_sample) return false;
     if (d->Cin != 64 || (d->Cout != 64 && d->Cout != 128) || d->Hin < 4 || d->Hout != d->Hin || d->Wout != d->Win) return false;
-    if (d->dtype != IR2RGB_BF16 && d->dtype != IR2RGB_F16) return false;
-    const int ldx = d->ldx > 0 ? d->ldx : d->Cin, ldy = d->ldy > 0 ? d->ldy : d->Cout;
-    if ((ldx & 7) || (d->ci_off & 7) || (ldy & 3) || (d->co_off & 3)) return false;
-    const long xb = (long)d->N * d->Hin * d->Win * ldx * 2, yb = (long)d->N * d->Hout * d->Wout * ldy * 2;
-    if (xb >= (1L << 31) || yb >= (1L << 31)) return false;
+    if (!v.half || (v.ldx & 7) || (d->ci_off & 7) || (v.ldy & 3) || (d->co_off & 3)) return false;
+    if (v.x_bytes >= (1L << 31) || v.y_bytes >= (1L << 31)) return false;
     *g = C7Geom{};
     g->N = d->N; g->H = d->Hin; g->W = d->Win; g->Cout = d->Cout;
-    g->ldx = ldx; g->ci_off = d->ci_off; g->ldy = ldy; g->co_off = d->co_off;
+    g->ldx = v.ldx; g->ci_off = d->ci_off; g->ldy = v.ldy; g->co_off = d->co_off;
     g->nty = (d->Hin + 7) / 8; g->ntx = (d->Win + 31) / 32;
-    g->x_bytes = (unsigned)xb; g->y_bytes = (unsigned)yb; g->w_bytes = (unsigned)((long)d->Cout * 64 * 7 * 2);
+    g->x_bytes = (unsigned)v.x_bytes; g->y_bytes = (unsigned)v.y_bytes; g->w_bytes = (unsigned)((long)d->Cout * 64 * 7 * 2);
     return true;
 }
 
@@ -203,14 +200,10 @@ int conv7x1_col_launch(const C7Geom &g, int dtype, const void *x, const void *wp
                        hipStream_t s) {
     const int tiles = g.N * g.nty * g.ntx;
     const unsigned grid = (unsigned)(tiles < 512 ? tiles : 512);      // persistent over tiles: weights loaded once per workgroup
-    const uint16_t *X = (const uint16_t *)x, *W = (const uint16_t *)wp;
-    uint16_t *Y = (uint16_t *)y;
-    if (dtype == IR2RGB_BF16) {
-        if (g.Cout == 128) conv7x1_col_kernel<IR2RGB_BF16, 128><<<grid, 256, 0, s>>>(X, W, bias, Y, stats, g);
-        else conv7x1_col_kernel<IR2RGB_BF16, 64><<<grid, 256, 0, s>>>(X, W, bias, Y, stats, g);
-    } else {
-        if (g.Cout == 128) conv7x1_col_kernel<IR2RGB_F16, 128><<<grid, 256, 0, s>>>(X, W, bias, Y, stats, g);
-        else conv7x1_col_kernel<IR2RGB_F16, 64><<<grid, 256, 0, s>>>(X, W, bias, Y, stats, g);
-    }
+    with_dtype(dtype, [&](auto dt) {
+        auto launch = [&](auto kernel) { kernel<<<grid, 256, 0, s>>>((const uint16_t *)x, (const uint16_t *)wp, bias, (uint16_t *)y, stats, g); };
+        if (g.Cout == 128) launch(conv7x1_col_kernel<dt.value, 128>);
+        else launch(conv7x1_col_kernel<dt.value, 64>);
+    });
     return ir2rgb_launch_status();
 }

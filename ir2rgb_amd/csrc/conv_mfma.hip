@@ -28,7 +28,6 @@
 // which makes every ds_read_b128 fragment read bank-conflict free.
 //
 // Algorithmic flops = 2 * pixels * Cout * ntaps * Cin; roofline bound: MFMA.
-#include <cstdlib>
 #include <cstring>
 #include <type_traits>
 #include <utility>
@@ -720,37 +719,41 @@ static int tile_pixels(long P, int Cout, int ksteps) {
 }
 
 // Builds the launch plan(s) for one convolution; returns the number of classes or < 0.
-static int make_plan(const ir2rgb_conv_desc *d, ClassPlan plans[4]) {
+static int make_plan(const ir2rgb_conv_desc *d, const ConvView &v, ClassPlan plans[4]) {
     if (!d || d->N < 1 || d->Cin < 64 || (d->Cin % 64) || d->Cout < 1 || d->kh < 1 || d->kw < 1 ||
         d->kh * d->kw > IR2RGB_MAX_TAPS || d->stride_h < 1 || d->stride_w < 1 || d->pad_h < 0 || d->pad_w < 0)
         return IR2RGB_EINVAL;
-    if (d->dtype != IR2RGB_BF16 && d->dtype != IR2RGB_F16) return IR2RGB_ENOSUP;
+    if (!v.half) return IR2RGB_ENOSUP;
     if (d->pad_mode != 0 && d->pad_mode != 1) return IR2RGB_ENOSUP;   // pad_mode 2 exists in conv3x3_patch_kernel only
     int ncls = 0;
     long woff = 0;
     int row0 = 0;
+    // what the plain convolution and every sub-pixel class have in common; the tap grid follows
+    auto new_class = [&](int Hsub, int Wsub) -> ClassPlan & {
+        ClassPlan &c = plans[ncls++];
+        ConvGeom &g = c.geom;
+        g = ConvGeom{};
+        g.N = d->N; g.Hin = d->Hin; g.Win = d->Win; g.Cin = d->Cin;
+        g.Hsub = Hsub; g.Wsub = Wsub; g.Hout = d->Hout; g.Wout = d->Wout; g.Cout = d->Cout;
+        g.pad_mode = d->pad_mode; g.kchunks = d->Cin / 64; g.act = d->act; g.out_f32 = d->out_f32;
+        c.pack = PackGeom{};
+        c.pack.Cout = d->Cout; c.pack.Cin = d->Cin; c.pack.kh = d->kh; c.pack.kw = d->kw; c.pack.transposed = d->transposed ? 1 : 0;
+        c.w_offset = woff;
+        return c;
+    };
     if (!d->transposed) {
         int Ho = (d->Hin + 2 * d->pad_h - d->kh) / d->stride_h + 1, Wo = (d->Win + 2 * d->pad_w - d->kw) / d->stride_w + 1;
         if (Ho != d->Hout || Wo != d->Wout || Ho < 1 || Wo < 1) return IR2RGB_EINVAL;
         if (d->pad_mode == 1 && (d->pad_h >= d->Hin || d->pad_w >= d->Win)) return IR2RGB_EINVAL;
-        ClassPlan &c = plans[0];
+        ClassPlan &c = new_class(Ho, Wo);
         ConvGeom &g = c.geom;
-        g = ConvGeom{};
-        g.N = d->N; g.Hin = d->Hin; g.Win = d->Win; g.Cin = d->Cin;
-        g.Hsub = Ho; g.Wsub = Wo; g.Hout = Ho; g.Wout = Wo; g.Cout = d->Cout;
         g.s_in_y = d->stride_h; g.s_in_x = d->stride_w; g.s_out_y = g.s_out_x = 1; g.off_y = g.off_x = 0;
-        g.ntaps = d->kh * d->kw; g.pad_mode = d->pad_mode; g.kchunks = d->Cin / 64; g.act = d->act;
-        g.out_f32 = d->out_f32;
-        c.pack = PackGeom{};
-        c.pack.Cout = d->Cout; c.pack.Cin = d->Cin; c.pack.kh = d->kh; c.pack.kw = d->kw; c.pack.transposed = 0;
-        c.pack.ntaps = g.ntaps;
+        g.ntaps = c.pack.ntaps = d->kh * d->kw;
         g.ntx = d->kw; g.dy0 = -d->pad_h; g.dys = 1; g.dx0 = -d->pad_w; g.dxs = 1;
         for (int ky = 0, t = 0; ky < d->kh; ++ky)
             for (int kx = 0; kx < d->kw; ++kx, ++t) {
                 c.pack.ky[t] = (signed char)ky; c.pack.kx[t] = (signed char)kx;
             }
-        c.w_offset = 0;
-        ncls = 1;
     } else {
         // transposed convolution (stride 1 or 2 per axis) as stride_h*stride_w sub-pixel classes:
         //   oy = sh*iy - pad + ky  ->  for oy = sh*sy + a: ky = (a + pad) mod sh (+ sh*j), iy = sy + (a + pad - ky)/sh
@@ -764,15 +767,9 @@ static int make_plan(const ir2rgb_conv_desc *d, ClassPlan plans[4]) {
             for (int b = 0; b < sw; ++b) {
                 const int Hsub = (d->Hout - a + sh - 1) / sh, Wsub = (d->Wout - b + sw - 1) / sw;
                 if (Hsub < 1 || Wsub < 1) continue;
-                ClassPlan &c = plans[ncls];
+                ClassPlan &c = new_class(Hsub, Wsub);
                 ConvGeom &g = c.geom;
-                g = ConvGeom{};
-                g.N = d->N; g.Hin = d->Hin; g.Win = d->Win; g.Cin = d->Cin;
-                g.Hsub = Hsub; g.Wsub = Wsub; g.Hout = d->Hout; g.Wout = d->Wout; g.Cout = d->Cout;
                 g.s_in_y = g.s_in_x = 1; g.s_out_y = sh; g.s_out_x = sw; g.off_y = a; g.off_x = b;
-                g.pad_mode = 0; g.kchunks = d->Cin / 64; g.act = d->act; g.out_f32 = d->out_f32;
-                c.pack = PackGeom{};
-                c.pack.Cout = d->Cout; c.pack.Cin = d->Cin; c.pack.kh = d->kh; c.pack.kw = d->kw; c.pack.transposed = 1;
                 int t = 0, ntx = 0;
                 const int ky0 = (a + d->pad_h) % sh, kx0 = (b + d->pad_w) % sw;
                 for (int ky = ky0; ky < d->kh; ky += sh) {
@@ -783,27 +780,25 @@ static int make_plan(const ir2rgb_conv_desc *d, ClassPlan plans[4]) {
                 }
                 if (t == 0) return IR2RGB_ENOSUP;  // a class without taps would need a bias-only fill
                 g.ntx = ntx; g.dy0 = (a + d->pad_h - ky0) / sh; g.dys = -1; g.dx0 = (b + d->pad_w - kx0) / sw; g.dxs = -1;
-                g.ntaps = t; c.pack.ntaps = t;
-                c.w_offset = woff;
+                g.ntaps = c.pack.ntaps = t;
                 woff += (long)d->Cout * d->Cin * t;
-                ++ncls;
             }
     }
     if ((long)d->N * d->Hin * d->Win >= (1L << 31) || (long)d->N * d->Hout * d->Wout >= (1L << 31) ||
-        (long)d->N * d->Hin * d->Win * ((d->ldx > 0 ? d->ldx : d->Cin) / 8) >= 0xFFFFFFFFL)
+        (long)d->N * d->Hin * d->Win * (v.ldx / 8) >= 0xFFFFFFFFL)
         return IR2RGB_EINVAL;
     for (int i = 0; i < ncls; ++i) {
         ConvGeom &g = plans[i].geom;
         g.div_hw = make_fastdiv((unsigned)(g.Hsub * g.Wsub)); g.div_w = make_fastdiv((unsigned)g.Wsub);
-        g.ldx = d->ldx > 0 ? d->ldx : d->Cin; g.ci_off = d->ci_off;
-        g.ldy = d->ldy > 0 ? d->ldy : d->Cout; g.co_off = d->co_off;
+        g.ldx = v.ldx; g.ci_off = d->ci_off;
+        g.ldy = v.ldy; g.co_off = d->co_off;
         if (g.ci_off < 0 || g.co_off < 0 || g.ci_off + d->Cin > g.ldx || g.co_off + d->Cout > g.ldy || (g.ldx & 7) || (g.ci_off & 7))
             return IR2RGB_EINVAL;
         // the epilogue's 4-channel vector stores (taken when Cout % 4 == 0) need 4-channel aligned rows
         if ((d->Cout & 3) == 0 && ((g.ldy & 3) || (g.co_off & 3))) return IR2RGB_EINVAL;
-        const long xb = (long)g.N * g.Hin * g.Win * g.ldx * 2, wb = (long)g.Cout * g.Cin * g.ntaps * 2;
-        if (xb >= (1L << 31) || wb >= (1L << 31)) return IR2RGB_EINVAL;  // 32-bit buffer offsets
-        g.x_bytes = (unsigned)xb; g.w_bytes = (unsigned)wb;
+        const long wb = (long)g.Cout * g.Cin * g.ntaps * 2;
+        if (v.x_bytes >= (1L << 31) || wb >= (1L << 31)) return IR2RGB_EINVAL;  // 32-bit buffer offsets
+        g.x_bytes = (unsigned)v.x_bytes; g.w_bytes = (unsigned)wb;
         g.cout_major = wb > (long)g.N * g.Hin * g.Win * g.Cin * 2 ? 1 : 0;     // weights outweigh the activations read
     }
     // pixel-tile size: per class, or -- when the classes share one launch -- one size for all of them chosen
@@ -843,97 +838,137 @@ static int make_plan(const ir2rgb_conv_desc *d, ClassPlan plans[4]) {
 
 extern "C" long ir2rgb_conv2d_packed_weight_elems(const ir2rgb_conv_desc *d) {
     ClassPlan plans[4];
-    int n = make_plan(d, plans);
+    int n = make_plan(d, conv_view(d), plans);
     if (n < 0) return n;
     long e = 0;
     for (int i = 0; i < n; ++i) e += (long)d->Cout * d->Cin * plans[i].geom.ntaps;
     return e;
 }
 
+// ---- the forward route: which kernel runs a descriptor, with which geometry, statistics rows and workspace ----
+enum ConvKernel { CONV_IGEMM, CONV_CLASSES, CONV_DOT, CONV_PATCH, CONV_THIN7, CONV_COL7 };
+static const char *const CONV_KERNEL_NAMES[] = {"conv_igemm_kernel", "conv_igemm_classes_kernel", "conv_dot_kernel",
+                                                "conv3x3_patch_kernel", "conv1x7_thin_kernel", "conv7x1_col_kernel"};
+struct ConvRoute {
+    ConvKernel kernel;
+    int variant;            // CONV_PATCH: conv3x3p_plan's variant, with its geometry p3
+    P3Geom p3;
+    T7Geom t7;              // CONV_THIN7
+    C7Geom c7;              // CONV_COL7
+    int ncls;               // CONV_IGEMM, CONV_DOT (one class) and CONV_CLASSES
+    ClassPlan cls[4];
+    int stats_rows;         // rows of the BatchNorm statistics buffer this kernel writes
+    long workspace_bytes;   // > 0: a split patch form, which runs only where the caller brings this workspace
+};
+
 // One fp32 output channel, zero padding, 512-channel slabs, <= 16 taps: conv_dot_kernel (IR2RGB_CONV_DOT=0: the GEMM tile,
 // which is what such a layer with other channel counts gets)
 static bool conv_dot_ok(const ir2rgb_conv_desc *d) {
-    static int v = -1;
-    if (v < 0) { const char *e = getenv("IR2RGB_CONV_DOT"); v = e ? atoi(e) : 1; }
-    const int ldx = d->ldx ? d->ldx : d->Cin;
+    static const int v = env_switch("IR2RGB_CONV_DOT", 1);
     return v != 0 && d->out_f32 && d->Cout == 1 && !d->transposed && d->pad_mode == 0 && d->Cin >= 512 && (d->Cin % 512) == 0 &&
-           d->kh * d->kw <= 16 && (ldx % 8) == 0 && (d->ci_off % 8) == 0;
+           d->kh * d->kw <= 16 && (d->ldx % 8) == 0 && (d->ci_off % 8) == 0;
 }
 
+// The one place that decides.  The flags say what the launch brings beside the descriptor: the 1x7 head kernel adds no
+// bias and writes no statistics, conv_dot_kernel writes no statistics, the split patch forms need a workspace.  The three
+// special kernels' plans exclude each other (3x3, 7x1, 1x7 taps) and come before make_plan, which knows no pad_mode 2.
+static int conv_route(const ir2rgb_conv_desc *d, bool has_bias, bool has_stats, bool has_workspace, ConvRoute *r) {
+    if (!d) return IR2RGB_EINVAL;
+    const ConvView v = conv_view(d);
+    r->stats_rows = 0; r->workspace_bytes = 0; r->ncls = 0;
+    if ((r->variant = conv3x3p_plan(d, v, &r->p3, &r->stats_rows, has_workspace)) != 0) {
+        r->kernel = CONV_PATCH;
+        r->workspace_bytes = conv3x3p_workspace_bytes(r->variant, r->p3);
+        return IR2RGB_OK;
+    }
+    if (conv7x1_col_plan(d, v, &r->c7)) {
+        r->kernel = CONV_COL7;
+        r->stats_rows = conv7x1_col_tiles(r->c7);
+        return IR2RGB_OK;
+    }
+    if (!has_bias && !has_stats && conv1x7_thin_plan(d, v, &r->t7)) {
+        r->kernel = CONV_THIN7;
+        return IR2RGB_OK;
+    }
+    r->ncls = make_plan(d, v, r->cls);
+    if (r->ncls < 0) return r->ncls;
+    for (int i = 0; i < r->ncls; ++i) r->stats_rows += r->cls[i].npt;
+    r->kernel = r->ncls > 1 ? CONV_CLASSES : !has_stats && conv_dot_ok(d) ? CONV_DOT : CONV_IGEMM;
+    return IR2RGB_OK;
+}
+
+// What each query assumes of the launch it answers for (ir2rgb_conv2d_fwd_ws itself passes what it was given).  The name is
+// that of a launch without bias, statistics and workspace: it says conv1x7_thin_kernel and conv_dot_kernel where a launch
+// with bias or statistics runs conv_igemm_kernel.
 extern "C" const char *ir2rgb_conv2d_kernel_name(const ir2rgb_conv_desc *d) {
-    if (!d) return "";
-    P3Geom g3;
-    int npt3 = 0;
-    if (conv3x3p_plan(d, &g3, &npt3)) return "conv3x3_patch_kernel";
-    {
-        T7Geom g7;
-        if (conv1x7_thin_plan(d, &g7)) return "conv1x7_thin_kernel";     // (launches without bias / statistics: the head pass)
-        C7Geom gc;
-        if (conv7x1_col_plan(d, &gc)) return "conv7x1_col_kernel";
-    }
-    ClassPlan plans[4];
-    const int n = make_plan(d, plans);
-    if (n < 0) return "";
-    if (n == 1 && conv_dot_ok(d)) return "conv_dot_kernel";
-    return n > 1 ? "conv_igemm_classes_kernel" : "conv_igemm_kernel";
+    ConvRoute r;
+    return conv_route(d, false, false, false, &r) < 0 ? "" : CONV_KERNEL_NAMES[r.kernel];
 }
 
+// The rows are those of a launch that writes statistics (the same in every patch variant).
 extern "C" int ir2rgb_conv2d_stats_rows(const ir2rgb_conv_desc *d) {
-    {
-        P3Geom g3;
-        int npt3 = 0;
-        if (d && conv3x3p_plan(d, &g3, &npt3)) return npt3;
-        C7Geom gc;
-        if (d && conv7x1_col_plan(d, &gc)) return conv7x1_col_tiles(gc);
-    }
-    ClassPlan plans[4];
-    int n = make_plan(d, plans);
-    if (n < 0) return n;
-    int rows = 0;
-    for (int i = 0; i < n; ++i) rows += plans[i].npt;
-    return rows;
+    ConvRoute r;
+    const int rc = conv_route(d, false, true, false, &r);
+    return rc < 0 ? rc : r.stats_rows;
 }
 
-extern "C" int ir2rgb_conv2d_pack_weight_adjoint(const ir2rgb_conv_desc *d, const float *w, void *wpacked, void *stream);
+// The workspace is what a launch that brings one can use (0 also for a descriptor that no kernel runs).
+extern "C" long ir2rgb_conv2d_fwd_workspace_bytes(const ir2rgb_conv_desc *d) {
+    ConvRoute r;
+    return !d ? IR2RGB_EINVAL : conv_route(d, false, false, true, &r) < 0 ? 0 : r.workspace_bytes;
+}
 
-static int pack_impl(const ir2rgb_conv_desc *d, const float *w, void *wpacked, void *stream, bool adjoint) {
+// ---- weight packing ----
+// How a weight is packed: `tiled` -- a plain convolution weight, one class, all taps in row-major order, <= 9 taps, 64-
+// multiples along the packed K axis and 16-byte aligned pointers -- through pack_tile_kernel's gx x gy tiles, anything
+// else class by class through the generic gather.
+struct PackPlan {
+    bool tiled;
+    int srcCout, srcCin, T, gx, gy;     // tiled: source dims (the adjoint's Cin plays the source's Cout axis), taps, tile grid
+    int n;                              // generic: classes, each with its gather geometry, offset and elements
+    PackGeom g[4];
+    long w_offset[4], total[4];
+};
+
+static int pack_plan(const ir2rgb_conv_desc *d, const void *w, const void *wpacked, bool adjoint, PackPlan *p) {
     ClassPlan plans[4];
-    int n = make_plan(d, plans);
+    const int n = make_plan(d, conv_view(d), plans);
     if (n < 0) return n;
     if (adjoint && d->transposed) return IR2RGB_ENOSUP;
-    // fast path: plain convolution weight, one class, all taps in row-major order, <= 9 taps
-    {
-        const PackGeom &pg = plans[0].pack;
-        const int T = d->kh * d->kw;
-        bool natural = n == 1 && !d->transposed && !pg.transposed && !pg.flip && pg.ntaps == T && T <= PACK_MAX_T;
-        for (int t = 0; natural && t < T; ++t) natural = pg.ky[t] == t / d->kw && pg.kx[t] == t % d->kw;
-        // the packed buffer of the adjoint descriptor d (Cin' = d->Cin plays the source's Cout axis)
-        const int srcCout = adjoint ? d->Cin : d->Cout, srcCin = adjoint ? d->Cout : d->Cin;
-        if (natural && srcCin % 64 == 0 && (!adjoint || srcCout % 64 == 0) && (((uintptr_t)w | (uintptr_t)wpacked) & 15) == 0) {
-            const int tco = adjoint ? 64 : 16, tci = adjoint ? 16 : 64;
-            dim3 grid((unsigned)(srcCin / tci), (unsigned)((srcCout + tco - 1) / tco));
-            uint16_t *dst = reinterpret_cast<uint16_t *>(wpacked);
-            hipStream_t s = as_stream(stream);
-            if (d->dtype == IR2RGB_BF16) {
-                if (adjoint) pack_tile_kernel<IR2RGB_BF16, 1><<<grid, 256, 0, s>>>(w, dst, srcCout, srcCin, T);
-                else pack_tile_kernel<IR2RGB_BF16, 0><<<grid, 256, 0, s>>>(w, dst, srcCout, srcCin, T);
-            } else {
-                if (adjoint) pack_tile_kernel<IR2RGB_F16, 1><<<grid, 256, 0, s>>>(w, dst, srcCout, srcCin, T);
-                else pack_tile_kernel<IR2RGB_F16, 0><<<grid, 256, 0, s>>>(w, dst, srcCout, srcCin, T);
-            }
-            return ir2rgb_launch_status();
-        }
-    }
+    const PackGeom &pg = plans[0].pack;
+    p->T = d->kh * d->kw;
+    bool natural = n == 1 && !d->transposed && pg.ntaps == p->T && p->T <= PACK_MAX_T;
+    for (int t = 0; natural && t < p->T; ++t) natural = pg.ky[t] == t / d->kw && pg.kx[t] == t % d->kw;
+    p->srcCout = adjoint ? d->Cin : d->Cout; p->srcCin = adjoint ? d->Cout : d->Cin;
+    p->tiled = natural && p->srcCin % 64 == 0 && (!adjoint || p->srcCout % 64 == 0) && (((uintptr_t)w | (uintptr_t)wpacked) & 15) == 0;
+    const int tco = adjoint ? 64 : 16, tci = adjoint ? 16 : 64;
+    p->gx = p->srcCin / tci; p->gy = (p->srcCout + tco - 1) / tco;
+    p->n = n;
     for (int i = 0; i < n; ++i) {
-        if (adjoint) { plans[i].pack.transposed = 1; plans[i].pack.flip = 1; }
-        long total = (long)d->Cout * d->Cin * plans[i].geom.ntaps;
-        uint16_t *dst = reinterpret_cast<uint16_t *>(wpacked) + plans[i].w_offset;
-        int grid = stream_grid(total, 256);
-        if (d->dtype == IR2RGB_BF16)
-            pack_weight_kernel<IR2RGB_BF16><<<grid, 256, 0, as_stream(stream)>>>(w, dst, plans[i].pack, total);
-        else
-            pack_weight_kernel<IR2RGB_F16><<<grid, 256, 0, as_stream(stream)>>>(w, dst, plans[i].pack, total);
+        p->g[i] = plans[i].pack;
+        if (adjoint) { p->g[i].transposed = 1; p->g[i].flip = 1; }
+        p->w_offset[i] = plans[i].w_offset;
+        p->total[i] = (long)d->Cout * d->Cin * plans[i].geom.ntaps;
     }
+    return IR2RGB_OK;
+}
+
+static int pack_impl(const ir2rgb_conv_desc *d, const float *w, void *wpacked, void *stream, bool adjoint) {
+    PackPlan p;
+    const int rc = pack_plan(d, w, wpacked, adjoint, &p);
+    if (rc < 0) return rc;
+    uint16_t *dst = reinterpret_cast<uint16_t *>(wpacked);
+    hipStream_t s = as_stream(stream);
+    with_dtype(d->dtype, [&](auto dt) {
+        if (p.tiled) {
+            auto tile = [&](auto kernel) { kernel<<<dim3((unsigned)p.gx, (unsigned)p.gy), 256, 0, s>>>(w, dst, p.srcCout, p.srcCin, p.T); };
+            if (adjoint) tile(pack_tile_kernel<dt.value, 1>);
+            else tile(pack_tile_kernel<dt.value, 0>);
+        } else {
+            for (int i = 0; i < p.n; ++i)
+                pack_weight_kernel<dt.value><<<stream_grid(p.total[i], 256), 256, 0, s>>>(w, dst + p.w_offset[i], p.g[i], p.total[i]);
+        }
+    });
     return ir2rgb_launch_status();
 }
 
@@ -941,41 +976,35 @@ extern "C" int ir2rgb_conv2d_pack_weight(const ir2rgb_conv_desc *d, const float 
     return pack_impl(d, w, wpacked, stream, false);
 }
 
-// The entries pack_impl's launches correspond to (same decisions, same kernels' bodies).
+extern "C" int ir2rgb_conv2d_pack_weight_adjoint(const ir2rgb_conv_desc *d, const float *w, void *wpacked, void *stream) {
+    return pack_impl(d, w, wpacked, stream, true);
+}
+
+// The batch table's entries for one job: what pack_impl launches, as PackEntry records (the generic gather here with four
+// elements per thread on at most 2048 blocks, where pack_impl's own launch is a grid-stride one of stream_grid blocks).
 static int pack_entries(const ir2rgb_conv_desc *d, const float *w, void *wpacked, bool adjoint, PackEntry *out) {
-    ClassPlan plans[4];
-    int n = make_plan(d, plans);
-    if (n < 0) return n;
-    if (adjoint && d->transposed) return IR2RGB_ENOSUP;
+    PackPlan p;
+    const int rc = pack_plan(d, w, wpacked, adjoint, &p);
+    if (rc < 0) return rc;
     if (!w || !wpacked) return IR2RGB_EINVAL;
-    const PackGeom &pg = plans[0].pack;
-    const int T = d->kh * d->kw;
-    bool natural = n == 1 && !d->transposed && !pg.transposed && !pg.flip && pg.ntaps == T && T <= PACK_MAX_T;
-    for (int t = 0; natural && t < T; ++t) natural = pg.ky[t] == t / d->kw && pg.kx[t] == t % d->kw;
-    const int srcCout = adjoint ? d->Cin : d->Cout, srcCin = adjoint ? d->Cout : d->Cin;
-    if (natural && srcCin % 64 == 0 && (!adjoint || srcCout % 64 == 0) && (((uintptr_t)w | (uintptr_t)wpacked) & 15) == 0) {
-        const int tco = adjoint ? 64 : 16, tci = adjoint ? 16 : 64;
-        PackEntry &e = out[0];
-        memset(&e, 0, sizeof(e));
-        e.w = w;
-        e.wp = reinterpret_cast<uint16_t *>(wpacked);
-        e.kind = adjoint ? 2 : 1;
-        e.Cout = srcCout; e.Cin = srcCin; e.T = T;
-        e.gx = srcCin / tci;
-        e.nblocks = e.gx * ((srcCout + tco - 1) / tco);
-        return 1;
-    }
+    const int n = p.tiled ? 1 : p.n;
     for (int i = 0; i < n; ++i) {
         PackEntry &e = out[i];
         memset(&e, 0, sizeof(e));
-        e.g = plans[i].pack;
-        if (adjoint) { e.g.transposed = 1; e.g.flip = 1; }
-        e.total = (long)d->Cout * d->Cin * plans[i].geom.ntaps;
         e.w = w;
-        e.wp = reinterpret_cast<uint16_t *>(wpacked) + plans[i].w_offset;
-        e.kind = 0;
-        long nb = (e.total + 1023) / 1024;                     // four elements per thread
-        e.nblocks = (int)(nb < 1 ? 1 : (nb > 2048 ? 2048 : nb));
+        if (p.tiled) {
+            e.wp = reinterpret_cast<uint16_t *>(wpacked);
+            e.kind = adjoint ? 2 : 1;
+            e.Cout = p.srcCout; e.Cin = p.srcCin; e.T = p.T;
+            e.gx = p.gx;
+            e.nblocks = p.gx * p.gy;
+        } else {
+            e.g = p.g[i];
+            e.total = p.total[i];
+            e.wp = reinterpret_cast<uint16_t *>(wpacked) + p.w_offset[i];
+            const long nb = (e.total + 1023) / 1024;
+            e.nblocks = (int)(nb < 1 ? 1 : (nb > 2048 ? 2048 : nb));
+        }
     }
     return n;
 }
@@ -1042,134 +1071,103 @@ extern "C" int ir2rgb_conv2d_pack_batch_run(const void *table_dev, int nentries,
     if ((uintptr_t)table_dev & 15) return IR2RGB_EALIGN;
     const PackEntry *E = reinterpret_cast<const PackEntry *>(table_dev);
     const PackBlock *B = reinterpret_cast<const PackBlock *>(reinterpret_cast<const char *>(table_dev) + pack_blocks_offset(nentries));
-    if (dtype == IR2RGB_BF16) pack_batch_kernel<IR2RGB_BF16><<<nblocks, 256, 0, as_stream(stream)>>>(E, B);
-    else pack_batch_kernel<IR2RGB_F16><<<nblocks, 256, 0, as_stream(stream)>>>(E, B);
+    with_dtype(dtype, [&](auto dt) { pack_batch_kernel<dt.value><<<nblocks, 256, 0, as_stream(stream)>>>(E, B); });
     return ir2rgb_launch_status();
 }
 
-extern "C" int ir2rgb_conv2d_pack_weight_adjoint(const ir2rgb_conv_desc *d, const float *w, void *wpacked, void *stream) {
-    return pack_impl(d, w, wpacked, stream, true);
-}
-
-template <int DT, int NTY, int NTX, bool THIN = false>
-static void launch_conv_taps(const ClassPlan &c, int tp, unsigned grid, const uint16_t *x, const uint16_t *wp,
-                             const float *bias, uint16_t *y, float *stats, hipStream_t s) {
-    const ConvGeom &g = c.geom;
+// ---- forward launches ----
+// Calls f with the pixel-tile size (ClassPlan::tp) as a compile-time constant.
+template <class F> static void with_tile(int tp, F &&f) {
     switch (tp) {
-        case 256: conv_igemm_kernel<DT, 256, NTY, NTX, THIN><<<grid, 512, 0, s>>>(x, wp, bias, y, stats, g); break;
-        case 128: conv_igemm_kernel<DT, 128, NTY, NTX, THIN><<<grid, 512, 0, s>>>(x, wp, bias, y, stats, g); break;
-        default:  conv_igemm_kernel<DT, 64, NTY, NTX, THIN><<<grid, 512, 0, s>>>(x, wp, bias, y, stats, g); break;
+        case 256: f(std::integral_constant<int, 256>{}); break;
+        case 128: f(std::integral_constant<int, 128>{}); break;
+        default:  f(std::integral_constant<int, 64>{}); break;
     }
 }
 
-template <int DT>
-static void launch_conv(const ClassPlan &c, const uint16_t *x, const uint16_t *wp, const float *bias, uint16_t *y,
+template <int NTY, int NTX, bool THIN = false> struct Taps {};
+
+static void launch_conv(const ClassPlan &c, int dtype, const uint16_t *x, const uint16_t *wp, const float *bias, uint16_t *y,
                         float *stats, hipStream_t s) {
     const ConvGeom &g = c.geom;
-    const int tp = c.tp;
-    const int nct = (g.Cout + 127) / 128;
-    const unsigned grid = (unsigned)(c.npt * nct);
+    const unsigned grid = (unsigned)(c.npt * ((g.Cout + 127) / 128));
     const int nty = g.ntaps / g.ntx;
     const bool thin = g.Cout <= 32;
-    if (thin && nty == 4 && g.ntx == 4)      launch_conv_taps<DT, 4, 4, true>(c, tp, grid, x, wp, bias, y, stats, s);
-    else if (thin && nty == 1 && g.ntx == 7) launch_conv_taps<DT, 1, 7, true>(c, tp, grid, x, wp, bias, y, stats, s);
-    else if (nty == 3 && g.ntx == 3) launch_conv_taps<DT, 3, 3>(c, tp, grid, x, wp, bias, y, stats, s);
-    else if (nty == 4 && g.ntx == 4) launch_conv_taps<DT, 4, 4>(c, tp, grid, x, wp, bias, y, stats, s);
-    else if (nty == 7 && g.ntx == 1) launch_conv_taps<DT, 7, 1>(c, tp, grid, x, wp, bias, y, stats, s);
-    else if (nty == 1 && g.ntx == 7) launch_conv_taps<DT, 1, 7>(c, tp, grid, x, wp, bias, y, stats, s);
-    else if (nty == 4 && g.ntx == 1) launch_conv_taps<DT, 4, 1>(c, tp, grid, x, wp, bias, y, stats, s);
+    auto launch = [&]<int NTY, int NTX, bool THIN>(Taps<NTY, NTX, THIN>) {
+        with_dtype(dtype, [&](auto dt) {
+            with_tile(c.tp, [&](auto tp) {
+                conv_igemm_kernel<dt.value, tp.value, NTY, NTX, THIN><<<grid, 512, 0, s>>>(x, wp, bias, y, stats, g);
+            });
+        });
+    };
+    if (thin && nty == 4 && g.ntx == 4)      launch(Taps<4, 4, true>{});
+    else if (thin && nty == 1 && g.ntx == 7) launch(Taps<1, 7, true>{});
+    else if (nty == 3 && g.ntx == 3) launch(Taps<3, 3>{});
+    else if (nty == 4 && g.ntx == 4) launch(Taps<4, 4>{});
+    else if (nty == 7 && g.ntx == 1) launch(Taps<7, 1>{});
+    else if (nty == 1 && g.ntx == 7) launch(Taps<1, 7>{});
+    else if (nty == 4 && g.ntx == 1) launch(Taps<4, 1>{});
     // small tap grids: 2x2 / 2x1 / 1x2 / 1x1 kernels, and a transposed convolution that has a single sub-pixel class
-    else if (nty == 2 && g.ntx == 2) launch_conv_taps<DT, 2, 2>(c, tp, grid, x, wp, bias, y, stats, s);
-    else if (nty == 2 && g.ntx == 1) launch_conv_taps<DT, 2, 1>(c, tp, grid, x, wp, bias, y, stats, s);
-    else if (nty == 1 && g.ntx == 2) launch_conv_taps<DT, 1, 2>(c, tp, grid, x, wp, bias, y, stats, s);
-    else if (nty == 1 && g.ntx == 1) launch_conv_taps<DT, 1, 1>(c, tp, grid, x, wp, bias, y, stats, s);
-    else                             launch_conv_taps<DT, 0, 0>(c, tp, grid, x, wp, bias, y, stats, s);
+    else if (nty == 2 && g.ntx == 2) launch(Taps<2, 2>{});
+    else if (nty == 2 && g.ntx == 1) launch(Taps<2, 1>{});
+    else if (nty == 1 && g.ntx == 2) launch(Taps<1, 2>{});
+    else if (nty == 1 && g.ntx == 1) launch(Taps<1, 1>{});
+    else                             launch(Taps<0, 0>{});
 }
 
-extern "C" long ir2rgb_conv2d_fwd_workspace_bytes(const ir2rgb_conv_desc *d) {
-    if (!d) return IR2RGB_EINVAL;
-    P3Geom g3;
-    int npt3 = 0;
-    return conv3x3p_workspace_bytes(conv3x3p_plan(d, &g3, &npt3, true), g3);
-}
-
-extern "C" int ir2rgb_conv2d_fwd_ws(const ir2rgb_conv_desc *d, const void *x, const void *wpacked, const float *bias,
-                                    void *y, float *stats_partial, void *workspace, long workspace_bytes, void *stream);
-
-extern "C" int ir2rgb_conv2d_fwd(const ir2rgb_conv_desc *d, const void *x, const void *wpacked, const float *bias,
-                                 void *y, float *stats_partial, void *stream) {
-    return ir2rgb_conv2d_fwd_ws(d, x, wpacked, bias, y, stats_partial, nullptr, 0, stream);
+// one launch for all classes: same pixel-tile size for all of them (the plans were made with it)
+static void launch_classes(const ClassPlan *plans, int n, int dtype, const uint16_t *x, const uint16_t *wp, const float *bias,
+                           uint16_t *y, float *stats, hipStream_t s) {
+    ConvClasses cs;
+    int order[4] = {0, 1, 2, 3};
+    for (int i = 0; i < n; ++i)           // longest K loop first
+        for (int j = i + 1; j < n; ++j)
+            if (plans[order[j]].geom.ntaps > plans[order[i]].geom.ntaps) { int t = order[i]; order[i] = order[j]; order[j] = t; }
+    int first = 0;
+    for (int i = 0; i < n; ++i) {
+        const ClassPlan &c = plans[order[i]];
+        cs.g[i] = c.geom;
+        cs.w_off[i] = c.w_offset;
+        cs.first[i] = first;
+        const int nwg = c.npt * ((c.geom.Cout + 127) / 128);
+        first += (nwg + 7) & ~7;
+    }
+    cs.first[n] = first;
+    cs.n = n;
+    with_dtype(dtype, [&](auto dt) {
+        with_tile(plans[0].tp, [&](auto tp) {
+            conv_igemm_classes_kernel<dt.value, tp.value><<<first, 512, 0, s>>>(x, wp, bias, y, stats, cs);
+        });
+    });
 }
 
 extern "C" int ir2rgb_conv2d_fwd_ws(const ir2rgb_conv_desc *d, const void *x, const void *wpacked, const float *bias,
                                     void *y, float *stats_partial, void *workspace, long workspace_bytes, void *stream) {
     if (!d) return IR2RGB_EINVAL;
     if ((((uintptr_t)x | (uintptr_t)wpacked | (uintptr_t)y) & 15) != 0) return IR2RGB_EALIGN;
-    if (bias == nullptr && stats_partial == nullptr) {
-        T7Geom g7;      // the 1x7 pass of the separable heads: row-segment staging, weights in registers (conv1x7_thin.hip)
-        if (conv1x7_thin_plan(d, &g7)) return conv1x7_thin_launch(g7, d->dtype, d->Cin, x, wpacked, y, as_stream(stream));
-    }
-    {
-        C7Geom gc;      // the 7x1 pass of the generators' first layers: column tiles staged once (conv7x1_col.hip)
-        if (conv7x1_col_plan(d, &gc)) return conv7x1_col_launch(gc, d->dtype, x, wpacked, bias, y, stats_partial, as_stream(stream));
-    }
-    {
-        P3Geom g3;
-        int npt3 = 0;
-        const int variant = conv3x3p_plan(d, &g3, &npt3, workspace != nullptr);
-        if (variant)
-            return conv3x3p_launch(variant, g3, d->dtype, x, wpacked, bias, y, stats_partial, as_stream(stream), workspace, workspace_bytes);
-    }
-    ClassPlan plans[4];
-    int n = make_plan(d, plans);
-    if (n < 0) return n;
-    if (n == 1 && stats_partial == nullptr && conv_dot_ok(d)) {
-        const ConvGeom &g = plans[0].geom;
-        const long P = (long)g.N * g.Hout * g.Wout;
-        const long waves = P < 8192 ? P : 8192;
-        const unsigned grid = (unsigned)((waves + 3) / 4);
-        if (d->dtype == IR2RGB_BF16)
-            conv_dot_kernel<IR2RGB_BF16><<<grid, 256, 0, as_stream(stream)>>>((const uint16_t *)x, (const uint16_t *)wpacked, bias, (float *)y, g);
-        else
-            conv_dot_kernel<IR2RGB_F16><<<grid, 256, 0, as_stream(stream)>>>((const uint16_t *)x, (const uint16_t *)wpacked, bias, (float *)y, g);
-        return ir2rgb_launch_status();
-    }
-    if (n > 1) {
-        // one launch for all classes: same pixel-tile size for all of them (plans were made with it)
-        ConvClasses cs;
-        int order[4] = {0, 1, 2, 3};
-        for (int i = 0; i < n; ++i)           // longest K loop first
-            for (int j = i + 1; j < n; ++j)
-                if (plans[order[j]].geom.ntaps > plans[order[i]].geom.ntaps) { int t = order[i]; order[i] = order[j]; order[j] = t; }
-        int first = 0;
-        for (int i = 0; i < n; ++i) {
-            const ClassPlan &c = plans[order[i]];
-            cs.g[i] = c.geom;
-            cs.w_off[i] = c.w_offset;
-            cs.first[i] = first;
-            const int nwg = c.npt * ((c.geom.Cout + 127) / 128);
-            first += (nwg + 7) & ~7;
+    ConvRoute r;
+    const int rc = conv_route(d, bias != nullptr, stats_partial != nullptr, workspace != nullptr, &r);
+    if (rc < 0) return rc;
+    hipStream_t s = as_stream(stream);
+    const uint16_t *X = (const uint16_t *)x, *W = (const uint16_t *)wpacked;
+    switch (r.kernel) {
+        case CONV_PATCH: return conv3x3p_launch(r.variant, r.p3, d->dtype, x, wpacked, bias, y, stats_partial, s, workspace, workspace_bytes);
+        case CONV_COL7: return conv7x1_col_launch(r.c7, d->dtype, x, wpacked, bias, y, stats_partial, s);
+        case CONV_THIN7: return conv1x7_thin_launch(r.t7, d->dtype, d->Cin, x, wpacked, y, s);
+        case CONV_DOT: {
+            const ConvGeom &g = r.cls[0].geom;
+            const long P = (long)g.N * g.Hout * g.Wout;
+            const long waves = P < 8192 ? P : 8192;
+            with_dtype(d->dtype, [&](auto dt) { conv_dot_kernel<dt.value><<<(unsigned)((waves + 3) / 4), 256, 0, s>>>(X, W, bias, (float *)y, g); });
+            break;
         }
-        cs.first[n] = first;
-        cs.n = n;
-        const int tp = plans[0].tp;
-        hipStream_t s = as_stream(stream);
-        const uint16_t *X = (const uint16_t *)x, *W = (const uint16_t *)wpacked;
-        uint16_t *Yp = (uint16_t *)y;
-        if (d->dtype == IR2RGB_BF16) {
-            if (tp == 256) conv_igemm_classes_kernel<IR2RGB_BF16, 256><<<first, 512, 0, s>>>(X, W, bias, Yp, stats_partial, cs);
-            else if (tp == 128) conv_igemm_classes_kernel<IR2RGB_BF16, 128><<<first, 512, 0, s>>>(X, W, bias, Yp, stats_partial, cs);
-            else conv_igemm_classes_kernel<IR2RGB_BF16, 64><<<first, 512, 0, s>>>(X, W, bias, Yp, stats_partial, cs);
-        } else {
-            if (tp == 256) conv_igemm_classes_kernel<IR2RGB_F16, 256><<<first, 512, 0, s>>>(X, W, bias, Yp, stats_partial, cs);
-            else if (tp == 128) conv_igemm_classes_kernel<IR2RGB_F16, 128><<<first, 512, 0, s>>>(X, W, bias, Yp, stats_partial, cs);
-            else conv_igemm_classes_kernel<IR2RGB_F16, 64><<<first, 512, 0, s>>>(X, W, bias, Yp, stats_partial, cs);
-        }
-        return ir2rgb_launch_status();
+        case CONV_CLASSES: launch_classes(r.cls, r.ncls, d->dtype, X, W, bias, (uint16_t *)y, stats_partial, s); break;
+        case CONV_IGEMM: launch_conv(r.cls[0], d->dtype, X, W, bias, (uint16_t *)y, stats_partial, s); break;
     }
-    if (d->dtype == IR2RGB_BF16)
-        launch_conv<IR2RGB_BF16>(plans[0], (const uint16_t *)x, (const uint16_t *)wpacked, bias, (uint16_t *)y, stats_partial, as_stream(stream));
-    else
-        launch_conv<IR2RGB_F16>(plans[0], (const uint16_t *)x, (const uint16_t *)wpacked, bias, (uint16_t *)y, stats_partial, as_stream(stream));
     return ir2rgb_launch_status();
+}
+
+extern "C" int ir2rgb_conv2d_fwd(const ir2rgb_conv_desc *d, const void *x, const void *wpacked, const float *bias,
+                                 void *y, float *stats_partial, void *stream) {
+    return ir2rgb_conv2d_fwd_ws(d, x, wpacked, bias, y, stats_partial, nullptr, 0, stream);
 }

@@ -203,15 +203,10 @@ extern "C" int ir2rgb_correlation_nhwc_half(const void *a, int lda, int offa, co
     const unsigned grid = (unsigned)(N * H * 4);
     hipStream_t s = as_stream(stream);
     const uint16_t *A = (const uint16_t *)a, *B = (const uint16_t *)b;
-#define CM_LAUNCH(DT, OUT, KC) corr_mfma_kernel<DT, OUT, KC><<<grid, 384, 0, s>>>(A, B, out, g)
-    const int kc = C / 32;
-    if (dtype == IR2RGB_BF16) {
-        if (out_mode == 0) { if (kc == 8) CM_LAUNCH(IR2RGB_BF16, 0, 8); else CM_LAUNCH(IR2RGB_BF16, 0, 4); }
-        else { if (kc == 8) CM_LAUNCH(IR2RGB_BF16, 1, 8); else CM_LAUNCH(IR2RGB_BF16, 1, 4); }
-    } else {
-        if (out_mode == 0) { if (kc == 8) CM_LAUNCH(IR2RGB_F16, 0, 8); else CM_LAUNCH(IR2RGB_F16, 0, 4); }
-        else { if (kc == 8) CM_LAUNCH(IR2RGB_F16, 1, 8); else CM_LAUNCH(IR2RGB_F16, 1, 4); }
-    }
-#undef CM_LAUNCH
+    with_dtype(dtype, [&](auto dt) {
+        auto launch = [&](auto kernel) { kernel<<<grid, 384, 0, s>>>(A, B, out, g); };
+        if (out_mode == 0) { if (C == 256) launch(corr_mfma_kernel<dt.value, 0, 8>); else launch(corr_mfma_kernel<dt.value, 0, 4>); }
+        else { if (C == 256) launch(corr_mfma_kernel<dt.value, 1, 8>); else launch(corr_mfma_kernel<dt.value, 1, 4>); }
+    });
     return ir2rgb_launch_status();
 }

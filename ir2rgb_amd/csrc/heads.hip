@@ -259,10 +259,9 @@ extern "C" int ir2rgb_head_finish_bwd(const float *gout, const float *out, void 
         return e == hipSuccess ? IR2RGB_OK : (int)e;
     }
     int grid = stream_grid(total, 256);
-    if (dtype == IR2RGB_BF16)
-        head_finish_bwd_kernel<IR2RGB_BF16><<<grid, 256, 0, s>>>(gout, out, (uint16_t *)dT, partial, H, W, Cout, KH, CT, pad_h, acts, mul, total);
-    else
-        head_finish_bwd_kernel<IR2RGB_F16><<<grid, 256, 0, s>>>(gout, out, (uint16_t *)dT, partial, H, W, Cout, KH, CT, pad_h, acts, mul, total);
+    with_dtype(dtype, [&](auto dt) {
+        head_finish_bwd_kernel<dt.value><<<grid, 256, 0, s>>>(gout, out, (uint16_t *)dT, partial, H, W, Cout, KH, CT, pad_h, acts, mul, total);
+    });
     head_bias_sum_kernel<<<1, 256, 0, s>>>(partial, dbias, grid, Cout);
     return ir2rgb_launch_status();
 }
@@ -321,7 +320,6 @@ extern "C" int ir2rgb_flow_upsample_slice(const float *in, const float *weight, 
     long total = (long)N * 4 * h * w;
     if (total == 0) return IR2RGB_OK;
     int grid = stream_grid(total, 256);
-    if (dtype == IR2RGB_BF16) flow_up_kernel<IR2RGB_BF16><<<grid, 256, 0, as_stream(stream)>>>(in, weight, bias, (uint16_t *)out, h, w, ld, c_off, total);
-    else flow_up_kernel<IR2RGB_F16><<<grid, 256, 0, as_stream(stream)>>>(in, weight, bias, (uint16_t *)out, h, w, ld, c_off, total);
+    with_dtype(dtype, [&](auto dt) { flow_up_kernel<dt.value><<<grid, 256, 0, as_stream(stream)>>>(in, weight, bias, (uint16_t *)out, h, w, ld, c_off, total); });
     return ir2rgb_launch_status();
 }

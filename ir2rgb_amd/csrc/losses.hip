@@ -21,16 +21,6 @@ struct LossArgs {
     int count;
 };
 
-static __device__ __forceinline__ float lh2f(uint16_t h, int dt) {
-    if (dt == IR2RGB_BF16) return __uint_as_float(((uint32_t)h) << 16);
-    return (float)__builtin_bit_cast(_Float16, h);
-}
-static __device__ __forceinline__ uint16_t lf2h(float f, int dt) {
-    if (dt == IR2RGB_BF16) { __bf16 h = (__bf16)f; return __builtin_bit_cast(uint16_t, h); }
-    _Float16 h = (_Float16)f;
-    return __builtin_bit_cast(uint16_t, h);
-}
-
 __device__ __forceinline__ int loss_find_item(const LossArgs &A, int blk) {
     int i = 0;
     while (i + 1 < A.count && blk >= A.blk0[i + 1]) ++i;
@@ -72,8 +62,8 @@ loss_multi_fwd_kernel(const LossArgs A, int dt, float *__restrict__ partial) {
                 float t = 0.f;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    t += fabsf(lh2f((uint16_t)(wa[j] & 0xffff), dt) - lh2f((uint16_t)(wb[j] & 0xffff), dt));
-                    t += fabsf(lh2f((uint16_t)(wa[j] >> 16), dt) - lh2f((uint16_t)(wb[j] >> 16), dt));
+                    t += fabsf(h2f((uint16_t)(wa[j] & 0xffff), dt) - h2f((uint16_t)(wb[j] & 0xffff), dt));
+                    t += fabsf(h2f((uint16_t)(wa[j] >> 16), dt) - h2f((uint16_t)(wb[j] >> 16), dt));
                 }
                 s += q + 256 * u < q1 ? t : 0.f;
             }
@@ -134,7 +124,7 @@ loss_multi_bwd_kernel(const LossArgs A, int dt, const float *__restrict__ gout) 
         const long per = (n8 + nb - 1) / nb, q0 = lb * per, q1 = min(n8, q0 + per);
         const uint4 *a = (const uint4 *)it.a, *b = (const uint4 *)it.b;
         uint4 *ga = (uint4 *)it.ga;
-        const uint32_t gp = lf2h(g, dt), gn = lf2h(-g, dt);
+        const uint32_t gp = f2h(g, dt), gn = f2h(-g, dt);
         for (long q = q0 + threadIdx.x; q < q1; q += 1024) {      // four operand pairs in flight per lane (see the forward)
             uint4 va[4], vb[4];
 #pragma unroll
@@ -149,8 +139,8 @@ loss_multi_bwd_kernel(const LossArgs A, int dt, const float *__restrict__ gout) 
                 uint32_t o[4];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    const float d0 = lh2f((uint16_t)(wa[j] & 0xffff), dt) - lh2f((uint16_t)(wb[j] & 0xffff), dt);
-                    const float d1 = lh2f((uint16_t)(wa[j] >> 16), dt) - lh2f((uint16_t)(wb[j] >> 16), dt);
+                    const float d0 = h2f((uint16_t)(wa[j] & 0xffff), dt) - h2f((uint16_t)(wb[j] & 0xffff), dt);
+                    const float d1 = h2f((uint16_t)(wa[j] >> 16), dt) - h2f((uint16_t)(wb[j] >> 16), dt);
                     const uint32_t lo = d0 > 0.f ? gp : (d0 < 0.f ? gn : 0u), hi = d1 > 0.f ? gp : (d1 < 0.f ? gn : 0u);
                     o[j] = lo | (hi << 16);
                 }

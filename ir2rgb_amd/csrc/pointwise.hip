@@ -8,17 +8,6 @@
 // All kernels move 16 bytes per lane on the NHWC side.
 #include "common.h"
 
-static __device__ __forceinline__ float h2f(uint16_t h, int dt) {
-    if (dt == IR2RGB_BF16) return __uint_as_float(((uint32_t)h) << 16);
-    _Float16 v = __builtin_bit_cast(_Float16, h);
-    return (float)v;
-}
-static __device__ __forceinline__ uint16_t f2h(float f, int dt) {
-    if (dt == IR2RGB_BF16) { __bf16 h = (__bf16)f; return __builtin_bit_cast(uint16_t, h); }
-    _Float16 h = (_Float16)f;
-    return __builtin_bit_cast(uint16_t, h);
-}
-
 // ----------------------------------------------------------------------------------------
 // BatchNorm statistics: reduce the per-tile partials written by the conv epilogue.
 // Block = 32 channels x 32 row groups (1024 threads): lanes of a wave read 32 consecutive channels
@@ -443,14 +432,11 @@ extern "C" int ir2rgb_bn_finalize_apply(const float *stats_partial, int rows, in
     const long per = (npix + chunks - 1) / chunks;
     dim3 grid((unsigned)(C / 64), (unsigned)((npix + per - 1) / per));
     hipStream_t s = as_stream(stream);
-    if (dtype == IR2RGB_BF16)
-        bn_finalize_apply_kernel<IR2RGB_BF16><<<grid, 256, 0, s>>>(stats_partial, rows, C, (double)count, gamma, beta, conv_bias,
+    with_dtype(dtype, [&](auto dt) {
+        bn_finalize_apply_kernel<dt.value><<<grid, 256, 0, s>>>(stats_partial, rows, C, (double)count, gamma, beta, conv_bias,
             running_mean, running_var, momentum, eps, scale, shift, mean_out, invstd_out, stat_updates, (const uint4 *)x,
             (const uint4 *)res1, (const uint4 *)res2, (uint4 *)y, npix, act, per);
-    else
-        bn_finalize_apply_kernel<IR2RGB_F16><<<grid, 256, 0, s>>>(stats_partial, rows, C, (double)count, gamma, beta, conv_bias,
-            running_mean, running_var, momentum, eps, scale, shift, mean_out, invstd_out, stat_updates, (const uint4 *)x,
-            (const uint4 *)res1, (const uint4 *)res2, (uint4 *)y, npix, act, per);
+    });
     return ir2rgb_launch_status();
 }
 
@@ -463,12 +449,10 @@ extern "C" int ir2rgb_bn_apply(const void *x, const float *scale, const float *s
     long total8 = npix * (C / 8);
     if (total8 == 0) return IR2RGB_OK;
     int grid = stream_grid(total8, 256);
-    if (dtype == IR2RGB_BF16)
-        bn_apply_kernel<IR2RGB_BF16><<<grid, 256, 0, as_stream(stream)>>>((const uint4 *)x, scale, shift, (const uint4 *)res1,
-                                                                          (const uint4 *)res2, (uint4 *)y, total8, C / 8, act);
-    else
-        bn_apply_kernel<IR2RGB_F16><<<grid, 256, 0, as_stream(stream)>>>((const uint4 *)x, scale, shift, (const uint4 *)res1,
-                                                                         (const uint4 *)res2, (uint4 *)y, total8, C / 8, act);
+    with_dtype(dtype, [&](auto dt) {
+        bn_apply_kernel<dt.value><<<grid, 256, 0, as_stream(stream)>>>((const uint4 *)x, scale, shift, (const uint4 *)res1,
+                                                                       (const uint4 *)res2, (uint4 *)y, total8, C / 8, act);
+    });
     return ir2rgb_launch_status();
 }
 
@@ -479,8 +463,7 @@ extern "C" int ir2rgb_nchw_f32_to_nhwc_half(const float *in, void *out, int N, i
     if (N == 0) return IR2RGB_OK;
     long HW = (long)H * W;
     dim3 grid((unsigned)cdiv(HW, 64), (unsigned)cdiv(C, 64), (unsigned)N);
-    if (dtype == IR2RGB_BF16) nchw_to_nhwc_kernel<IR2RGB_BF16><<<grid, 256, 0, as_stream(stream)>>>(in, (uint16_t *)out, C, HW);
-    else nchw_to_nhwc_kernel<IR2RGB_F16><<<grid, 256, 0, as_stream(stream)>>>(in, (uint16_t *)out, C, HW);
+    with_dtype(dtype, [&](auto dt) { nchw_to_nhwc_kernel<dt.value><<<grid, 256, 0, as_stream(stream)>>>(in, (uint16_t *)out, C, HW); });
     return ir2rgb_launch_status();
 }
 
@@ -491,8 +474,7 @@ extern "C" int ir2rgb_nhwc_half_to_nchw_f32(const void *in, float *out, int N, i
     if (N == 0) return IR2RGB_OK;
     long HW = (long)H * W;
     dim3 grid((unsigned)cdiv(HW, 64), (unsigned)cdiv(C, 64), (unsigned)N);
-    if (dtype == IR2RGB_BF16) nhwc_to_nchw_kernel<IR2RGB_BF16><<<grid, 256, 0, as_stream(stream)>>>((const uint16_t *)in, out, C, HW);
-    else nhwc_to_nchw_kernel<IR2RGB_F16><<<grid, 256, 0, as_stream(stream)>>>((const uint16_t *)in, out, C, HW);
+    with_dtype(dtype, [&](auto dt) { nhwc_to_nchw_kernel<dt.value><<<grid, 256, 0, as_stream(stream)>>>((const uint16_t *)in, out, C, HW); });
     return ir2rgb_launch_status();
 }
 
@@ -511,10 +493,9 @@ extern "C" int ir2rgb_xexpand_cx(const float *in, void *out, int N, int Cin, int
     if (blocks > 0x7fffffffL) return IR2RGB_EINVAL;
     const size_t lds = (size_t)Cin * ((XE_TW - 1) * stride_w + KW) * sizeof(float);
     if (lds > 64 * 1024) return IR2RGB_ENOSUP;
-    if (dtype == IR2RGB_BF16)
-        xexpand_kernel<IR2RGB_BF16><<<(unsigned)blocks, 256, lds, as_stream(stream)>>>(in, (uint4 *)out, Cin, H, W, Wout, KW, stride_w, pad_w, pad_mode, lanes, xtiles);
-    else
-        xexpand_kernel<IR2RGB_F16><<<(unsigned)blocks, 256, lds, as_stream(stream)>>>(in, (uint4 *)out, Cin, H, W, Wout, KW, stride_w, pad_w, pad_mode, lanes, xtiles);
+    with_dtype(dtype, [&](auto dt) {
+        xexpand_kernel<dt.value><<<(unsigned)blocks, 256, lds, as_stream(stream)>>>(in, (uint4 *)out, Cin, H, W, Wout, KW, stride_w, pad_w, pad_mode, lanes, xtiles);
+    });
     return ir2rgb_launch_status();
 }
 
@@ -530,8 +511,7 @@ extern "C" int ir2rgb_nchw_f32_to_nhwc_half_slice(const float *in, void *out, in
     if (N == 0) return IR2RGB_OK;
     long HW = (long)H * W;
     dim3 grid((unsigned)cdiv(HW, 64), (unsigned)cdiv(C, 64), (unsigned)N);
-    if (dtype == IR2RGB_BF16) nchw_to_nhwc_slice_kernel<IR2RGB_BF16><<<grid, 256, 0, as_stream(stream)>>>(in, (uint16_t *)out, C, HW, ld, c_off, act);
-    else nchw_to_nhwc_slice_kernel<IR2RGB_F16><<<grid, 256, 0, as_stream(stream)>>>(in, (uint16_t *)out, C, HW, ld, c_off, act);
+    with_dtype(dtype, [&](auto dt) { nchw_to_nhwc_slice_kernel<dt.value><<<grid, 256, 0, as_stream(stream)>>>(in, (uint16_t *)out, C, HW, ld, c_off, act); });
     return ir2rgb_launch_status();
 }
 

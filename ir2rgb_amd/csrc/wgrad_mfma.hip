@@ -792,27 +792,6 @@ wgrad_sum_kernel(const float4 *__restrict__ D, float4 *__restrict__ out, long n4
     }
 }
 
-static bool plan9(const ir2rgb_conv_desc *d, Wgrad9Geom *g) {
-    if (d->transposed || d->kh != 3 || d->kw != 3 || d->stride_h != 1 || d->stride_w != 1 || d->pad_h != 1 || d->pad_w != 1)
-        return false;
-    if (d->Hout != d->Hin || d->Wout != d->Win || (d->Win % 64) || (d->Cin % 64) || (d->Cout % 64) || d->Hin < 2) return false;
-    const long Q = (long)d->N * d->Hin * d->Win;
-    if (Q * d->Cout * 2 >= (1L << 31) || Q * d->Cin * 2 >= (1L << 31)) return false;
-    *g = Wgrad9Geom{};
-    g->N = d->N; g->H = d->Hin; g->W = d->Win; g->Ca = d->Cout; g->Cb = d->Cin; g->pad_mode = d->pad_mode;
-    g->segs = d->Win / 64;
-    g->ksteps = (int)(Q / 64);
-    g->u_bytes = (unsigned)(Q * d->Cout * 2); g->v_bytes = (unsigned)(Q * d->Cin * 2);
-    // one workgroup per CU: split K until ~256 workgroups exist, keeping >= 8 K-steps per split
-    const long tiles = (long)(d->Cout / 64) * (d->Cin / 64);
-    long ks = (256 + tiles - 1) / tiles;
-    if (ks > g->ksteps / 8) ks = g->ksteps / 8;
-    if (ks < 1) ks = 1;
-    if (ks > 256) ks = 256;
-    g->ksplit = (int)ks;
-    return true;
-}
-
 // out[a][b][tap] = sum_split D[split][tap][a][b]   (torch weight layout [Ca][Cb][kh][kw], fp32)
 __global__ void __launch_bounds__(256)
 wgrad_finish_kernel(const float *__restrict__ D, float *__restrict__ out, int Ca, int Cb, int ntaps, int nsplit,
@@ -880,6 +859,9 @@ wgrad_finish_wide_kernel(const float *__restrict__ D, float *__restrict__ out, l
     }
 }
 
+// ----------------------------------------------------------------------------------------
+// host side
+// ----------------------------------------------------------------------------------------
 static void launch_wgrad_finish(const float *D, float *out, int Ca, int Cb, int ntaps, int nsplit, hipStream_t s, int acc = 0) {
     const long AB = (long)Ca * Cb, elems = AB * ntaps;
     if (nsplit > 64 && (AB + 63) / 64 <= 0x7fffffffL && ntaps <= 65535)
@@ -890,6 +872,15 @@ static void launch_wgrad_finish(const float *D, float *out, int Ca, int Cb, int 
         wgrad_finish_kernel<<<stream_grid(elems, 256), 256, 0, s>>>(D, out, Ca, Cb, ntaps, nsplit, elems, acc);
 }
 
+// U (channels a, whose pixels are the K axis) and V (channels b): the gradient of the output [N,Hout,Wout,Cout] and the
+// input [N,Hin,Win,Cin] -- for ConvTranspose2d the other way round.
+template <class Geom> static void orient_uv(const ir2rgb_conv_desc *d, Geom *g) {
+    g->N = d->N;
+    if (!d->transposed) { g->Hq = d->Hout; g->Wq = d->Wout; g->Hv = d->Hin; g->Wv = d->Win; g->Ca = d->Cout; g->Cb = d->Cin; }
+    else                { g->Hq = d->Hin; g->Wq = d->Win; g->Hv = d->Hout; g->Wv = d->Wout; g->Ca = d->Cin; g->Cb = d->Cout; }
+}
+
+// The one-tap kernel, which runs every valid descriptor: its plan is also the descriptor's validation.
 static int plan(const ir2rgb_conv_desc *d, WgradGeom *g) {
     if (!d || d->N < 1 || d->Cin < 8 || d->Cout < 8 || (d->Cin % 8) || (d->Cout % 8) || d->kh < 1 || d->kw < 1 ||
         d->stride_h < 1 || d->stride_w < 1 || d->pad_h < 0 || d->pad_w < 0)
@@ -897,12 +888,7 @@ static int plan(const ir2rgb_conv_desc *d, WgradGeom *g) {
     if (d->dtype != IR2RGB_BF16 && d->dtype != IR2RGB_F16) return IR2RGB_ENOSUP;
     if (d->transposed && d->pad_mode != 0) return IR2RGB_ENOSUP;
     *g = WgradGeom{};
-    g->N = d->N;
-    if (!d->transposed) {  // U = grad output [N,Hout,Wout,Cout], V = input [N,Hin,Win,Cin]
-        g->Hq = d->Hout; g->Wq = d->Wout; g->Hv = d->Hin; g->Wv = d->Win; g->Ca = d->Cout; g->Cb = d->Cin;
-    } else {               // U = input [N,Hin,Win,Cin], V = grad output [N,Hout,Wout,Cout]
-        g->Hq = d->Hin; g->Wq = d->Win; g->Hv = d->Hout; g->Wv = d->Wout; g->Ca = d->Cin; g->Cb = d->Cout;
-    }
+    orient_uv(d, g);
     g->stride_y = d->stride_h; g->stride_x = d->stride_w; g->pad_mode = d->pad_mode;
     g->nty = d->kh; g->ntx = d->kw; g->dy0 = -d->pad_h; g->dx0 = -d->pad_w;
     long Q = (long)g->N * g->Hq * g->Wq;
@@ -931,9 +917,32 @@ static int plan(const ir2rgb_conv_desc *d, WgradGeom *g) {
     return IR2RGB_OK;
 }
 
+static bool plan9(const ir2rgb_conv_desc *d, Wgrad9Geom *g) {
+    if (d->transposed || d->kh != 3 || d->kw != 3 || d->stride_h != 1 || d->stride_w != 1 || d->pad_h != 1 || d->pad_w != 1)
+        return false;
+    if (d->Hout != d->Hin || d->Wout != d->Win || (d->Win % 64) || (d->Cin % 64) || (d->Cout % 64) || d->Hin < 2) return false;
+    const long Q = (long)d->N * d->Hin * d->Win;
+    if (Q * d->Cout * 2 >= (1L << 31) || Q * d->Cin * 2 >= (1L << 31)) return false;
+    *g = Wgrad9Geom{};
+    g->N = d->N; g->H = d->Hin; g->W = d->Win; g->Ca = d->Cout; g->Cb = d->Cin; g->pad_mode = d->pad_mode;
+    g->segs = d->Win / 64;
+    g->ksteps = (int)(Q / 64);
+    g->u_bytes = (unsigned)(Q * d->Cout * 2); g->v_bytes = (unsigned)(Q * d->Cin * 2);
+    // one workgroup per CU: split K until ~256 workgroups exist, keeping >= 8 K-steps per split
+    const long tiles = (long)(d->Cout / 64) * (d->Cin / 64);
+    long ks = (256 + tiles - 1) / tiles;
+    if (ks > g->ksteps / 8) ks = g->ksteps / 8;
+    if (ks < 1) ks = 1;
+    if (ks > 256) ks = 256;
+    g->ksplit = (int)ks;
+    return true;
+}
+
 // k x 1 / 1 x k layers on conv_wgrad_line_kernel: 7x1, 1x7 (stride 1 along the taps' axis is not required: the taps run
 // along y for k x 1, where the stride enters the row index) and the stride-2 4x1; 64-multiples on both channel axes.
-static bool plan_line(const ir2rgb_conv_desc *d, WgradLineGeom *g) {
+// 7x1 at stride 1 and 4x1 at stride 2 have a ring kernel of their own (conv_wgrad_col_kernel).
+enum LineForm { LINE_3X3S2, LINE_COL7, LINE_COL4S2, LINE_7X1, LINE_1X7, LINE_4X1 };
+static bool plan_line(const ir2rgb_conv_desc *d, WgradLineGeom *g, LineForm *form) {
     if ((d->Cin % 64) || (d->Cout % 64)) return false;
     // the stride-2 3x3 layers (measured against the one-tap kernel, us at the training sizes: 64->128 @512x1024 49 vs 60, 512->1024 @64x128 54 vs 60,
     // 1024->512 transposed 53 vs 58, 128->64 transposed 49 vs 56 -- but 128->256 52 vs 43, 256->512 48 vs 43: every 64 x 64
@@ -947,13 +956,9 @@ static bool plan_line(const ir2rgb_conv_desc *d, WgradLineGeom *g) {
     if (k4x1 && d->pad_w != 0) return false;
     if (d->pad_mode != 0 && d->pad_mode != 1) return false;
     if (d->pad_mode == 1 && (d->pad_h >= d->Hin || d->pad_w >= d->Win)) return false;
+    *form = k3s2 ? LINE_3X3S2 : k7x1 ? (d->stride_h == 1 ? LINE_COL7 : LINE_7X1) : k1x7 ? LINE_1X7 : d->stride_h == 2 ? LINE_COL4S2 : LINE_4X1;
     *g = WgradLineGeom{};
-    g->N = d->N;
-    if (!d->transposed) {   // U = gradient of the output (a = cout), V = input (b = cin)
-        g->Hq = d->Hout; g->Wq = d->Wout; g->Hv = d->Hin; g->Wv = d->Win; g->Ca = d->Cout; g->Cb = d->Cin;
-    } else {                // ConvTranspose2d: U = input (a = cin), V = gradient of the output (b = cout)
-        g->Hq = d->Hin; g->Wq = d->Win; g->Hv = d->Hout; g->Wv = d->Wout; g->Ca = d->Cin; g->Cb = d->Cout;
-    }
+    orient_uv(d, g);
     const long Q = (long)d->N * g->Hq * g->Wq, Pv = (long)d->N * g->Hv * g->Wv;
     if (Q * g->Ca * 2 >= (1L << 31) || Pv * g->Cb * 2 >= (1L << 31)) return false;
     g->stride_y = d->stride_h; g->pad_mode = d->pad_mode; g->dy0 = -d->pad_h; g->dx0 = -d->pad_w;
@@ -974,30 +979,80 @@ static bool plan_line(const ir2rgb_conv_desc *d, WgradLineGeom *g) {
 }
 
 template <int DT>
-static void launch_line(const ir2rgb_conv_desc *d, const WgradLineGeom &g, const uint16_t *U, const uint16_t *V, float *D, hipStream_t s) {
-    const unsigned grid = (unsigned)((long)g.ksplit * (g.Ca / 64) * (g.Cb / 64));
-    // (7x1 / 4x1 at another stride than the ring kernel's: the row-major line kernel)
-    if (d->kh == 3 && d->kw == 3) conv_wgrad_line_kernel<DT, 3, 3, 2><<<grid, 512, 0, s>>>(U, V, D, g);
-    else if (d->kh == 7 && d->stride_h == 1) conv_wgrad_col_kernel<DT, 7, 1><<<grid, 512, 0, s>>>(U, V, D, g);
-    else if (d->kh == 4 && d->stride_h == 2) conv_wgrad_col_kernel<DT, 4, 2><<<grid, 512, 0, s>>>(U, V, D, g);
-    else if (d->kh == 7) conv_wgrad_line_kernel<DT, 7, 1><<<grid, 512, 0, s>>>(U, V, D, g);
-    else if (d->kw == 7) conv_wgrad_line_kernel<DT, 1, 7><<<grid, 512, 0, s>>>(U, V, D, g);
-    else conv_wgrad_line_kernel<DT, 4, 1><<<grid, 512, 0, s>>>(U, V, D, g);
+static void launch_line(LineForm form, const WgradLineGeom &g, const uint16_t *U, const uint16_t *V, float *D, hipStream_t s) {
+    auto launch = [&](auto kernel) { kernel<<<(unsigned)((long)g.ksplit * (g.Ca / 64) * (g.Cb / 64)), 512, 0, s>>>(U, V, D, g); };
+    switch (form) {
+        case LINE_3X3S2: launch(conv_wgrad_line_kernel<DT, 3, 3, 2>); break;
+        case LINE_COL7: launch(conv_wgrad_col_kernel<DT, 7, 1>); break;
+        case LINE_COL4S2: launch(conv_wgrad_col_kernel<DT, 4, 2>); break;
+        case LINE_7X1: launch(conv_wgrad_line_kernel<DT, 7, 1>); break;
+        case LINE_1X7: launch(conv_wgrad_line_kernel<DT, 1, 7>); break;
+        case LINE_4X1: launch(conv_wgrad_line_kernel<DT, 4, 1>); break;
+    }
 }
 
-extern "C" long ir2rgb_conv2d_wgrad_workspace_elems(const ir2rgb_conv_desc *d) {
-    WgradGeom g;
-    int rc = plan(d, &g);
+// ---- the route: which kernel computes a descriptor's weight gradient, with which split and workspace ----
+enum WgradKernel { WGRAD_ONETAP, WGRAD_NINE, WGRAD_LINE };
+struct WgradRoute {
+    WgradKernel kernel;
+    WgradGeom g;                // WGRAD_ONETAP
+    Wgrad9Geom g9;              // WGRAD_NINE
+    WgradLineGeom gl;           // WGRAD_LINE, in the form `line`
+    LineForm line;
+    int Ca, Cb, ksplit;         // of the kernel that runs
+    long workspace_elems;       // ksplit slabs of taps * Ca * Cb floats; the unsplit nine-tap form writes dw itself (4: never empty)
+};
+
+static int wgrad_route(const ir2rgb_conv_desc *d, bool accumulate, WgradRoute *r) {
+    const int rc = plan(d, &r->g);
     if (rc) return rc;
-    Wgrad9Geom g9;
-    if (plan9(d, &g9)) return g9.ksplit > 1 ? (long)g9.ksplit * 9 * g9.Ca * g9.Cb : 4;
-    WgradLineGeom gl;
-    if (plan_line(d, &gl)) return (long)gl.ksplit * d->kh * d->kw * gl.Ca * gl.Cb;
-    return (long)g.ksplit * d->kh * d->kw * g.Ca * g.Cb;
+    // accumulate mode (a parameter used several times per pass: the discriminators) sums in the finish pass; the nine-tap
+    // kernel's direct-write form has no such pass, so those layers take the one-tap kernel
+    if (!accumulate && plan9(d, &r->g9)) { r->kernel = WGRAD_NINE; r->Ca = r->g9.Ca; r->Cb = r->g9.Cb; r->ksplit = r->g9.ksplit; }
+    else if (plan_line(d, &r->gl, &r->line)) { r->kernel = WGRAD_LINE; r->Ca = r->gl.Ca; r->Cb = r->gl.Cb; r->ksplit = r->gl.ksplit; }
+    else { r->kernel = WGRAD_ONETAP; r->Ca = r->g.Ca; r->Cb = r->g.Cb; r->ksplit = r->g.ksplit; }
+    r->workspace_elems = r->kernel == WGRAD_NINE && r->ksplit == 1 ? 4 : (long)r->ksplit * d->kh * d->kw * r->Ca * r->Cb;
+    return IR2RGB_OK;
 }
+
+static long wgrad_workspace(const ir2rgb_conv_desc *d, bool accumulate) {
+    WgradRoute r;
+    const int rc = wgrad_route(d, accumulate, &r);
+    return rc ? rc : r.workspace_elems;
+}
+extern "C" long ir2rgb_conv2d_wgrad_workspace_elems(const ir2rgb_conv_desc *d) { return wgrad_workspace(d, false); }
+extern "C" long ir2rgb_conv2d_wgrad_acc_workspace_elems(const ir2rgb_conv_desc *d) { return wgrad_workspace(d, true); }
 
 static int wgrad_impl(const ir2rgb_conv_desc *d, const void *x, const void *gy, float *dw, float *workspace, void *stream,
-                      int acc);
+                      int acc) {
+    WgradRoute r;
+    const int rc = wgrad_route(d, acc != 0, &r);
+    if (rc) return rc;
+    if ((((uintptr_t)x | (uintptr_t)gy) & 15) || !dw || !workspace) return IR2RGB_EALIGN;
+    if (r.kernel == WGRAD_NINE && (((uintptr_t)dw | (uintptr_t)workspace) & 15)) return IR2RGB_EALIGN;
+    hipStream_t s = as_stream(stream);
+    const int ntaps = d->kh * d->kw;
+    const uint16_t *U = (const uint16_t *)(d->transposed ? x : gy), *V = (const uint16_t *)(d->transposed ? gy : x);
+    with_dtype(d->dtype, [&](auto dt) {
+        if (r.kernel == WGRAD_NINE) {
+            const unsigned grid9 = (unsigned)((long)r.ksplit * (r.Ca / 64) * (r.Cb / 64));
+            conv_wgrad3x3_kernel<dt.value><<<grid9, 512, 0, s>>>(U, V, r.ksplit > 1 ? workspace : dw, r.g9);
+        } else if (r.kernel == WGRAD_LINE) {    // k x 1 / 1 x k layers: all taps of a 64 x 64 tile per workgroup
+            launch_line<dt.value>(r.line, r.gl, U, V, workspace, s);
+        } else {
+            const WgradGeom &g = r.g;
+            const unsigned grid = (unsigned)((long)g.ksplit * ((ntaps + g.tpb - 1) / g.tpb) * ((g.Ca + 127) / 128) * ((g.Cb + 127) / 128));
+            conv_wgrad_kernel<dt.value><<<grid, 512, 0, s>>>(U, V, workspace, g);
+        }
+    });
+    if (r.kernel != WGRAD_NINE) {
+        launch_wgrad_finish(workspace, dw, r.Ca, r.Cb, ntaps, r.ksplit, s, acc);
+    } else if (r.ksplit > 1) {
+        const long n4 = (long)ntaps * r.Ca * r.Cb / 4;
+        wgrad_sum_kernel<<<stream_grid(n4, 256), 256, 0, s>>>((const float4 *)workspace, (float4 *)dw, n4, r.ksplit);
+    }
+    return ir2rgb_launch_status();
+}
 
 extern "C" int ir2rgb_conv2d_wgrad(const ir2rgb_conv_desc *d, const void *x, const void *gy, float *dw,
                                    float *workspace, void *stream) {
@@ -1007,50 +1062,4 @@ extern "C" int ir2rgb_conv2d_wgrad(const ir2rgb_conv_desc *d, const void *x, con
 extern "C" int ir2rgb_conv2d_wgrad_acc(const ir2rgb_conv_desc *d, const void *x, const void *gy, float *dw,
                                        float *workspace, void *stream) {
     return wgrad_impl(d, x, gy, dw, workspace, stream, 1);
-}
-
-extern "C" long ir2rgb_conv2d_wgrad_acc_workspace_elems(const ir2rgb_conv_desc *d) {
-    WgradGeom g;
-    int rc = plan(d, &g);
-    if (rc) return rc;
-    WgradLineGeom gl;
-    if (plan_line(d, &gl)) return (long)gl.ksplit * d->kh * d->kw * gl.Ca * gl.Cb;
-    return (long)g.ksplit * d->kh * d->kw * g.Ca * g.Cb;       // else always the one-tap kernel's slabs (see wgrad_impl)
-}
-
-static int wgrad_impl(const ir2rgb_conv_desc *d, const void *x, const void *gy, float *dw, float *workspace, void *stream,
-                      int acc) {
-    WgradGeom g;
-    int rc = plan(d, &g);
-    if (rc) return rc;
-    if ((((uintptr_t)x | (uintptr_t)gy) & 15) || !dw || !workspace) return IR2RGB_EALIGN;
-    hipStream_t s = as_stream(stream);
-    const int ntaps = d->kh * d->kw;
-    const long elems = (long)ntaps * g.Ca * g.Cb;
-    Wgrad9Geom g9;
-    // accumulate mode (a parameter used several times per pass: the discriminators) sums in the finish pass of the
-    // one-tap kernel; the nine-tap kernel's direct-write form has no such pass, so those layers take the one-tap kernel
-    if (!acc && plan9(d, &g9)) {
-        if (((uintptr_t)dw | (uintptr_t)workspace) & 15) return IR2RGB_EALIGN;
-        float *dst = g9.ksplit > 1 ? workspace : dw;
-        const unsigned grid9 = (unsigned)((long)g9.ksplit * (g9.Ca / 64) * (g9.Cb / 64));
-        if (d->dtype == IR2RGB_BF16) conv_wgrad3x3_kernel<IR2RGB_BF16><<<grid9, 512, 0, s>>>((const uint16_t *)gy, (const uint16_t *)x, dst, g9);
-        else conv_wgrad3x3_kernel<IR2RGB_F16><<<grid9, 512, 0, s>>>((const uint16_t *)gy, (const uint16_t *)x, dst, g9);
-        if (g9.ksplit > 1)
-            wgrad_sum_kernel<<<stream_grid(elems / 4, 256), 256, 0, s>>>((const float4 *)workspace, (float4 *)dw, elems / 4, g9.ksplit);
-        return ir2rgb_launch_status();
-    }
-    const uint16_t *U = (const uint16_t *)(d->transposed ? x : gy), *V = (const uint16_t *)(d->transposed ? gy : x);
-    WgradLineGeom gl;
-    if (plan_line(d, &gl)) {        // k x 1 / 1 x k layers: all taps of a 64 x 64 tile per workgroup
-        if (d->dtype == IR2RGB_BF16) launch_line<IR2RGB_BF16>(d, gl, U, V, workspace, s);
-        else launch_line<IR2RGB_F16>(d, gl, U, V, workspace, s);
-        launch_wgrad_finish(workspace, dw, gl.Ca, gl.Cb, ntaps, gl.ksplit, s, acc);
-        return ir2rgb_launch_status();
-    }
-    const unsigned grid = (unsigned)((long)g.ksplit * ((ntaps + g.tpb - 1) / g.tpb) * ((g.Ca + 127) / 128) * ((g.Cb + 127) / 128));
-    if (d->dtype == IR2RGB_BF16) conv_wgrad_kernel<IR2RGB_BF16><<<grid, 512, 0, s>>>(U, V, workspace, g);
-    else conv_wgrad_kernel<IR2RGB_F16><<<grid, 512, 0, s>>>(U, V, workspace, g);
-    launch_wgrad_finish(workspace, dw, g.Ca, g.Cb, ntaps, g.ksplit, s, acc);
-    return ir2rgb_launch_status();
 }

@@ -62,23 +62,23 @@ statistics row; tests/test_edge_conv_cpu.py holds the library's host queries aga
   an odd co_off with Cout % 4 != 0.  The replay asserts that nothing outside the slice is written.
 * borders: reflection with pad < H <= 2 * pad per axis, Hout / Wout / the whole output of one pixel, zero padding
   larger than the image, a tile that spans two samples.
-* make_plan's sub-pixel classes and ir2rgb_conv2d_fwd_ws: 3x3 (output_padding 0 / 1 / mixed) and 4x4 at stride 2,
+* make_plan's sub-pixel classes and launch_classes: 3x3 (output_padding 0 / 1 / mixed) and 4x4 at stride 2,
   4x1 at stride (2, 1) (two classes), odd outputs (classes of different Hsub / Wsub), a 1 x 1 input, per-class
   workgroup counts of 1 and 2 (the (nwg + 7) & ~7 padding blocks), thin Cout, tp_all = 64, 64 because wg128 <= 320,
   and 128; a transposed layer with a single class (stride 1, and the 1 x 1 output) runs conv_igemm_kernel.
-* conv_dot_ok: Cin 512 / 1024, 1x1 / 4x4, P = 1, 3, 5, 18 and 8195 (over the 8192-wave cap), a channel-slice input;
-  with statistics the same descriptor runs conv_igemm_kernel (``named`` keeps what the query, which sees the descriptor
-  alone, answers).
+* conv_dot_ok (through conv_route): Cin 512 / 1024, 1x1 / 4x4, P = 1, 3, 5, 18 and 8195 (over the 8192-wave cap), a
+  channel-slice input; with statistics conv_route sends the same descriptor to conv_igemm_kernel (``named`` keeps what
+  the query, which asks conv_route for a launch without bias and statistics, answers).
 * conv3x3p_plan (conv3x3_patch.hip): variants 1 .. 4, each at padding 0, 1 and 2 (2 also reflected: two pixels deep),
   pad_mode 0 / 1 / 2, odd Hout, 200 tiles against 199 (conv_igemm_kernel); variants 3 and 4 through the workspace of
   "fwd_ws".
 * conv1x7_thin_plan: Cin 64 / 128, Cout 1 .. 32 (1 and 3 inside ldy = 4: the plan wants ldy % 4 == 0), W = 4, 5, 127,
-  129, 514 segments on 512 workgroups; with a bias or statistics the general kernel.
+  129, 514 segments on 512 workgroups; with a bias or statistics conv_route takes the general kernel.
 * conv7x1_col_plan: Cout 64 / 128, H = 4, 7, 9, W = 1, 31, 33, N = 2, a channel slice, 540 tiles on 512 workgroups.
 
 EDGE_WGRAD (entry "wgrad"; ``splits`` = workspace slabs of the plain call, 0 = written directly) from wgrad_mfma.hip.
 replay_wgrad runs every record plain and accumulating; the accumulating call of a nine-tap record takes the one-tap
-kernel (wgrad_impl), so each of those records covers both.
+kernel (wgrad_route), so each of those records covers both.
 
 * plan: tpb = 2 with an odd tap count (3x3 at Cb <= 64) against tpb = 1, Ca / Cb of 8 .. 200, Q = 35 < 64 and
   Q % 64 != 0, a geometry the cost model splits (16 and 8 slabs) and ones it cannot (< 8 K-steps), stride 2 on odd
@@ -86,7 +86,7 @@ kernel (wgrad_impl), so each of those records covers both.
 * launch_wgrad_finish: <= 16 taps (tiled), 25 / 49 taps (the gather form), > 64 splits (wide).
 * plan9: Win = 64 / 128 / 192, H = 2 and odd H, ksplit == 1 (Q / 64 < 16: direct write) and > 1 (wgrad_sum_kernel),
   pad_mode 0 / 1, N = 2, 128 -> 192 channels.
-* plan_line / launch_line: 7x1 at stride 1 (column kernel) and 2 (line kernel), 4x1 at stride 2 (column) and 1 (line),
+* plan_line (which picks launch_line's LineForm): 7x1 at stride 1 (column kernel) and 2 (line kernel), 4x1 at stride 2 (column) and 1 (line),
   1x7, 3x3 / stride 2 with tl = 1, 2, 128 (also transposed) and tl = 4 (the one-tap kernel); Wq % 64 != 0, fewer than
   8 K-steps, a short last split, 65 splits, reflection on the taps' axis with pad < H <= 2 * pad.
 """

@@ -66,7 +66,7 @@ def digest(obj, tmp):
     rows = []
     for name, pretty in zip(names, demangle(names)):
         body = bodies[name]
-        while body and body[-1] in ("s_nop 0", "s_code_end"):      # padding behind s_endpgm
+        while body and body[-1] in ("s_nop 0", "s_code_end", "..."):   # padding behind s_endpgm ("...": objdump's run of zero bytes)
             body.pop()
         ops = [i.split()[0] for i in body]
         n = lambda pred: sum(1 for i, o in zip(body, ops) if pred(i, o))  # noqa: E731
