@@ -416,6 +416,58 @@ int ir2rgb_adam_step(const void *table, const void *blocks, int nblocks, float l
                      int step, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Dynamic loss scaling for f16 training, decided on the device (loss_scale.hip).  The loss is multiplied by
+ * `scale` before backward(); the step then (1) checks the scaled gradient for inf / NaN, (2) takes the Adam step
+ * on g * inv_scale or leaves p, m, v and the step count alone, (3) updates the scale by torch._amp_update_scale_'s
+ * rule.  The host never reads the decision: the step count, the coefficients of the step being taken and the
+ * scale live in two device blocks, laid out as the structs below (plain C layout; ir2rgb_loss_scale_state_bytes
+ * answers their sizes, so that a caller need not repeat them).
+ *   table, blocks, nblocks : as for ir2rgb_adam_step
+ *   partial   : device scratch of ir2rgb_grad_check_partial_bytes(nblocks) bytes, 8-byte aligned: one
+ *               { double sumsq; float nonfinite; float reserved; } row per workgroup, summed in row order
+ *   opt_state : ir2rgb_adam_state, 8-byte aligned, one per optimizer;  scaler_state : ir2rgb_loss_scale_state,
+ *               4-byte aligned, one per trainer.  Both are written by the kernels only.
+ * IR2RGB_EINVAL: a NULL pointer, nblocks < 0, a beta outside [0, 1), count outside [0, 8], growth_interval < 0,
+ * growth < 1, backoff outside (0, 1]; IR2RGB_EALIGN: partial / opt_state / opt_states off an 8-byte boundary,
+ * scaler_state off a 4-byte one.  Both before any launch.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct ir2rgb_adam_state {
+    int step;            /* successful (not skipped) steps so far */
+    float step_size, beta1, beta2, omb1, omb2, bc2_sqrt, eps;   /* coefficients of the step being taken (AdamCoef) */
+    float found_inf;     /* 1 when the last checked gradient held an inf or a NaN, else 0 */
+    int reserved;
+    double grad_sumsq;   /* sum of squares of the last checked gradient, unscaled (x inv_scale^2) */
+} ir2rgb_adam_state;
+
+typedef struct ir2rgb_loss_scale_state {
+    float scale, inv_scale;   /* inv_scale = (float)(1.0 / (double)scale) */
+    int growth_tracker;       /* consecutive unskipped windows since the last change of the scale */
+    int skipped;              /* windows skipped so far (for logging) */
+} ir2rgb_loss_scale_state;
+
+/* Size in bytes of ir2rgb_adam_state (which 0) or ir2rgb_loss_scale_state (which 1); IR2RGB_EINVAL otherwise. */
+long ir2rgb_loss_scale_state_bytes(int which);
+long ir2rgb_grad_check_partial_bytes(int nblocks);
+/* Two launches.  Every workgroup of the first reads its chunk of g only (16-byte loads where adam_kernel takes them) and
+ * writes its partial row: finiteness decided per element from the value, squares accumulated in double in a fixed
+ * order, no atomics.  The second (one workgroup) sums the rows and writes found_inf and
+ * grad_sumsq = sumsq * inv_scale^2; if the gradient is finite it advances `step` and evaluates that step's
+ * coefficients in double from lr, beta1, beta2, eps -- the expressions of ir2rgb_adam_step's host code.
+ * nblocks 0: the second launch alone (a finite, empty gradient). */
+int ir2rgb_grad_check(const void *table, const void *blocks, int nblocks, void *partial, void *opt_state,
+                      const void *scaler_state, float lr, float beta1, float beta2, float eps, void *stream);
+/* ir2rgb_adam_step on g * inv_scale with the coefficients ir2rgb_grad_check left in opt_state; touches nothing when
+ * opt_state's found_inf is set. */
+int ir2rgb_adam_step_scaled(const void *table, const void *blocks, int nblocks, const void *opt_state,
+                            const void *scaler_state, void *stream);
+/* opt_states: device array of `count` (<= 8) addresses of the ir2rgb_adam_state blocks stepped this window.  Any
+ * found_inf: scale *= backoff, tracker 0, skipped += 1.  Otherwise the tracker is incremented and, when it reaches
+ * growth_interval, reset, with scale *= growth unless that product is not finite.  growth_interval 0: a static
+ * scale -- the scale and the tracker never change, skipped still counts. */
+int ir2rgb_loss_scale_update(void *scaler_state, const void *opt_states, int count, float growth, float backoff,
+                             int growth_interval, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Frame I/O of frame-by-frame inference (frame_io.hip): the 8-bit image boundary and the recurrence state
  * as device-resident histories.  A history is fp32 [T][C][H][W], oldest frame first; both entry points move
  * slots 1..T-1 down to 0..T-2 in place (same element index, same thread) and fill slot T-1.  Rows whose

@@ -43,6 +43,17 @@ class PackJob(ctypes.Structure):
 
 _pjob = ctypes.POINTER(PackJob)
 
+
+class AdamState(ctypes.Structure):
+    """ir2rgb_adam_state of include/ir2rgb_hip.h (device-resident; the size comes from ir2rgb_loss_scale_state_bytes(0))."""
+    _fields_ = [("step", c_int)] + [(n, c_float) for n in ("step_size", "beta1", "beta2", "omb1", "omb2", "bc2_sqrt", "eps",
+                                                           "found_inf")] + [("reserved", c_int), ("grad_sumsq", ctypes.c_double)]
+
+
+class LossScaleState(ctypes.Structure):
+    """ir2rgb_loss_scale_state of include/ir2rgb_hip.h (ir2rgb_loss_scale_state_bytes(1))."""
+    _fields_ = [("scale", c_float), ("inv_scale", c_float), ("growth_tracker", c_int), ("skipped", c_int)]
+
 # name -> (restype, argtypes)
 PROTOTYPES = {
     "ir2rgb_version": (ctypes.c_char_p, []),
@@ -98,7 +109,12 @@ PROTOTYPES = {
     "ir2rgb_loss_multi_bwd": (c_int, [_pitem, c_int, c_int, P, P]),
     "ir2rgb_adam_chunk_elems": (c_int, []),
     "ir2rgb_adam_step": (c_int, [P, P, c_int, c_float, c_float, c_float, c_float, c_int, P]),
-    "ir2rgb_frame_push_u8": (c_int, [P, P, P] + [c_int] * 5 + [P]),
+    "ir2rgb_loss_scale_state_bytes": (c_long, [c_int]),
+    "ir2rgb_grad_check_partial_bytes": (c_long, [c_int]),
+    "ir2rgb_grad_check": (c_int, [P, P, c_int, P, P, P, c_float, c_float, c_float, c_float, P]),
+    "ir2rgb_adam_step_scaled": (c_int, [P, P, c_int, P, P, P]),
+    "ir2rgb_loss_scale_update": (c_int, [P, P, c_int, c_float, c_float, c_int, P]),
+    "ir2rgb_frame_push_u8":(c_int, [P, P, P] + [c_int] * 5 + [P]),
     "ir2rgb_frame_finish_u8": (c_int, [P, P, P] + [c_int] * 3 + [P]),
     "ir2rgb_video_metrics_workspace_bytes": (c_long, [c_int] * 3),
     "ir2rgb_video_metrics_tile": (c_int, [c_int]),

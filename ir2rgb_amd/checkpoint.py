@@ -3,6 +3,8 @@
     {label}_net_{G0,G1,...,D,D_T0,D_T1,...}.pth   plain ``state_dict`` per network
                                                   (models/utils.py:6-9; generator.py:292-294;
                                                   discriminator.py:250-253)
+    {label}_loss_scaler.pth                       the loss scaler's state when the trainer has one (no reference
+                                                  counterpart: apex keeps its scale in the amp state)
     iter.txt                                      "epoch,epoch_iter" written with np.savetxt(fmt='%d')
                                                   (models/models.py:62-68, :96-110)
 
@@ -83,6 +85,9 @@ def save_trainer(trainer, label, save_dir, epoch=None, epoch_iter=None):
     save_network(trainer.netD, "D", label, save_dir)
     for s, d in enumerate(trainer.netD_T):
         save_network(d, f"D_T{s}", label, save_dir)
+    scaler = getattr(trainer, "loss_scaler", None)
+    if scaler is not None:          # (scale, growth tracker, skipped windows: ir2rgb_amd.optim.LossScaler.state_dict)
+        torch.save(scaler.state_dict(), os.path.join(save_dir, f"{label}_loss_scaler.pth"))
     if epoch is not None:
         write_iter(save_dir, epoch, epoch_iter or 0)
 
@@ -96,4 +101,10 @@ def load_trainer(trainer, label, save_dir, log=print):
     load_network(trainer.netD, "D", label, save_dir, log)
     for s, d in enumerate(trainer.netD_T):
         load_network(d, f"D_T{s}", label, save_dir, log)
+    scaler = getattr(trainer, "loss_scaler", None)
+    path = os.path.join(save_dir, f"{label}_loss_scaler.pth")
+    if scaler is not None and os.path.isfile(path):
+        scaler.load_state_dict(torch.load(path, map_location="cpu", weights_only=True))
+    elif scaler is not None:
+        log(f"{path} not exists yet!")
     return read_iter(save_dir)

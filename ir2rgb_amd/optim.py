@@ -5,8 +5,13 @@ which is what the reference builds (generator.py / discriminator.py ``torch.opti
 betas=(opt.beta1, 0.999))``).  Moments live in two flat fp32 buffers; a device table of
 {param, grad, exp_avg, exp_avg_sq, numel} rows is refreshed with the current gradient pointers before
 every step (one small asynchronous copy from pinned memory).
+
+f16 training scales its losses (``LossScaler``; libir2rgb_hip.so: loss_scale.hip): ``FusedAdam.step(scaler)`` then checks
+the scaled gradient on the device, steps on ``g * inv_scale`` or skips, and ``LossScaler.update`` applies
+``torch._amp_update_scale_``'s rule -- the decision, the step count and the scale never visit the host.
 """
 import ctypes
+import math
 
 import numpy as np
 import torch
@@ -52,6 +57,10 @@ class FusedAdam:
         self._blocks = torch.tensor(blocks, dtype=torch.int32, device=dev)
         self._ptrs = [p.data_ptr() for p in self.params]
         self.device = dev
+        self._flip = 0
+        # loss-scaled steps only (scaled_state): ir2rgb_adam_state on the device and the check kernel's partial rows
+        self._state = self._partial = None
+        self._on_device = False          # the step count lives in _state[0] (loss-scaled steps) / in step_count
 
     @property
     def lr(self):
@@ -80,6 +89,7 @@ class FusedAdam:
         """torch.optim.Adam's layout ({'state': {i: {'step', 'exp_avg', 'exp_avg_sq'}}, 'param_groups': [...]}), so a
         checkpoint written here loads into torch.optim.Adam over the same parameter list and vice versa."""
         state = {}
+        self._read_step_count()
         if self.step_count:
             for i in range(len(self.params)):
                 m, v = self.moments(i)
@@ -98,6 +108,7 @@ class FusedAdam:
         if len(steps) > 1:
             raise ValueError("FusedAdam.load_state_dict: parameters with different step counts (one launch updates all)")
         self.step_count = steps.pop() if steps else 0
+        self._on_device = False          # (the next loss-scaled step seeds the device state from step_count)
         with torch.no_grad():
             if not sd["state"]:         # a state saved before the first step: start from zero moments, as torch.optim.Adam does
                 self.exp_avg.zero_()
@@ -113,9 +124,35 @@ class FusedAdam:
         k = self.params[i].numel()
         return self.exp_avg[off:off + k].view_as(self.params[i]), self.exp_avg_sq[off:off + k].view_as(self.params[i])
 
-    @torch.no_grad()
-    def step(self):
-        k = self.step_count & 1
+    def scaled_state(self):
+        """The optimizer's device state of loss-scaled steps (ir2rgb_adam_state as an int32 tensor: ``[0]`` is the count of
+        steps taken, seeded from ``step_count``), created on first use together with the check kernel's partial rows."""
+        if self._state is None:          # allocated once: LossScaler.update keeps its address
+            nbytes = _lib.query("ir2rgb_loss_scale_state_bytes", 0)
+            assert ctypes.sizeof(_lib.AdamState) == nbytes
+            self._state = torch.zeros(nbytes // 4, dtype=torch.int32, device=self.device)
+            nbytes = _lib.query("ir2rgb_grad_check_partial_bytes", self._blocks.shape[0])
+            self._partial = torch.zeros(nbytes // 8, dtype=torch.float64, device=self.device)
+        if not self._on_device:
+            st = _lib.AdamState(step=self.step_count)
+            self._state.copy_(torch.frombuffer(bytearray(bytes(st)), dtype=torch.int32))
+            self._on_device = True
+        return self._state
+
+    def _read_step_count(self):
+        """``step_count`` from the device state when loss-scaled steps have been counting there (synchronises)."""
+        if self._on_device:
+            self.step_count = int(self._state[0].item())
+
+    def grad_stats(self):
+        """(found_inf, unscaled gradient norm) of the last loss-scaled step (synchronises)."""
+        st = _lib.AdamState.from_buffer_copy(self.scaled_state().cpu().numpy().tobytes())
+        return bool(st.found_inf), math.sqrt(st.grad_sumsq) if st.grad_sumsq >= 0 else float("nan")
+
+    def _refresh_table(self):
+        """The current gradient pointers into the device table (one asynchronous copy from pinned memory)."""
+        k = self._flip
+        self._flip ^= 1
         if self._copied[k] is not None:
             self._copied[k].synchronize()
         rows = self._rows_np[k]
@@ -132,12 +169,178 @@ class FusedAdam:
         if self._copied[k] is None:
             self._copied[k] = torch.cuda.Event()
         self._copied[k].record()
-        self.step_count += 1
-        _lib.launch("ir2rgb_adam_step", self.exp_avg, self._rows_dev.data_ptr(), self._blocks.data_ptr(),
-                    self._blocks.shape[0], self.lr, self.betas[0], self.betas[1], self.eps, self.step_count)
+
+    @torch.no_grad()
+    def step(self, scaler=None):
+        """One Adam step.  With a ``LossScaler`` the gradients are those of the scaled loss: they are checked on the
+        device (ir2rgb_grad_check), and the step is taken on ``g * inv_scale`` or -- an inf or NaN anywhere -- not at all
+        (ir2rgb_adam_step_scaled); the host learns neither."""
+        self._refresh_table()
+        nblocks = self._blocks.shape[0]
+        if scaler is None:
+            if self._on_device:              # loss-scaled steps came before: their count moves back to the host
+                self._read_step_count()
+                self._on_device = False
+            self.step_count += 1
+            _lib.launch("ir2rgb_adam_step", self.exp_avg, self._rows_dev.data_ptr(), self._blocks.data_ptr(),
+                        nblocks, self.lr, self.betas[0], self.betas[1], self.eps, self.step_count)
+        else:
+            state = self.scaled_state()
+            _lib.launch("ir2rgb_grad_check", self.exp_avg, self._rows_dev, self._blocks, nblocks, self._partial, state,
+                        scaler.state, self.lr, self.betas[0], self.betas[1], self.eps)
+            _lib.launch("ir2rgb_adam_step_scaled", self.exp_avg, self._rows_dev, self._blocks, nblocks, state, scaler.state)
         # the kernel wrote the parameters behind autograd's back: bump their version counters so that
         # caches keyed on them (the packed MFMA weights of ir2rgb_amd.layers) are refreshed
         torch.autograd.graph.increment_version(self.params)
         if SC.ENABLED:
             for p in self.params:
                 SC.produced(p, "fp32 parameter (Adam step)")
+
+
+def _fp32_exact(x):
+    return float(np.float32(x)) == float(x)
+
+
+class LossScaler:
+    """Loss scale of f16 training, owned by the device (ir2rgb_loss_scale_state: scale, inv_scale, growth tracker, count of
+    skipped windows).  ``scale_tensor`` multiplies every loss before its backward pass; each ``FusedAdam.step(scaler)``
+    unscales, checks and steps or skips; ``update(optimizers)`` then moves the scale as ``torch.amp.GradScaler`` would:
+    times ``backoff_factor`` after a window in which any optimizer saw an inf or NaN, times ``growth_factor`` after
+    ``growth_interval`` windows without one.  ``growth_interval=0`` is a static scale (windows that overflow are still
+    skipped).  None of this synchronises; ``state_dict`` / ``load_state_dict`` / ``stats`` do.  The factors must be
+    exact in fp32 (the kernel receives floats and multiplies in double, as torch does with its doubles)."""
+
+    def __init__(self, device, init_scale=2.0 ** 16, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise ValueError("LossScaler: GPU only (no CPU fallback; loss_scale_update_reference restates the rule)")
+        check_scaler_arguments(init_scale, growth_factor, backoff_factor, growth_interval)
+        self.device = device
+        self.growth_factor, self.backoff_factor, self.growth_interval = float(growth_factor), float(backoff_factor), int(growth_interval)
+        assert ctypes.sizeof(_lib.LossScaleState) == _lib.query("ir2rgb_loss_scale_state_bytes", 1)
+        self.state = torch.zeros(ctypes.sizeof(_lib.LossScaleState) // 4, dtype=torch.float32, device=device)
+        self.scale_tensor = self.state[0]        # 0-dim fp32 view: a device operand of the loss products
+        self._write(init_scale, 0, 0)
+        self._tables = {}
+        self._last = []
+
+    def _write(self, scale, tracker, skipped):
+        scale = float(np.float32(scale))
+        st = _lib.LossScaleState(scale=scale, inv_scale=float(np.float32(1.0 / scale)), growth_tracker=tracker, skipped=skipped)
+        self.state.copy_(torch.frombuffer(bytearray(bytes(st)), dtype=torch.float32))
+
+    def _read(self):
+        return _lib.LossScaleState.from_buffer_copy(self.state.cpu().numpy().tobytes())
+
+    def register(self, optimizers):
+        """The device table of the optimizers' state addresses ``update`` hands the kernel; built once per set of
+        optimizers (a small blocking copy: call it ahead of the loop for an ``update`` that never synchronises)."""
+        key = tuple(id(o) for o in optimizers)
+        if key not in self._tables:
+            if not 1 <= len(optimizers) <= 8:
+                raise ValueError("LossScaler.update: between 1 and 8 optimizers")
+            self._tables[key] = torch.tensor([o.scaled_state().data_ptr() for o in optimizers], dtype=torch.int64,
+                                             device=self.device)
+        return self._tables[key]
+
+    def update(self, optimizers):
+        """Once per window, after the ``step(scaler)`` of every optimizer in ``optimizers``."""
+        optimizers = list(optimizers)
+        table = self.register(optimizers)
+        self._last = optimizers
+        _lib.launch("ir2rgb_loss_scale_update", self.state, self.state, table, len(optimizers), self.growth_factor,
+                    self.backoff_factor, self.growth_interval)
+
+    def stats(self):
+        """{scale, skipped, grad_norms}: the current scale, the windows skipped so far and the unscaled gradient norm each
+        optimizer of the last ``update`` saw (synchronises)."""
+        st = self._read()
+        return {"scale": st.scale, "skipped": st.skipped, "grad_norms": [o.grad_stats()[1] for o in self._last]}
+
+    def state_dict(self):
+        st = self._read()
+        return {"scale": st.scale, "growth_tracker": st.growth_tracker, "skipped": st.skipped,
+                "growth_factor": self.growth_factor, "backoff_factor": self.backoff_factor, "growth_interval": self.growth_interval}
+
+    def load_state_dict(self, sd):
+        check_scaler_arguments(sd["scale"], sd.get("growth_factor", self.growth_factor), sd.get("backoff_factor", self.backoff_factor),
+                               sd.get("growth_interval", self.growth_interval))
+        self.growth_factor = float(sd.get("growth_factor", self.growth_factor))
+        self.backoff_factor = float(sd.get("backoff_factor", self.backoff_factor))
+        self.growth_interval = int(sd.get("growth_interval", self.growth_interval))
+        self._write(sd["scale"], int(sd["growth_tracker"]), int(sd.get("skipped", 0)))
+
+
+def check_scaler_arguments(scale, growth_factor, backoff_factor, growth_interval):
+    if isinstance(scale, bool) or not isinstance(scale, (int, float)) or not math.isfinite(scale) or scale <= 0 or \
+            not math.isfinite(float(np.float32(scale))) or float(np.float32(scale)) == 0.0:
+        raise ValueError(f"loss scale: a positive finite fp32 number, got {scale!r}")
+    if not (growth_factor >= 1.0 and _fp32_exact(growth_factor)) or not (0.0 < backoff_factor <= 1.0 and _fp32_exact(backoff_factor)):
+        raise ValueError("loss scale: growth_factor >= 1 and backoff_factor in (0, 1], both exact in fp32")
+    if isinstance(growth_interval, bool) or not isinstance(growth_interval, int) or growth_interval < 0:
+        raise ValueError("loss scale: growth_interval is a count of windows (0: static scale)")
+
+
+def check_loss_scale_option(value, fused_adam):
+    """Validates the trainer's ``loss_scale`` option -- None, a number (static scale), "dynamic" or a LossScaler -- without
+    touching a device.  -> "none" | "static" | "dynamic" | "instance"."""
+    if value is None:
+        return "none"
+    if isinstance(value, LossScaler):
+        kind = "instance"
+    elif isinstance(value, str):
+        if value != "dynamic":
+            raise ValueError(f"loss_scale: None, a number, \"dynamic\" or a LossScaler, got {value!r}")
+        kind = "dynamic"
+    elif isinstance(value, (int, float)) and not isinstance(value, bool):
+        check_scaler_arguments(value, 2.0, 0.5, 0)
+        kind = "static"
+    else:
+        raise ValueError(f"loss_scale: None, a number, \"dynamic\" or a LossScaler, got {value!r}")
+    if not fused_adam:
+        raise ValueError("loss_scale needs fused_adam=True: the skip decision is taken on the device by ir2rgb_amd.optim.FusedAdam")
+    return kind
+
+
+def make_loss_scaler(value, device):
+    """The LossScaler of a validated ``loss_scale`` option (None for None)."""
+    kind = check_loss_scale_option(value, True)
+    if kind == "none":
+        return None
+    if kind == "instance":
+        return value
+    if kind == "dynamic":
+        return LossScaler(device)
+    return LossScaler(device, init_scale=float(value), growth_interval=0)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# plain-torch restatements, usable on a CPU (what the kernels are tested against; never on the training path)
+def loss_scale_update_reference(scale, growth_tracker, found_inf, growth_factor, backoff_factor, growth_interval):
+    """loss_scale_update_kernel's rule, in place on a 1-element fp32 ``scale`` and int32 ``growth_tracker``;
+    ``found_inf``: any non-zero element means an optimizer skipped.  For ``growth_interval > 0`` this is
+    ``torch._amp_update_scale_`` (products in double, rounded to fp32; a growth that would reach inf is refused but
+    still resets the tracker); ``growth_interval == 0`` leaves both alone.  -> (inv_scale, 1 if the window was skipped)."""
+    found = bool(torch.as_tensor(found_inf).ne(0).any())
+    if growth_interval > 0:
+        if found:
+            scale.copy_((scale.double() * backoff_factor).float())
+            growth_tracker.zero_()
+        else:
+            growth_tracker += 1
+            if int(growth_tracker) == growth_interval:
+                grown = (scale.double() * growth_factor).float()
+                if bool(torch.isfinite(grown).all()):
+                    scale.copy_(grown)
+                growth_tracker.zero_()
+    return (1.0 / scale.double()).float(), int(found)
+
+
+def grad_check_reference(grads, inv_scale):
+    """grad_check_kernel + grad_check_finish_kernel in plain torch: -> (found_inf as 0. / 1., the fp64 sum of squares of
+    the unscaled gradient, the unscaled gradients ``g * inv_scale`` in fp32).  Finiteness is decided per element."""
+    inv = torch.as_tensor(inv_scale, dtype=torch.float32)
+    found = any(not bool(torch.isfinite(g).all()) for g in grads)
+    sumsq = sum((g.double() ** 2).sum() for g in grads) * inv.double() ** 2
+    return (torch.tensor(1.0 if found else 0.0), torch.as_tensor(sumsq, dtype=torch.float64),
+            [g.float() * inv for g in grads])

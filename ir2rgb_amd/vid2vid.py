@@ -29,7 +29,7 @@ from .flownet import FlowNet
 from .frames import FrameHistory
 from .losses import _SplitGroupsFn, drop_grad_dsts, fused_losses, split_groups  # noqa: F401  (re-exported)
 from .networks import SLOT_D_TEMPORAL, SLOT_FLOWNET, _Branch, side_stream
-from .optim import FusedAdam
+from .optim import FusedAdam, LossScaler, check_loss_scale_option, make_loss_scaler  # noqa: F401
 
 DEFAULTS = dict(  # options/base_options.py, options/train_options.py
     input_nc=3, output_nc=3, n_input_gen_frames=3, first_layer_gen_filters=128, gen_network="composite", gen_ds_layers=3,
@@ -45,6 +45,8 @@ DEFAULTS = dict(  # options/base_options.py, options/train_options.py (SURVEY se
     allreduce_chunk_elems=32 * 1024 * 1024,   # fp32 elements per gradient all-reduce (128 MB)
     batched_D=True,      # (with shared_fake_forward) real | generated | raw frames go through a discriminator as ONE batch of sample groups
     fused_adam=True,     # one-launch HIP Adam (ir2rgb_amd.optim); False = torch.optim.Adam(foreach=True)
+    loss_scale=None,     # f16 training: a number (static scale), "dynamic" (2^16, halved on overflow, doubled after 2000 clean
+                         # windows) or an ir2rgb_amd.optim.LossScaler; overflowed windows are skipped on the device.  Needs fused_adam
     fused_losses=True,   # grouped HIP loss kernels (ir2rgb_amd.losses); False = the same terms through torch ops
     batched_repack=True,  # all packed weight copies refreshed by one launch after the optimizer steps (layers.WeightRepacker)
     build_flow_net=True,  # False: trainer.flow_net is left None for the caller to set (tests plug a stand-in for FlowNet2)
@@ -123,6 +125,7 @@ class Vid2VidTrainer:
     def __init__(self, device, world_size=1, seed=0, **overrides):
         o = dict(DEFAULTS)
         o.update(overrides)
+        check_loss_scale_option(o["loss_scale"], o["fused_adam"])     # (a ValueError before anything is built)
         self.opt, self.device, self.world = o, device, world_size
         tG = o["n_input_gen_frames"]
         self.n_scales, self.t_scales, self.tD = o["n_scales_spatial"], o["n_scales_temporal"], o["n_frames_D"]
@@ -183,6 +186,10 @@ class Vid2VidTrainer:
         self.optimizer_G = make(self.grads_G.params)
         self.optimizer_D = make(self.grads_D.params)
         self.optimizer_D_T = [make(g.params) for g in self.grads_DT]
+        self.loss_scaler = make_loss_scaler(o["loss_scale"], device)
+        if self.loss_scaler is not None:        # the device tables of every window's optimizer set, ahead of the loop
+            for n in range(self.t_scales + 1):
+                self.loss_scaler.register([self.optimizer_G, self.optimizer_D] + self.optimizer_D_T[:n])
         self.repacker = layers.WeightRepacker(list(self.netG) + [self.netD] + list(self.netD_T)) if o["batched_repack"] else None
         self.reset_sequence()
 
@@ -564,6 +571,10 @@ class Vid2VidTrainer:
         # (inputs=...: the engine then runs only the nodes that lead to those tensors, so the
         # discriminators' passes never enter the generator graph)
         batched = shared and self.opt["batched_D"]
+        if self.loss_scaler is not None:
+            # the passes differentiate scale * loss (a device operand: no sync); the callers' losses stay unscaled
+            k = self.loss_scaler.scale_tensor
+            loss_G, loss_D, loss_D_T = loss_G * k, loss_D * k, [l * k for l in loss_D_T]
         with autograd.backward_flags([self.netD] if shared else [], autograd.SKIP_PARAM_GRADS, 2 if batched else None), \
                 autograd.backward_flags(self.netD_T if shared else [], autograd.SKIP_PARAM_GRADS, 1 if batched else None):
             loss_G.backward(retain_graph=shared, inputs=g_inputs)
@@ -593,13 +604,19 @@ class Vid2VidTrainer:
 
     def optimizer_steps(self, n_temporal):
         """The three ``optimizer.step()`` of train_vid2vid.py:104-111, then one launch refreshing every packed weight."""
+        scaler = self.loss_scaler
+        step = (lambda o: o.step()) if scaler is None else (lambda o: o.step(scaler))  # noqa: E731
+        # (world > 1: the averaged gradient is the same on every rank, so every rank takes the same skip decision)
         self.grads_G.wait()
-        self.optimizer_G.step()
+        step(self.optimizer_G)
         self.grads_D.wait()
-        self.optimizer_D.step()
+        step(self.optimizer_D)
         for s in range(n_temporal):
             self.grads_DT[s].wait()
-            self.optimizer_D_T[s].step()
+            step(self.optimizer_D_T[s])
+        if scaler is not None:
+            scaler.update([self.optimizer_G, self.optimizer_D] + self.optimizer_D_T[:n_temporal])
+        # (after a skipped step this re-packs unchanged weights: correct, and not worth a device-side branch)
         if self.repacker is not None:
             self.repacker.run()          # every packed forward / data-gradient weight copy, one launch
 
