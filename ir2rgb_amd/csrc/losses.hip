@@ -124,7 +124,8 @@ loss_multi_bwd_kernel(const LossArgs A, int dt, const float *__restrict__ gout) 
         const long per = (n8 + nb - 1) / nb, q0 = lb * per, q1 = min(n8, q0 + per);
         const uint4 *a = (const uint4 *)it.a, *b = (const uint4 *)it.b;
         uint4 *ga = (uint4 *)it.ga;
-        const uint32_t gp = f2h(g, dt), gn = f2h(-g, dt);
+        // where a == b: sign(0) * g, i.e. +0 for a finite g and NaN for an inf / NaN one (g - g), as torch's product
+        const uint32_t gp = f2h(g, dt), gn = f2h(-g, dt), gz = f2h(g - g, dt);
         for (long q = q0 + threadIdx.x; q < q1; q += 1024) {      // four operand pairs in flight per lane (see the forward)
             uint4 va[4], vb[4];
 #pragma unroll
@@ -141,7 +142,7 @@ loss_multi_bwd_kernel(const LossArgs A, int dt, const float *__restrict__ gout) 
                 for (int j = 0; j < 4; ++j) {
                     const float d0 = h2f((uint16_t)(wa[j] & 0xffff), dt) - h2f((uint16_t)(wb[j] & 0xffff), dt);
                     const float d1 = h2f((uint16_t)(wa[j] >> 16), dt) - h2f((uint16_t)(wb[j] >> 16), dt);
-                    const uint32_t lo = d0 > 0.f ? gp : (d0 < 0.f ? gn : 0u), hi = d1 > 0.f ? gp : (d1 < 0.f ? gn : 0u);
+                    const uint32_t lo = d0 > 0.f ? gp : (d0 < 0.f ? gn : gz), hi = d1 > 0.f ? gp : (d1 < 0.f ? gn : gz);
                     o[j] = lo | (hi << 16);
                 }
                 if (q + 256 * u < q1) ga[q + 256 * u] = make_uint4(o[0], o[1], o[2], o[3]);
@@ -158,7 +159,7 @@ loss_multi_bwd_kernel(const LossArgs A, int dt, const float *__restrict__ gout) 
                 const long img = q / it.chw, hw = (q - img * it.chw) % it.hw;
                 const float mv = m[img * it.hw + hw];
                 const float d = a[q] * mv - (b ? b[q] * mv : 0.f);
-                ga[q] = (d > 0.f ? g : (d < 0.f ? -g : 0.f)) * mv;
+                ga[q] = (d > 0.f ? g : (d < 0.f ? -g : g - g)) * mv;
             }
         }
     }

@@ -59,7 +59,7 @@ bn_finalize_kernel(const float *__restrict__ partial, int rows, int C, double co
     for (int r = 0; r < RG; ++r) { s1 += red[0][r][cl]; s2 += red[1][r][cl]; }
     double mean = s1 / count;
     double var = s2 / count - mean * mean;
-    var = var > 0.0 ? var : 0.0;
+    var = (var > 0.0 || var != var) ? var : 0.0;      // (a NaN variance -- an overflowed forward -- stays NaN)
     float invstd = (float)(1.0 / sqrt(var + (double)eps));
     float g = gamma ? gamma[c] : 1.f, b = beta ? beta[c] : 0.f;
     float sc = g * invstd;
@@ -125,7 +125,7 @@ bn_apply_kernel(const uint4 *__restrict__ x, const float *__restrict__ scale, co
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 float t = h2f((uint16_t)(w[j] >> (16 * h)), DT) * sc[2 * j + h] + sh[2 * j + h];
-                if (act == 1) t = t > 0.f ? t : 0.f;
+                if (act == 1) t = (t > 0.f || t != t) ? t : 0.f;     // torch.relu: NaN stays NaN
                 else if (act == 2) t = t > 0.f ? t : 0.2f * t;
                 if (r1) t += h2f((uint16_t)(a[j] >> (16 * h)), DT);
                 if (r2) t += h2f((uint16_t)(b[j] >> (16 * h)), DT);
@@ -179,7 +179,7 @@ bn_finalize_apply_kernel(const float *__restrict__ partial, int rows, int C, dou
         const double s1 = red[0][0][cl] + red[1][0][cl], s2 = red[0][1][cl] + red[1][1][cl];
         const double mean = s1 / count;
         double var = s2 / count - mean * mean;
-        var = var > 0.0 ? var : 0.0;
+        var = (var > 0.0 || var != var) ? var : 0.0;      // as bn_finalize_kernel: NaN stays NaN
         const float invstd = (float)(1.0 / sqrt(var + (double)eps));
         const float g = gamma ? gamma[c] : 1.f, b = beta ? beta[c] : 0.f;
         const float sc = g * invstd, sh = b - (float)mean * sc;
@@ -234,7 +234,7 @@ bn_finalize_apply_kernel(const float *__restrict__ partial, int rows, int C, dou
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
                     float t = h2f((uint16_t)(w[j] >> (16 * h)), DT) * sc[2 * j + h] + sh[2 * j + h];
-                    if (act == 1) t = t > 0.f ? t : 0.f;
+                    if (act == 1) t = (t > 0.f || t != t) ? t : 0.f;     // torch.relu: NaN stays NaN
                     else if (act == 2) t = t > 0.f ? t : 0.2f * t;
                     if (r1) t += h2f((uint16_t)(a[j] >> (16 * h)), DT);
                     if (r2) t += h2f((uint16_t)(b[j] >> (16 * h)), DT);

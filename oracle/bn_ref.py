@@ -10,7 +10,8 @@ Arithmetic restated from include/ir2rgb_hip.h and read off the kernels:
   then rounded to the half format.
 * ``bn_bwd``: g' = gz * act'(y * scale + shift); dbeta = sum g', dgamma = sum g' * yhat, summed per thread in fp32 over
   a pixel range and across ranges in double (backward.hip) -- bounded with the random-walk term of a chain of npix;
-  gy = scale * (g' - dbeta / n - yhat * dgamma / n) in fp32 from the kernel's own sums, rounded to the half format.
+  gy = scale * (g' - dbeta / n - yhat * dgamma / n) in fp32 from the kernel's own sums, rounded to the half format
+  (``gy_acc``: the error before that rounding, for oracle.bounds.check_range).
 
 Elements whose pre-activation is so close to zero that fp32 and fp64 may disagree on its sign carry no gradient (the
 caller zeroes gz there): the derivative of the activation is then not an arithmetic question.
@@ -71,9 +72,10 @@ def finalize_frozen(gamma, beta, conv_bias, rm, rv, eps):
     return dict(mean=(mu, e_mu), invstd=(invstd, e_inv), scale=(scale, e_scale), shift=(shift, e_shift))
 
 
-def apply(y, scale, shift, act, res1, res2, fmt, e_scale=0.0, e_shift=0.0):
-    """z = act(y * scale + shift) + res1 + res2: (ref, bound).  y / res [P, C] fp64 of half values; e_*: the error of
-    the scale / shift the kernel used (0 when they are exact inputs)."""
+def apply_acc(y, scale, shift, act, res1, res2, e_scale=0.0, e_shift=0.0):
+    """z = act(y * scale + shift) + res1 + res2: (ref, the error of the fp32 arithmetic before the result is rounded to
+    the half format).  y / res [P, C] fp64 of half values; e_*: the error of the scale / shift the kernel used (0 when
+    they are exact inputs)."""
     pre = y * scale + shift
     z = act_np(pre, act)
     mag = np.abs(y * scale) + np.abs(shift)
@@ -83,6 +85,12 @@ def apply(y, scale, shift, act, res1, res2, fmt, e_scale=0.0, e_shift=0.0):
             z = z + r
             mag = mag + np.abs(r)
             e = e + B.U32 * mag
+    return z, e
+
+
+def apply(y, scale, shift, act, res1, res2, fmt, e_scale=0.0, e_shift=0.0):
+    """(ref, bound) of apply_acc with the rounding to the half format and ETA."""
+    z, e = apply_acc(y, scale, shift, act, res1, res2, e_scale, e_shift)
     u = B.U_OUT[fmt]
     return z, u * np.abs(z) + (1 + u) * e + B.ETA[fmt]
 
@@ -107,7 +115,8 @@ def bwd(gz, y, scale, shift, mean, invstd, act, fmt, base=None, frozen=False):
         db = gp.sum(0)
         # (the sum may be of the rounded half gy: + u_out per term)
         e_db = (chain + u) * np.abs(gp).sum(0)
-        out = dict(gy=(gp, u * np.abs(gp) + 2 * B.U32 * np.abs(gp) + B.ETA[fmt]), dbeta=(db, e_db))
+        out = dict(gy=(gp, u * np.abs(gp) + 2 * B.U32 * np.abs(gp) + B.ETA[fmt]), dbeta=(db, e_db),
+                   gy_acc=2 * B.U32 * np.abs(gp))
     else:
         gp = gz * dact_np(y * scale + shift, act)
         yhat = (y - mean) * invstd
@@ -121,7 +130,7 @@ def bwd(gz, y, scale, shift, mean, invstd, act, fmt, base=None, frozen=False):
             gy = scale * (gp - db / n - yhat * dg / n)
             mag = np.abs(scale) * (np.abs(gp) + np.abs(db) / n + np.abs(yhat * dg) / n)
             e_gy = np.abs(scale) * (e_db / n + np.abs(yhat) * e_dg / n) + FIN * mag
-        out = dict(gy=(gy, u * np.abs(gy) + (1 + u) * e_gy + B.ETA[fmt]), dbeta=(db, e_db), dgamma=(dg, e_dg))
+        out = dict(gy=(gy, u * np.abs(gy) + (1 + u) * e_gy + B.ETA[fmt]), dbeta=(db, e_db), dgamma=(dg, e_dg), gy_acc=e_gy)
     if base is not None:
         g0, b0 = base
         out["dbeta"] = (out["dbeta"][0] + b0, out["dbeta"][1] + B.U32 * (np.abs(b0) + np.abs(out["dbeta"][0])))

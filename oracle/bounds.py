@@ -153,3 +153,66 @@ def check_bound(got, ref, bnd):
     i = int(np.argmax(r))
     over = int((r > 1.0).sum())
     return over == 0, float(r.ravel()[i]), i, over
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The range-aware check (tests/test_range_cpu.py, tests/test_range_gpu.py): f16's overflow and underflow edges and
+# planted inf / NaN, which check() and check_bound() refuse outright or cover with ETA.
+#
+# * rounding: max(u_out |ref|, H) with H half the subnormal spacing of the output format -- f16: 2^-25, and no ETA, so
+#   a store that flushes a subnormal |ref| > H + the accumulation term fails.  bf16 and f32 keep u_out |ref| + ETA
+#   (their subnormals are fp32's).
+# * overflow (f16 outputs): T_F16 = 65520 is the round-to-nearest-even midpoint between 65504 and 2^16.  The fp32 value
+#   v the kernel rounds is within the accumulation term e of ref, and the rounding of v is not in doubt: an element whose
+#   |ref| - e > T must be inf of ref's sign, one whose |ref| + e < T must be finite and inside the bound, and in between
+#   either is accepted.  (The rounding term is deliberately not part of that band: with it the band would reach 2^16 and
+#   a store that rounded toward zero at the top -- 65521 -> 65504 -- could not be told from a correct one.)
+# * a non-finite reference element (fp64 evaluation of planted operands under torch's semantics) wants a non-finite
+#   result: for +-inf that inf or NaN, for NaN anything non-finite.  ``allow`` marks the finite-reference elements where
+#   the record lists by rule that the kernel may be non-finite as well.
+T_F16 = 65520.0
+H_SUB = {"f16": 2.0 ** -25}
+
+
+def range_masks(ref, bnd_acc, fmt):
+    """What check_range pins, from the reference alone: (ref finite, the bound of a finite result, must be inf, must be
+    finite); the finite elements in neither mask are undecided."""
+    ref = np.asarray(ref, dtype=np.float64)
+    u = U_OUT[fmt]
+    fin = np.isfinite(ref)
+    with np.errstate(all="ignore"):
+        aref = np.where(fin, np.abs(ref), 0.0)
+        acc = np.where(fin, np.broadcast_to(np.asarray(bnd_acc, dtype=np.float64), ref.shape), 0.0)
+        assert np.isfinite(acc).all(), "the accumulation bound of a finite reference element is not finite"
+        rnd = np.maximum(u * aref, H_SUB[fmt]) if fmt in H_SUB else u * aref + ETA[fmt]
+        bnd = rnd + (1.0 + u) * acc
+        if fmt == "f16":
+            return fin, bnd, fin & (aref - acc > T_F16), fin & (aref + acc < T_F16)
+        return fin, bnd, np.zeros(ref.shape, dtype=bool), fin
+
+
+def check_range(got, ref, bnd_acc, fmt, allow=None):
+    """got against the fp64 ``ref`` of the operands as stored.  ``bnd_acc``: the accumulation part of the kernel's bound
+    (b_rw / gamma terms times S) without u_out |ref| and without ETA.  -> (ok, worst err/bound over the elements that
+    must be finite -- inf when any element fails --, index of the worst or first failing element, counts of
+    {must_inf, must_finite, undecided, ref_nonfinite})."""
+    got = np.asarray(got, dtype=np.float64)
+    ref = np.asarray(ref, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        fin, bnd, must_inf, must_fin = range_masks(ref, bnd_acc, fmt)
+        und = fin & ~must_inf & ~must_fin
+        gfin = np.isfinite(got)
+        inside = gfin & (np.abs(got - np.where(fin, ref, 0.0)) <= bnd)
+        right_inf = np.isinf(got) & (np.sign(got) == np.sign(ref))
+        good = np.where(must_inf, right_inf, np.where(must_fin, inside, inside | right_inf))
+        if allow is not None:
+            good = good | (fin & np.asarray(allow, dtype=bool) & ~gfin)
+        good = np.where(np.isnan(ref), ~gfin, good)
+        good = np.where(np.isinf(ref), right_inf | np.isnan(got), good)
+        ratio = np.where(fin & gfin & ~must_inf, np.abs(got - np.where(fin, ref, 0.0)) / bnd, 0.0)
+    counts = {"must_inf": int(must_inf.sum()), "must_finite": int(must_fin.sum()), "undecided": int(und.sum()),
+              "ref_nonfinite": int((~fin).sum())}
+    if not good.all():
+        return False, math.inf, int(np.argmin(good.ravel())), counts
+    i = int(np.argmax(ratio)) if ratio.size else 0
+    return True, float(ratio.ravel()[i]) if ratio.size else 0.0, i, counts

@@ -1,6 +1,8 @@
 """The edge records (test-only data, nothing here touches a device): hand-written tables in the format of
 tests/window_geometries.json at small and ragged shapes, for the replays of oracle/replay_ops.py (EDGE, which ends
 with EDGE_FLOW) and of oracle/replay_kernels.py: bn_case (EDGE_BN), replay_forward (EDGE_CONV) and replay_wgrad (EDGE_WGRAD).
+EDGE_RANGE, at the end of the file with its own table of which record reaches which half store, reuses the smallest of
+them for the ``mode=`` of those replays: f16's overflow and subnormal edges and planted inf / NaN (oracle/range_cases.py).
 
 The window's own geometries (512 x 1024, widths a multiple of 128, H far above 2 * pad) are the least likely to expose
 an indexing bug.  A record is ``entry``, then ``args`` with booleans standing for pointers, or the ``items`` / ``tensors``
@@ -10,6 +12,9 @@ records do, chosen on the CPU so that the fp64 reference alone has clamped pixel
 
 EDGE is chosen from the kernels' code: tile tails, pad < H <= 2 * pad (both mirrors of a reflection land near the far
 border), one-pixel planes, N > 1, every threshold between two code paths.
+
+The layout converters (pointwise.hip: 64-pixel x 64-channel LDS tiles) run at 1, 63, 64, 65 and 129 pixels times 1, 3,
+63, 64 and 65 channels with N = 2, the slice form with ld > C, an odd c_off and both activations.
 
 EDGE_FLOW (the FlowNet2 operators) is chosen from correlation.hip, correlation_mfma.hip, resample2d.hip and
 channelnorm.hip.  A record names its ``form`` (FLOW_FORMS) by hand; for the forward cost volume corr_form restates the
@@ -202,6 +207,24 @@ def _small():
     return out
 
 
+# H x W of 1, 63, 64, 65 and 129 pixels (the converters' tiles are 64 pixels x 64 channels)
+CONVERT_HW = ((1, 1), (7, 9), (8, 8), (5, 13), (3, 43))
+CONVERT_C = (1, 3, 63, 64, 65)
+
+
+def _converters():
+    out = []
+    for H, W in CONVERT_HW:
+        for C in CONVERT_C:
+            out.append(op("ir2rgb_nchw_f32_to_nhwc_half", N=2, C=C, H=H, W=W, dtype=1))
+            out.append(op("ir2rgb_nhwc_half_to_nchw_f32", N=2, C=C, H=H, W=W, dtype=1))
+    # the slice form: ld > C, an odd c_off, both activations (the replay checks the neighbouring channels untouched)
+    for i, ((H, W), C) in enumerate(zip(CONVERT_HW + CONVERT_HW, CONVERT_C + CONVERT_C[::-1])):
+        out.append(op("ir2rgb_nchw_f32_to_nhwc_half_slice", N=2, C=C, H=H, W=W, ld=C + 8 + i, c_off=(1, 3, 7)[i % 3],
+                      act=(0, 2)[i % 2], dtype=1))
+    return out
+
+
 def _item(kind, n, slot, weight=1.0, target=0.0, hw=0, chw=0, b=None, ga=True):
     return {"kind": kind, "n": n, "hw": hw, "chw": chw, "weight": weight, "target": target, "slot": slot,
             "b": (kind != 1) if b is None else b, "ga": ga, "mask": kind == 2}
@@ -352,7 +375,7 @@ def _channelnorm_bwds():
 
 EDGE_FLOW = _corr_fwd() + _corr_bwd() + _corr_mfma() + _resamples() + _channelnorm_bwds()
 
-EDGE = _heads() + _warps() + _pools() + _xexpands() + _small() + _losses() + [ADAM] + EDGE_FLOW
+EDGE = _heads() + _warps() + _pools() + _xexpands() + _small() + _converters() + _losses() + [ADAM] + EDGE_FLOW
 
 # ---------------------------------------------------------------------------------------------------------------------
 # BatchNorm
@@ -737,3 +760,153 @@ def _lines():
 
 
 EDGE_WGRAD = _onetap() + _nine() + _lines()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# EDGE_RANGE: the records of tests/test_range_cpu.py and tests/test_range_gpu.py, each with the modes that apply
+# (oracle/range_cases.py: "overflow" O, "subnormal" U, "nonfinite" N).  The smallest EDGE record of each form is
+# reused; ``plant`` = (operand, position, value) of the nonfinite mode.
+#
+#   record                                   modes   half store / fp32 consumer reached
+#   conv store:scalar (Cout 5)               O U N   conv_igemm_body epilogue, scalar Half<>::cvt stores (conv_mfma.hip)
+#   conv store:vector (Cout 36)              O U N   ... 8-byte stores from the registers
+#   conv tile:64 (Cout 72), tile:128         O U N   ... the staged epilogue (LDS, 16-byte stores), 64- and 128-pixel tiles
+#   conv thin:4x4 (Cout 32)                  O U N   ... the THIN tile's stores
+#   conv act (bias, LeakyReLU 0.2, Cout 72)  O U N   ... bias and activation before the store
+#   conv classes:two, transposed:one-class   O U N   conv_igemm_classes_kernel's stores; a transposed single class
+#   conv patch:1, patch:adjoint (pad_mode 2) O U N   conv3x3_patch.hip stores, the reflect-adjoint fold
+#   conv col7x1                              O U N   conv7x1_col.hip stores
+#   conv dot, thin1x7 (fp32 outputs)           U N   conv_dot_kernel / conv1x7_thin.hip: fp32 consumers of half operands
+#   wgrad nine:direct / nine:split,            U N   wgrad_mfma.hip: fp32 consumers of the half gradient, plain and
+#     line:col7 / line:line7, onetap:split             accumulating (ir2rgb_conv2d_wgrad_acc); plants in gy and in x
+#   bn_bwd 4096 / 4097 / 2049 pixels         O U N   backward.hip f2h of gy (one launch, two passes, C = 2048), act 0 / 1 / 2,
+#     (+ act | 16, + bias-only)                        dgamma / dbeta; plants in gz and in y
+#   bn_apply, bn_finalize_apply              O   N   pointwise.hip f2h of the two apply kernels; plants in x and in a
+#                                                      statistics row
+#   bn_finalize_ex (32- and 8-channel forms)     N   the same statistics-row plant through the two-launch path
+#   the three layout converters              O U N   pointwise.hip f2h of nchw_to_nhwc[_slice]_kernel, h2f of the inverse
+#   head_finish_bwd (dT, dbias)              O U N   heads.hip:112, the (_Float16) cast of head_finish_bwd_kernel
+#   flow_upsample_slice                      O U N   heads.hip:310, the (_Float16) casts of flow_up_kernel
+#   thin_grad_expand (g8, g64, dbias)        O U N   backward.hip f2h of the expanded logit gradient
+#   fold_reflect                               U N   backward.hip f2h of the folded gradient (sums of <= 4 inputs)
+#   xexpand                                  O U N   pointwise.hip:377 f2h of xexpand_kernel
+#   xexpand_bwd                                U N   its adjoint: an fp32 consumer of the half gradient
+#   correlation_nhwc_half, out mode 1        O   N   correlation_mfma.hip's half store behind the LeakyReLU
+#   loss_multi_bwd                           O U N   losses.hip:127 f2h(gout * weight / n), the root of the scaled backward
+def _of(recs, form=None, **fields):
+    for r in recs:
+        where = r.get("desc") or {}
+        if (form is None or r.get("form") == form) and r.get("entry", "fwd_ws") != "fwd" and \
+                all(where.get(k, r.get(k)) == v for k, v in fields.items()):
+            return r
+    raise LookupError((form, fields))
+
+
+def ranged(rec, modes, plant=None, **kw):
+    rec = dict(rec, modes=tuple(modes), **kw)
+    if plant is not None:
+        rec["plant"] = tuple(plant)
+    return rec
+
+
+O_U_N, U_N, O_N = ("overflow", "subnormal", "nonfinite"), ("subnormal", "nonfinite"), ("overflow", "nonfinite")
+_PLANTS = (("x", "first", "nan"), ("x", "last", "+inf"), ("x", "border", "-inf"), ("w", "first", "+inf"),
+           ("x", "border", "nan"), ("x", "last", "-inf"))
+
+
+def _range_convs():
+    half = [_of(EDGE_CONV, "store:scalar", Cout=5), _of(EDGE_CONV, "store:vector", Cout=36), _of(EDGE_CONV, "tile:64", Cout=72),
+            _of(EDGE_CONV, "tile:128"), _of(EDGE_CONV, "thin:4x4"), _of(EDGE_CONV, "act", Cout=72, act=1),
+            _of(EDGE_CONV, "classes:two"), _of(EDGE_CONV, "transposed:one-class"), _of(EDGE_CONV, "patch:1"),
+            _of(EDGE_CONV, "patch:adjoint"), _of(EDGE_CONV, "col7x1", Win=31)]
+    f32 = [_of(EDGE_CONV, "dot", N=2), _of(EDGE_CONV, "thin1x7", Win=5)]
+    out = [ranged(r, O_U_N, _PLANTS[i % len(_PLANTS)]) for i, r in enumerate(half)]
+    out += [ranged(r, U_N, _PLANTS[i]) for i, r in enumerate(f32)]
+    out.append(ranged(_of(EDGE_CONV, "act", Cout=72, act=1), ("nonfinite",), ("bias", "last", "nan")))
+    return out
+
+
+def _range_wgrads():
+    recs = [_of(EDGE_WGRAD, "nine:direct", N=2), _of(EDGE_WGRAD, "nine:split", N=1), _of(EDGE_WGRAD, "line:col7"),
+            _of(EDGE_WGRAD, "line:line7"), _of(EDGE_WGRAD, "onetap:split", Cin=72)]
+    vals = ("nan", "+inf", "-inf")
+    out = []
+    for i, r in enumerate(recs):
+        out.append(ranged(r, U_N, ("gy", ("first", "last")[i % 2], vals[i % 3])))
+        out.append(ranged(r, ("nonfinite",), ("x", ("last", "border", "first")[i % 3], vals[(i + 1) % 3])))
+    return out
+
+
+def _range_bns():
+    out = []
+    vals = ("nan", "+inf", "-inf")
+    for i, (npix, C) in enumerate(((4096, 64), (4097, 128), (2049, 2048))):
+        for act in (0, 1, 2):
+            j = 3 * i + act
+            out.append(ranged(bwd(npix, C, act), O_U_N, ("gz", ("first", "last")[j % 2], vals[j % 3])))
+            if act != 1:
+                out.append(ranged(bwd(npix, C, act), ("nonfinite",), ("y", ("last", "first")[j % 2], vals[(j + 1) % 3])))
+    out.append(ranged(bwd(4097, 64, 2 | 16), O_U_N, ("gz", "last", "+inf")))
+    out.append(ranged(bwd(4096, 128, 1 | 16), O_U_N, ("gz", "first", "nan")))
+    out.append(ranged(bwd(513, 64, 1, scale=False), U_N, ("gz", "last", "-inf")))
+    out.append(ranged(bwd(4097, 512, 2, scale=False), U_N, ("gz", "first", "nan")))
+    for i, (npix, C, res, act) in enumerate(((257, 64, 0, 1), (257, 24, 1, 2), (3, 8, 2, 0))):
+        out.append(ranged(apply(npix, C, res, act), O_N, ("x", ("last", "first")[i % 2], vals[i % 3])))
+    for i, (rows, C, npix, res, act) in enumerate(((9, 64, 129, 0, 1), (2, 192, 33, 1, 2), (128, 64, 1000, 2, 0))):
+        r = finalize_apply(rows, C, npix, res, act)
+        r.pop("two_launch")
+        out.append(ranged(r, O_N, ("x", ("first", "last")[i % 2], vals[(i + 1) % 3])))
+        out.append(ranged(r, ("nonfinite",), ("rows", "last", "nan")))
+    out.append(ranged(finalize(9, 72, 129, upd=2), ("nonfinite",), ("rows", "last", "nan")))
+    out.append(ranged(finalize(2049, 64, 4100, bias=False), ("nonfinite",), ("rows", "last", "nan")))
+    return out
+
+
+def _range_converters():
+    out = []
+    for e in ("ir2rgb_nchw_f32_to_nhwc_half", "ir2rgb_nhwc_half_to_nchw_f32"):
+        for (H, W), C in (((5, 13), 65), ((3, 43), 3)):
+            out.append(ranged(op(e, N=2, C=C, H=H, W=W, dtype=1), O_U_N if e.endswith("half") else U_N))
+    for act in (0, 2):
+        out.append(ranged(op("ir2rgb_nchw_f32_to_nhwc_half_slice", N=2, C=65, H=5, W=13, ld=75, c_off=3, act=act, dtype=1),
+                          O_U_N))
+    return out
+
+
+# loss_multi_bwd: three L1 items (half operands) whose weight / n puts gout * weight / n on both sides of 65520 at
+# gout = 2^23 * (1, 2, .5, 4) (81920 and 158875 against 5110) and into [2^-21, 2^-15) at 2^-10 * the same; an MSE and a
+# masked-L1 item (fp32 gradients) beside them.  The nonfinite plant names the slot of gout.
+RANGE_LOSS = [_item(0, 2048, 1, 10.0), _item(0, 4104, 2, 5.0), _item(0, 264, 0, 5.0), _item(1, 257, 1, 1.0, 1.0),
+              _item(2, 135, 3, 10.0, hw=15, chw=45)]
+
+
+def _range_ops():
+    e = lambda entry, **want: next(r for r in EDGE if r["entry"] == entry and  # noqa: E731
+                                   all(dict(zip(ARGS[entry].split(), r["args"]))[k] == v for k, v in want.items()))
+    loss = {"kind": "op", "entry": "ir2rgb_loss_multi_bwd", "count": len(RANGE_LOSS), "dtype": 1, "items": RANGE_LOSS}
+    return [
+        ranged(e("ir2rgb_head_finish_bwd", H=9, W=5, Cout=3), O_U_N, ("gout", "last", "nan")),
+        ranged(e("ir2rgb_head_finish_bwd", H=4, W=5, Cout=8), O_U_N, ("gout", "first", "-inf")),
+        ranged(e("ir2rgb_thin_grad_expand", Cout=5), O_U_N, ("gz", "last", "+inf")),
+        ranged(e("ir2rgb_thin_grad_expand", Cout=8), O_U_N, ("gz", "first", "nan")),
+        ranged(e("ir2rgb_fold_reflect", H=4, C=64), U_N, ("dxpad", "first", "nan")),
+        ranged(e("ir2rgb_fold_reflect", H=5, C=72), U_N, ("dxpad", "last", "-inf")),
+        ranged(e("ir2rgb_xexpand_bwd", Cin=9, W=4), U_N, ("dxe", "first", "+inf")),
+        ranged(e("ir2rgb_xexpand_bwd", Cin=13, W=254), U_N, ("dxe", (1, 2, 64, 51), "nan")),    # the last used channel
+        ranged(e("ir2rgb_xexpand", Cin=9, W=129), O_U_N, ("x", "border", "nan")),
+        ranged(e("ir2rgb_xexpand", Cin=13, W=5), O_U_N, ("x", "last", "-inf")),
+        ranged(e("ir2rgb_flow_upsample_slice", h=3, w=5, bias=True), O_U_N, ("x", "last", "+inf")),
+        ranged(e("ir2rgb_flow_upsample_slice", h=1, w=9, bias=False), O_U_N, ("x", "first", "nan")),
+        # (21 x 33 pixels: a third of the 441 displacements stay inside the image, so that the overflow mode is live)
+        ranged(flow("ir2rgb_correlation_nhwc_half", "mfma:kc4", lda=128, offa=0, ldb=128, offb=0, out_mode=1, ldo=512, offo=32,
+                    slope=0.1, N=1, C=128, H=21, W=33, dtype=1), O_N, ("f1", "first", "nan")),
+        ranged(flow("ir2rgb_correlation_nhwc_half", "mfma:kc8", lda=256, offa=0, ldb=320, offb=64, out_mode=1, ldo=448, offo=7,
+                    slope=0.1, N=2, C=256, H=21, W=31, dtype=1), O_N, ("f1", "last", "-inf")),
+        ranged(loss, O_U_N, ("gout", 1, "nan"), ek=(23, 10)),
+        ranged(loss, ("nonfinite",), ("gout", 2, "-inf"), ek=(23, 10)),
+        ranged(loss, ("nonfinite",), ("gout", 0, "+inf"), ek=(23, 10)),
+    ]
+
+
+EDGE_RANGE = _range_convs() + _range_wgrads() + _range_bns() + _range_converters() + _range_ops()
+RANGE_CASES = [(r, m) for r in EDGE_RANGE for m in r["modes"]]

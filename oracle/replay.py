@@ -52,11 +52,17 @@ def bits(t):
     return t.view(torch.int16) if t.element_size() == 2 else t.view(torch.int32)
 
 
+def differs(g, want):
+    """Mask of the elements of two CPU tensors of one format whose bits differ.  The sign of a zero is not checked, nor
+    the payload of a NaN where the reference is NaN too (oracle/range_cases.py plants them; no other reference has one)."""
+    return (bits(g) != bits(want)) & ~((g == 0) & (want == 0)) & ~(torch.isnan(g) & torch.isnan(want))
+
+
 def exact(name, got, ref_t):
     """got (device half / fp32) == the fp64 reference rounded to nearest even into got's format, bit for bit."""
     want = ref_t.to(got.dtype)
     g = got.cpu()
-    bad = (bits(g) != bits(want)) & ~((g == 0) & (want == 0))        # (the sign of a zero is not checked)
+    bad = differs(g, want)
     assert not bool(bad.any()), f"{name}: {int(bad.sum())} elements differ from the rounded fp64 result " \
                                 f"(first at {tuple(int(v) for v in bad.nonzero()[0])})"
     return 0.0
@@ -115,3 +121,40 @@ class Table:
             else:
                 print("  " + " ".join(f"{k} {v:7.4f}" for k, v in worst.items()) + f"  {t:6.1f} s  {name}")
         print("per family: " + fams)
+
+
+class RangeTable:
+    """The rows of tests/test_range_gpu.py: per launch and mode the worst err/bound per format and check_range's four
+    counts (must-inf, must-finite, undecided, non-finite reference elements), printed by its teardown_module (run with -s)."""
+
+    def __init__(self):
+        self.rows = []
+
+    def run(self, name, mode, fn, *a, **kw):
+        t0 = time.perf_counter()
+        worst = fn(*a, mode=mode, **kw)
+        dt = time.perf_counter() - t0
+        counts = worst.pop("counts")
+        self.rows.append((name, mode, worst, counts, dt))
+        print(f"\n{name} [{mode}]: worst err/bound " + " ".join(f"{k} {v:.3f}" for k, v in worst.items()) + f" ({dt:.2f} s)")
+
+    def report(self):
+        if not self.rows:
+            return
+        print("\nper launch: mode, worst err/bound, must-inf / must-finite / undecided / ref-nonfinite per format")
+        fam = {}
+        for name, mode, worst, counts, dt in self.rows:
+            cs = "  ".join(f"{f} {worst[f]:.4f} " + "/".join(str(counts[f][k]) for k in
+                                                              ("must_inf", "must_finite", "undecided", "ref_nonfinite"))
+                           for f in worst)
+            print(f"  {mode:9s} {cs}  {dt:5.1f} s  {name}")
+            key = (name.split("-")[0], mode)
+            w, c = fam.get(key, (0.0, [0, 0, 0, 0]))
+            for f in worst:
+                c = [x + counts[f][k] for x, k in zip(c, ("must_inf", "must_finite", "undecided", "ref_nonfinite"))]
+            fam[key] = (max(w, max(worst.values())), c)
+        print("per family and mode: worst err/bound, summed counts")
+        for (f, mode), (w, c) in sorted(fam.items()):
+            print(f"  {f:34s} {mode:9s} {w:.4f}  " + " / ".join(str(x) for x in c))
+        secs = [r[4] for r in self.rows]
+        print(f"{len(secs)} launches, {sum(secs):.1f} s, slowest {max(secs):.2f} s")

@@ -54,10 +54,19 @@ def _group_rows(stats, d, mode, rows):
     return st.sum(0, keepdims=True)
 
 
-def replay_forward(dev, rec):
+def _ranged(dev, rec, mode, build):
+    """``mode`` of a replay: the inputs of oracle/range_cases.py (overflow / subnormal / nonfinite) under
+    oracle.bounds.check_range, at an EDGE_RANGE record.  -> {format: worst err/bound, "counts": {format: the four counts}}."""
+    from oracle import range_cases as RC
+    return RC.run(dev, rec, mode, getattr(RC, build))
+
+
+def replay_forward(dev, rec, mode=None):
     """A forward-type launch (conv2d_fwd with its split-K workspace, or conv2d_fwd_view on channel-slice buffers) with
     the recorded bias / statistics arguments.  -> worst err/bound per format, and per format of the statistics rows."""
     from ir2rgb_amd import conv as C
+    if mode is not None:
+        return _ranged(dev, rec, mode, "forward_case")
     d = rec["desc"]
     g = gen(rec)
     x = R.draw((d["N"], d["Cin"], d["Hin"], d["Win"]), g)
@@ -130,9 +139,11 @@ def replay_forward(dev, rec):
     return out
 
 
-def replay_wgrad(dev, rec):
+def replay_wgrad(dev, rec, mode=None):
     """A weight gradient through conv2d_wgrad, plain and accumulating onto a seeded base."""
     from ir2rgb_amd import conv as C
+    if mode is not None:
+        return _ranged(dev, rec, mode, "wgrad_case")
     d = rec["desc"]
     g = gen(rec)
     x = R.draw((d["N"], d["Cin"], d["Hin"], d["Win"]), g)
@@ -194,13 +205,15 @@ def _pc(t, dtype, dev):
     return t.to(dev, dtype).contiguous().view(1, 1, P, C).permute(0, 3, 1, 2)
 
 
-def bn_case(dev, rec, shifted):
+def bn_case(dev, rec, shifted=False, mode=None):
     """One BatchNorm record.  What a record can ask for beyond the window's launches (oracle/edge_records.py): the
     plain ir2rgb_bn_finalize entry; no conv_bias; evaluation mode (the frozen argument of ir2rgb_bn_finalize_ex, act | 16
     of ir2rgb_bn_bwd, also with act | 32); and, with the key "two_launch", the bit-identity of ir2rgb_bn_finalize_apply
     with ir2rgb_bn_finalize_ex + ir2rgb_bn_apply as a second assertion."""
     from ir2rgb_amd import _lib
     from oracle import bn_ref as BR
+    if mode is not None:
+        return _ranged(dev, rec, mode, "bn_case")
     a = rec["args"]
     g = gen(rec) if not shifted else torch.Generator().manual_seed(20)
     entry = rec["entry"]

@@ -24,6 +24,9 @@ ARGS = {    # argument names of the header's prototypes, without the stream
     "ir2rgb_xexpand": "inp out N Cin H W Wout KW stride_w pad_w pad_mode dtype",
     "ir2rgb_xexpand_cx": "inp out N Cin H W Wout KW stride_w pad_w pad_mode Cx dtype",
     "ir2rgb_flow_upsample_slice": "inp weight bias out N h w ld c_off dtype",
+    "ir2rgb_nchw_f32_to_nhwc_half": "inp out N C H W dtype",
+    "ir2rgb_nhwc_half_to_nchw_f32": "inp out N C H W dtype",
+    "ir2rgb_nchw_f32_to_nhwc_half_slice": "inp out N C H W ld c_off act dtype",
     "ir2rgb_head_finish": "T bias out N H W Cout KH CT pad_h acts mul",
     "ir2rgb_warp_blend_fwd": "raw prev flow w out warp_out N Cp H W",
     "ir2rgb_thin_grad_expand": "gz g64 g8 dbias N Cout H W dtype",
@@ -44,6 +47,13 @@ ARGS = {    # argument names of the header's prototypes, without the stream
 
 def named_args(rec):
     return dict(zip(ARGS[rec["entry"]].split(), rec["args"]))
+
+
+def _ranged(dev, rec, mode):
+    """``mode`` of a replay: the inputs of oracle/range_cases.py (overflow / subnormal / nonfinite) under
+    oracle.bounds.check_range, at an EDGE_RANGE record."""
+    from oracle import range_cases as RC
+    return RC.run(dev, rec, mode, RC.build_for(rec))
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -80,7 +90,9 @@ def replay_avgpool(dev, rec, g):
     return {"f32": assert_bound("avgpool3s2", *B.check_bound(np64(y), ref, B.bound_sum(ref, S, "f32", terms)), ref.shape)}
 
 
-def replay_xexpand(dev, rec, g):
+def replay_xexpand(dev, rec, g, mode=None):
+    if mode is not None:
+        return _ranged(dev, rec, mode)
     a = named_args(rec)
     N, Cin, H, W, Wout, KW, s, p, pm = (a[k] for k in "N Cin H W Wout KW stride_w pad_w pad_mode".split())
     Cx = a.get("Cx", 64)
@@ -96,7 +108,9 @@ def replay_xexpand(dev, rec, g):
     return out
 
 
-def replay_xexpand_bwd(dev, rec, g):
+def replay_xexpand_bwd(dev, rec, g, mode=None):
+    if mode is not None:
+        return _ranged(dev, rec, mode)
     a = named_args(rec)
     N, Cin, H, W, Wout, KW, s, p, pm = (a[k] for k in "N Cin H W Wout KW stride_w pad_w pad_mode".split())
     dxe = R.draw((N, H, Wout, 64), g)
@@ -112,7 +126,9 @@ def replay_xexpand_bwd(dev, rec, g):
     return out
 
 
-def replay_fold(dev, rec, g):
+def replay_fold(dev, rec, g, mode=None):
+    if mode is not None:
+        return _ranged(dev, rec, mode)
     a = named_args(rec)
     N, H, W, C, ph, pw = (a[k] for k in "N H W C pad_h pad_w".split())
     dxpad = R.draw((N, H + 2 * ph, W + 2 * pw, C), g)
@@ -128,7 +144,9 @@ def replay_fold(dev, rec, g):
     return out
 
 
-def replay_thin_grad(dev, rec, g):
+def replay_thin_grad(dev, rec, g, mode=None):
+    if mode is not None:
+        return _ranged(dev, rec, mode)
     a = named_args(rec)
     N, Cout, H, W = a["N"], a["Cout"], a["H"], a["W"]
     gz = torch.randn(N, Cout, H, W, generator=g)
@@ -157,7 +175,9 @@ def replay_thin_grad(dev, rec, g):
     return out
 
 
-def replay_flow_up(dev, rec, g):
+def replay_flow_up(dev, rec, g, mode=None):
+    if mode is not None:
+        return _ranged(dev, rec, mode)
     a = named_args(rec)
     N, h, w, ld, off = a["N"], a["h"], a["w"], a["ld"], a["c_off"]
     x = R.draw((N, 2, h, w), g, 4.0)
@@ -179,6 +199,54 @@ def replay_flow_up(dev, rec, g):
     return out
 
 
+def launch_convert(dev, rec, x, fmt):
+    """One launch of a layout converter on x [N,C,H,W] fp32 (for ir2rgb_nhwc_half_to_nchw_f32: the values of its half
+    input).  -> the output as an fp64 array in the reference's layout; the slice form asserts its neighbours untouched."""
+    a = named_args(rec)
+    N, C, H, W = a["N"], a["C"], a["H"], a["W"]
+    dtype, dt = {f: (t, d) for f, t, d in DTYPES}[fmt]
+    entry = rec["entry"]
+    if entry == "ir2rgb_nhwc_half_to_nchw_f32":
+        y = sentinel((N, C, H, W), torch.float32, dev)
+        call(entry, x.permute(0, 2, 3, 1).contiguous().to(dev, dtype), y, N, C, H, W, dt)
+        torch.cuda.synchronize()
+        return np64(y)
+    if entry == "ir2rgb_nchw_f32_to_nhwc_half":
+        y = sentinel((N, H, W, C), dtype, dev)
+        call(entry, x.contiguous().to(dev), y, N, C, H, W, dt)
+        torch.cuda.synchronize()
+        return np64(y)
+    ld, off = a["ld"], a["c_off"]
+    buf = torch.randn(N, H, W, ld, generator=torch.Generator().manual_seed(ld)).to(dev, dtype)
+    before = buf.clone()
+    call(entry, x.contiguous().to(dev), buf, N, C, H, W, ld, off, a["act"], dt)
+    torch.cuda.synchronize()
+    keep = torch.ones(ld, dtype=torch.bool)
+    keep[off:off + C] = False
+    assert torch.equal(bits(buf[..., keep]), bits(before[..., keep])), f"{fmt}: the converter wrote outside its channels"
+    return np64(buf[..., off:off + C])
+
+
+def replay_convert(dev, rec, g, mode=None):
+    """The layout converters: every element bit for bit the fp64 value rounded to nearest even into the output format.
+    ``mode``: the inputs of oracle/range_cases.py (beyond f16's range, subnormal, inf / NaN) under the same comparison."""
+    if mode is not None:
+        return _ranged(dev, rec, mode)
+    a = named_args(rec)
+    x = torch.randn(a["N"], a["C"], a["H"], a["W"], generator=g)
+    out = {}
+    for fmt, dtype, _ in DTYPES:
+        if rec["entry"] == "ir2rgb_nhwc_half_to_nchw_f32":
+            xin = x.to(dtype).float()
+            ref, want_dt = xin.double(), torch.float32
+        else:
+            xin = x
+            ref, want_dt = torch.from_numpy(O.nchw_to_nhwc(np64(x), a.get("act", 0))), dtype
+        got = torch.from_numpy(launch_convert(dev, rec, xin, fmt)).to(want_dt)
+        out[fmt] = exact(f"{fmt} {rec['entry']}", got, ref)
+    return out
+
+
 def replay_head_finish(dev, rec, g):
     a = named_args(rec)
     N, H, W, Cout, KH, CT, pad, acts, mul = (a[k] for k in "N H W Cout KH CT pad_h acts mul".split())
@@ -192,7 +260,9 @@ def replay_head_finish(dev, rec, g):
     return {"f32": assert_bound("head_finish", *B.check_bound(np64(y), ref, bnd), ref.shape)}
 
 
-def replay_head_finish_bwd(dev, rec, g):
+def replay_head_finish_bwd(dev, rec, g, mode=None):
+    if mode is not None:
+        return _ranged(dev, rec, mode)
     from ir2rgb_amd import _lib
     a = named_args(rec)
     N, H, W, Cout, KH, CT, pad, acts, mul = (a[k] for k in "N H W Cout KH CT pad_h acts mul".split())
@@ -435,7 +505,9 @@ def leaky(x, slope):
     return np.where(x > 0, x, x * slope)
 
 
-def replay_corr_mfma(dev, rec, g):
+def replay_corr_mfma(dev, rec, g, mode=None):
+    if mode is not None:
+        return _ranged(dev, rec, mode)
     a = named_args(rec)
     N, C, H, W = a["N"], a["C"], a["H"], a["W"]
     lda, offa, ldb, offb, ldo, offo, slope = (a[k] for k in "lda offa ldb offb ldo offo slope".split())
@@ -632,7 +704,9 @@ def replay_loss_fwd(dev, rec, g):
     return out
 
 
-def replay_loss_bwd(dev, rec, g):
+def replay_loss_bwd(dev, rec, g, mode=None):
+    if mode is not None:
+        return _ranged(dev, rec, mode)
     from ir2rgb_amd import _lib
     out = {}
     for fmt, dtype, dt in DTYPES:
@@ -728,6 +802,9 @@ REPLAY = {
     "ir2rgb_fold_reflect": replay_fold,
     "ir2rgb_thin_grad_expand": replay_thin_grad,
     "ir2rgb_flow_upsample_slice": replay_flow_up,
+    "ir2rgb_nchw_f32_to_nhwc_half": replay_convert,
+    "ir2rgb_nhwc_half_to_nchw_f32": replay_convert,
+    "ir2rgb_nchw_f32_to_nhwc_half_slice": replay_convert,
     "ir2rgb_head_finish": replay_head_finish,
     "ir2rgb_head_finish_bwd": replay_head_finish_bwd,
     "ir2rgb_warp_blend_fwd": replay_warp_fwd,

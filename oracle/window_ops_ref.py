@@ -22,6 +22,21 @@ def nibble(acts, co):
 
 
 # --------------------------------------------------------------------------------------------------------------------
+# layout converters (ir2rgb_nchw_f32_to_nhwc_half[_slice], ir2rgb_nhwc_half_to_nchw_f32)
+SLOPE_01 = float(np.float32(0.1))
+
+
+def nchw_to_nhwc(x, act=0):
+    """x [N,C,H,W] fp64 of fp32 values -> [N,H,W,C], what the half store must round.  act 2: LeakyReLU(0.1) -- one fp32
+    product x * 0.1f, exact in fp64 (24 + 24 significand bits) and rounded to fp32 here, as F.leaky_relu on the fp32 tensor
+    rounds it (FlowNetC.py:32 applies it before any cast): the half store rounds that fp32 value, not the fp64 product."""
+    y = x.transpose(0, 2, 3, 1)
+    if act == 2:
+        y = np.where(y > 0, y, (y * SLOPE_01).astype(np.float32).astype(np.float64))
+    return np.ascontiguousarray(y)
+
+
+# --------------------------------------------------------------------------------------------------------------------
 # separable heads (networks.py:166, :170-171, :200-201)
 def head_finish(T, bias, Cout, KH, pad, acts, mul):
     """T [N,H,W,CT] -> (out, pre, S_pre) [N,Cout,H,W]: out = f(bias + sum_ky T[refl(y+ky-pad)][x][co*KH+ky])."""

@@ -6,9 +6,9 @@ applies, and -- a power-of-two scale being exact -- bit for bit against ir2rgb_a
 Trainer level: the backward pass is linear in the upstream gradient and training is bit-reproducible, so a power-of-two
 scale is tested with tolerance 0.
 
-Half stores on the gradient path (read for the f16 test below): every fp32 -> f16 conversion of the library is a plain
-``(_Float16)f`` (common.h f2h / Half<F16>::cvt, heads.hip), round-to-nearest-even with overflow to inf; nothing
-saturates, so an overflowed activation gradient reaches the check as inf or NaN.
+Half stores on the gradient path: that an fp32 -> f16 store overflows to inf and never saturates, keeps subnormals, and
+that an inf / NaN of a backward pass stays one is tested kernel by kernel in tests/test_range_gpu.py (the EDGE_RANGE
+records of oracle/edge_records.py), not here; the f16 test below starts from a scale whose first gradient is already inf.
 """
 import math
 import os
