@@ -232,8 +232,8 @@ int ir2rgb_bn_finalize_ex(const float *stats_partial, int rows, int C, long coun
                           float *invstd_out, int stat_updates, int frozen, void *stream);
 
 /* ir2rgb_bn_finalize_ex (training mode, frozen = 0) and ir2rgb_bn_apply in ONE launch, for convolutions that wrote at
- * most IR2RGB_BN_FUSED_MAX_ROWS partial rows (the residual blocks).  Same arithmetic in the same order: results are
- * bit-identical to the two calls.  C % 64 == 0.  x / y / res1 / res2 as in ir2rgb_bn_apply (y may alias x). */
+ * most IR2RGB_BN_FUSED_MAX_ROWS partial rows (the residual blocks).  The same device functions (csrc/bn.h) on sums taken
+ * in the same order: results are bit-identical to the two calls.  C % 64 == 0.  x / y / res1 / res2 as in ir2rgb_bn_apply (y may alias x). */
 #define IR2RGB_BN_FUSED_MAX_ROWS 128
 int ir2rgb_bn_finalize_apply(const float *stats_partial, int rows, int C, long count, const float *gamma,
                              const float *beta, const float *conv_bias, float *running_mean, float *running_var,
@@ -288,17 +288,23 @@ int ir2rgb_warp_blend_fwd(const float *raw, const float *prev, const float *flow
  * ------------------------------------------------------------------------------------------ */
 
 /* Rows R of the scratch needed by ir2rgb_bn_bwd: `partial` must hold (R*2 + 3)*C floats
- * ([R][2][C] pixel-range partial sums followed by three coefficient vectors).  < 0: error; C must
- * be a power of two in [64, 2048]. */
+ * ([R][2][C] pixel-range partial sums; the tail of 3*C floats is reserved: nothing is written there).
+ * < 0: error; C must be a power of two in [64, 2048]. */
 int ir2rgb_bn_bwd_blocks(long npix, int C);
 
 /* Backward of activation + training-mode BatchNorm2d on NHWC half tensors:
  *   g' = gz * act'(y*scale+shift);  dbeta = sum g';  dgamma = sum g'*yhat;
  *   gy = scale * (g' - dbeta/n - yhat*dgamma/n),  yhat = (y-mean)*invstd.
- * With scale == NULL (no norm layer): gy = gz * act'(y) and dbeta = sum gy (the bias gradient).
- * act: 0 none, 1 ReLU, 2 LeakyReLU(0.2); act | 16: the statistics were frozen (evaluation-mode BatchNorm,
- * ir2rgb_bn_finalize_ex(frozen)): gy = scale * g', dgamma / dbeta as above; act | 32: dgamma / dbeta are ADDED to what the
- * two vectors hold (the later sample groups of a layer whose batch is several independent forwards).  gy may alias gz. */
+ * scale, shift, mean and invstd are given together or not at all (anything else: IR2RGB_EINVAL).  With all four
+ * NULL (no norm layer): gy = gz * act'(y) and dbeta = sum gy (the bias gradient).
+ * act: 0 none, 1 ReLU, 2 LeakyReLU(0.2), or-ed with
+ *   IR2RGB_BN_BWD_FROZEN: the statistics were frozen (evaluation-mode BatchNorm, ir2rgb_bn_finalize_ex(frozen)):
+ *     gy = scale * g', dgamma / dbeta as above;
+ *   IR2RGB_BN_BWD_ACCUMULATE: dgamma / dbeta are ADDED to what the two vectors hold (the later sample groups of a layer
+ *     whose batch is several independent forwards).
+ * gy may alias gz. */
+#define IR2RGB_BN_BWD_FROZEN 16
+#define IR2RGB_BN_BWD_ACCUMULATE 32
 int ir2rgb_bn_bwd(const void *gz, const void *y, const float *scale, const float *shift, const float *mean,
                   const float *invstd, void *gy, float *dgamma, float *dbeta, float *partial, long npix, int C,
                   int act, int dtype, void *stream);

@@ -36,17 +36,20 @@ def _as_half_nhwc(g, dtype):
     return g.to(dtype).contiguous(memory_format=torch.channels_last)
 
 
+BN_BWD_FROZEN, BN_BWD_ACCUMULATE = 16, 32      # IR2RGB_BN_BWD_FROZEN / _ACCUMULATE of include/ir2rgb_hip.h, or-ed into act
+
+
 def bn_bwd(gz, y, scale, shift, mean, invstd, act, out=None, params=None):
     """-> (gy, dgamma, dbeta).  scale None: activation-only stage (dbeta is then the bias gradient).  ``out``: where gy
     goes (a sample-group slice of the batch's gradient tensor, see ConvStageFn); ``params`` = (dgamma, dbeta) of an earlier
-    group of the same layer: this group's are added to them in the kernel (act | 32)."""
+    group of the same layer: this group's are added to them in the kernel (act | BN_BWD_ACCUMULATE)."""
     n, ch, h, w = y.shape
     npix = n * h * w
     nblk = _lib.query("ir2rgb_bn_bwd_blocks", npix, ch)
     dev = y.device
     if params is not None:
         dgamma, dbeta = params
-        act |= 32
+        act |= BN_BWD_ACCUMULATE
         buf = torch.empty((nblk * 2 + 3) * ch, dtype=torch.float32, device=dev)
         ppartial = buf.data_ptr()
     else:
@@ -464,7 +467,7 @@ def _output_grad(ctx, gz, y, scale, shift, mean, invstd):
         return gz, g64, g8, dbias, None, None
     gz = _as_half_nhwc(gz, hdt)
     if ctx.has_bn:
-        gy, dgamma, dbeta = _bn_grad(gz, y, scale, shift, mean, invstd, spec["act"] | (16 if ctx.frozen else 0))
+        gy, dgamma, dbeta = _bn_grad(gz, y, scale, shift, mean, invstd, spec["act"] | (BN_BWD_FROZEN if ctx.frozen else 0))
         # training mode: BatchNorm removes the per-channel mean, the bias gradient is exactly 0 (None = zeros);
         # evaluation mode: the layer is affine in the bias, d/dbias = scale * sum g' (the same running statistics for
         # every sample group)

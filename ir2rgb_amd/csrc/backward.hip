@@ -1,34 +1,12 @@
 // backward.hip -- HBM-bound backward companions of the MFMA convolution (gfx950):
-//   * bn_bwd_reduce / bn_bwd_finalize / bn_bwd_apply : backward of activation + training-mode
-//     BatchNorm2d on NHWC half tensors, producing the gradient w.r.t. the convolution output
-//     plus dgamma / dbeta (and the bias gradient of norm-less stages);
+//   * bn_bwd_onepass, or bn_bwd_reduce + bn_bwd_finalize_apply : backward of activation + BatchNorm2d on NHWC half
+//     tensors, producing the gradient w.r.t. the convolution output plus dgamma / dbeta (formulas: bn.h);
+//     bn_bwd_reduce + bn_bwd_finalize + bn_bwd_apply : the same for a norm-less stage (activation and bias gradient);
 //   * fold_reflect : adjoint of nn.ReflectionPad2d -- folds the border of the padded-domain
 //     gradient produced by the data-gradient convolution back into the image;
 //   * xexpand_bwd  : adjoint of the x-direction im2col of the first layers.
 // Reductions are two-level and deterministic (per-block partial rows, then a finalize kernel).
-#include "common.h"
-
-__device__ __forceinline__ void unpack8(const uint4 &v, float *f, int dt) {
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        f[2 * j] = h2f((uint16_t)(w[j] & 0xffff), dt);
-        f[2 * j + 1] = h2f((uint16_t)(w[j] >> 16), dt);
-    }
-}
-__device__ __forceinline__ uint4 pack8(const float *f, int dt) {
-    uint32_t w[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) w[j] = (uint32_t)f2h(f[2 * j], dt) | ((uint32_t)f2h(f[2 * j + 1], dt) << 16);
-    return make_uint4(w[0], w[1], w[2], w[3]);
-}
-
-// g' = gz * act'(pre) where pre = y*scale+shift (BN output) or y itself (scale == nullptr)
-__device__ __forceinline__ float act_grad(float g, float pre, int act) {
-    if (act == 1) return pre > 0.f ? g : 0.f;
-    if (act == 2) return pre > 0.f ? g : 0.2f * g;
-    return g;
-}
+#include "bn.h"
 
 // One block (512 threads) = one 64-channel group x one pixel range.  partial[r][0][c] = sum g',
 // partial[r][1][c] = sum g' * yhat over range r.  Thread t owns channel octet t & 7 of the group
@@ -68,17 +46,7 @@ bn_bwd_reduce_kernel(const uint4 *__restrict__ gz, const uint4 *__restrict__ y, 
             yq[u] = ok ? y[q * octs + lane_off] : make_uint4(0, 0, 0, 0);
         }
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            float g[8], v[8];
-            unpack8(gq[u], g, dt);
-            unpack8(yq[u], v, dt);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                float gp = act_grad(g[j], v[j] * sc[j] + sh[j], act);   // g == 0 for the padding rows
-                s1[j] += gp;
-                s2[j] += gp * (v[j] - mu[j]) * is[j];
-            }
-        }
+        for (int u = 0; u < 4; ++u) bn_bwd_sums8(gq[u], yq[u], sc, sh, mu, is, act, dt, true, s1, s2);   // g == 0 for the padding rows
     }
     // the 8 pixel rows of a wave (lane bits 3..5), then the 8 waves through LDS in wave order
 #pragma unroll
@@ -103,82 +71,39 @@ bn_bwd_reduce_kernel(const uint4 *__restrict__ gz, const uint4 *__restrict__ y, 
     }
 }
 
-// One block (1024 threads) per 64-channel group: dbeta[c] = sum_r partial[r][0][c],
-// dgamma[c] = sum_r partial[r][1][c] (R <= 128 rows: thread = (value, slice of 16 rows), every load
-// of a thread in flight at once; slices and rows are added in a fixed order, in double), and the
-// three coefficient vectors of the apply pass:  gy = cA*g' + cB*y + cC
-//   cA = scale, cB = -scale*invstd*dgamma/n, cC = scale*(invstd*mean*dgamma/n - dbeta/n).
+// The two kernels behind bn_bwd_reduce_kernel for a stage WITHOUT a norm layer (scale == nullptr there: g' = gz * act'(y)).
+// One block (1024 threads) per 64-channel group: dbeta[c] = sum_r partial[r][0][c], the bias gradient, and
+// dgamma[c] = sum_r partial[r][1][c] (R <= 128 rows: thread = (value, slice of 16 rows), every load of a thread in
+// flight at once; slices and rows are added in a fixed order, in double).
 __global__ void __launch_bounds__(1024)
-bn_bwd_finalize_kernel(const float *__restrict__ partial, int R, int C, const float *__restrict__ scale,
-                       const float *__restrict__ mean, const float *__restrict__ invstd, float inv_n,
-                       float *__restrict__ dgamma, float *__restrict__ dbeta, float *__restrict__ coef, int acc) {
+bn_bwd_finalize_kernel(const float *__restrict__ partial, int R, int C, float *__restrict__ dgamma,
+                       float *__restrict__ dbeta, int acc) {
     __shared__ double fin[8][2][64];
     const int cg = blockIdx.x;
     {
         const int slice = threadIdx.x >> 7, which = (threadIdx.x >> 6) & 1, cl = threadIdx.x & 63;
-        float t[16];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) {     // unconditional loads of a clamped row, masked below: a predicated load
-            const int k = min(slice + 8 * u, R - 1);   // compiles to a branch with its own s_waitcnt (16 serial round trips)
-            t[u] = partial[((long)k * 2 + which) * C + cg * 64 + cl];
-        }
-        double a = 0.0;
-#pragma unroll
-        for (int u = 0; u < 16; ++u) a += slice + 8 * u < R ? (double)t[u] : 0.0;
-        fin[slice][which][cl] = a;
+        fin[slice][which][cl] = bn_bwd_slice_sum(partial, slice, R, which, C, cg * 64 + cl);
     }
     __syncthreads();
     if (threadIdx.x < 64) {
-        const int cl = threadIdx.x, c = cg * 64 + cl;
+        const int cl = threadIdx.x;
         double a = 0.0, b = 0.0;
 #pragma unroll
         for (int k = 0; k < 8; ++k) { a += fin[k][0][cl]; b += fin[k][1][cl]; }
-        // (acc: the parameter gradients of an earlier sample group of the same layer are already there)
-        dbeta[c] = (acc ? dbeta[c] : 0.f) + (float)a;
-        dgamma[c] = (acc ? dgamma[c] : 0.f) + (float)b;
-        if (scale) {
-            const float scv = scale[c], isv = invstd[c], muv = mean[c];
-            const float dg = (float)b * inv_n, db = (float)a * inv_n;
-            coef[c] = scv;
-            coef[C + c] = -scv * isv * dg;
-            coef[2 * C + c] = scv * (isv * muv * dg - db);
-        }
+        bn_bwd_param_grads(a, b, cg * 64 + cl, dgamma, dbeta, acc);
     }
 }
 
-// gy = cA*g' + cB*y + cC, g' = gz * act'(y*scale + shift)   (BatchNorm stage; coef = [cA|cB|cC])
-// gy = g' = gz * act'(y)                                     (scale == nullptr: activation only)
-// The grid-stride (a multiple of 256 items) is a multiple of C/8, so a lane keeps its channel octet
-// for the whole loop and the per-channel vectors are loaded once.
+// gy = g' = gz * act'(y)
 __global__ void __launch_bounds__(256)
-bn_bwd_apply_kernel(const uint4 *__restrict__ gz, const uint4 *__restrict__ y, const float *__restrict__ scale,
-                    const float *__restrict__ shift, const float *__restrict__ coef, uint4 *__restrict__ gy,
-                    long total8, int C8, int act, int dt) {
-    const long i0 = blockIdx.x * (long)blockDim.x + threadIdx.x;
-    const int c0 = (int)(i0 % C8) * 8, C = C8 * 8;
-    float sc[8], sh[8], cA[8], cB[8], cC[8];
-    if (scale) {
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const float4 a = *reinterpret_cast<const float4 *>(scale + c0 + 4 * h), b = *reinterpret_cast<const float4 *>(shift + c0 + 4 * h);
-            const float4 k0 = *reinterpret_cast<const float4 *>(coef + c0 + 4 * h), k1 = *reinterpret_cast<const float4 *>(coef + C + c0 + 4 * h),
-                         k2 = *reinterpret_cast<const float4 *>(coef + 2 * C + c0 + 4 * h);
-            sc[4 * h] = a.x; sc[4 * h + 1] = a.y; sc[4 * h + 2] = a.z; sc[4 * h + 3] = a.w;
-            sh[4 * h] = b.x; sh[4 * h + 1] = b.y; sh[4 * h + 2] = b.z; sh[4 * h + 3] = b.w;
-            cA[4 * h] = k0.x; cA[4 * h + 1] = k0.y; cA[4 * h + 2] = k0.z; cA[4 * h + 3] = k0.w;
-            cB[4 * h] = k1.x; cB[4 * h + 1] = k1.y; cB[4 * h + 2] = k1.z; cB[4 * h + 3] = k1.w;
-            cC[4 * h] = k2.x; cC[4 * h + 1] = k2.y; cC[4 * h + 2] = k2.z; cC[4 * h + 3] = k2.w;
-        }
-    }
-    for (long i = i0; i < total8; i += (long)gridDim.x * blockDim.x) {
+bn_bwd_apply_kernel(const uint4 *__restrict__ gz, const uint4 *__restrict__ y, uint4 *__restrict__ gy, long total8,
+                    int act, int dt) {
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total8; i += (long)gridDim.x * blockDim.x) {
         float g[8], v[8], o[8];
         unpack8(gz[i], g, dt);
         unpack8(y[i], v, dt);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            if (scale) o[j] = cA[j] * act_grad(g[j], v[j] * sc[j] + sh[j], act) + cB[j] * v[j] + cC[j];
-            else o[j] = act_grad(g[j], v[j], act);
-        }
+        for (int j = 0; j < 8; ++j) o[j] = act_grad(g[j], v[j], act);
         gy[i] = pack8(o, dt);
     }
 }
@@ -202,29 +127,17 @@ bn_bwd_finalize_apply_kernel(const float *__restrict__ partial, int R, int C, co
         // order (slice k = rows k, k+8, k+16, ...), so that (group 0) + (group 1) = its slice-ordered total
         const int cl = threadIdx.x & 63, which = (threadIdx.x >> 6) & 1, h = threadIdx.x >> 7;
         double a = 0.0;
-        for (int k = 4 * h; k < 4 * h + 4; ++k) {
-            float t[16];
-#pragma unroll
-            for (int u = 0; u < 16; ++u) t[u] = partial[((long)min(k + 8 * u, R - 1) * 2 + which) * C + c0 + cl];
-            double sl = 0.0;
-#pragma unroll
-            for (int u = 0; u < 16; ++u) sl += k + 8 * u < R ? (double)t[u] : 0.0;
-            a += sl;
-        }
+        for (int k = 4 * h; k < 4 * h + 4; ++k) a += bn_bwd_slice_sum(partial, k, R, which, C, c0 + cl);
         fin[h][which][cl] = a;
     }
     __syncthreads();
     if (threadIdx.x < 64) {
         const int cl = threadIdx.x, c = c0 + cl;
         const double a = fin[0][0][cl] + fin[1][0][cl], b = fin[0][1][cl] + fin[1][1][cl];
-        const float scv = scale[c], isv = invstd[c], muv = mean[c];
-        const float dg = (float)b * inv_n, db = (float)a * inv_n;
-        co[0][cl] = scv;
-        co[1][cl] = -scv * isv * dg;
-        co[2][cl] = scv * (isv * muv * dg - db);
-        ssc[cl] = scv;
+        bn_bwd_coef(a, b, scale[c], invstd[c], mean[c], inv_n, co[0][cl], co[1][cl], co[2][cl]);
+        ssc[cl] = scale[c];
         ssh[cl] = shift[c];
-        if (blockIdx.y == 0) { dbeta[c] = (acc ? dbeta[c] : 0.f) + (float)a; dgamma[c] = (acc ? dgamma[c] : 0.f) + (float)b; }
+        if (blockIdx.y == 0) bn_bwd_param_grads(a, b, c, dgamma, dbeta, acc);
     }
     __syncthreads();
     const int oc = threadIdx.x & 7, prow = threadIdx.x >> 3;
@@ -248,12 +161,7 @@ bn_bwd_finalize_apply_kernel(const float *__restrict__ partial, int R, int C, co
         for (int u = 0; u < 4; ++u) {
             const long q = p + 32 * u;
             if (q >= p_end) break;
-            float g[8], v[8], o[8];
-            unpack8(gq[u], g, dt);
-            unpack8(yq[u], v, dt);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) o[j] = cA[j] * act_grad(g[j], v[j] * sc[j] + sh[j], act) + cB[j] * v[j] + cC[j];
-            gy[q * C8 + cg * 8 + oc] = pack8(o, dt);
+            gy[q * C8 + cg * 8 + oc] = bn_bwd_gy8(gq[u], yq[u], sc, sh, cA, cB, cC, act, dt);
         }
     }
 }
@@ -294,6 +202,29 @@ fold_reflect_kernel(const uint4 *__restrict__ dxpad, uint4 *__restrict__ dx, int
 // and the Cin values wanted from a row sit in that one row -- one thread per (channel, pixel) fetched every row Cin times
 // from waves far apart (84 us for a 512x1024 image at 6 channels; the tensors are 20 us of HBM time).
 #define XB_MAXC 32
+// f(kx, ox) for every expanded pixel (tap kx of output column ox) that forward filled from input column ix, kx outer
+// and the mirror candidates inner: the order both kernels below add in (their sums are bit-identical).
+template <class F>
+__device__ __forceinline__ void xexpand_sources(int ix, int W, int Wout, int KW, int sx, int px, int pad_mode, F &&f) {
+    // unpadded source positions that map to ix: ix itself, and its mirror images under reflection
+    int cand[3], nc = 0;
+    cand[nc++] = ix;
+    if (pad_mode) {
+        if (ix >= 1) cand[nc++] = -ix;
+        if (ix <= W - 2) cand[nc++] = 2 * W - 2 - ix;
+    }
+    for (int kx = 0; kx < KW; ++kx)
+        for (int q = 0; q < nc; ++q) {
+            const int t = cand[q] + px - kx;  // = ox * sx
+            if (t < 0 || (t % sx) != 0) continue;
+            const int ox = t / sx;
+            if (ox >= Wout) continue;
+            const int src = ox * sx + kx - px;  // must lie inside the padded range actually read in forward
+            if (src < -px || src > W - 1 + px) continue;
+            f(kx, ox);
+        }
+}
+
 __global__ void __launch_bounds__(256)
 xexpand_bwd_kernel(const uint16_t *__restrict__ dxe, float *__restrict__ din, int Cin, int H, int W, int Wout, int KW,
                    int sx, int px, int pad_mode, long total, int dt) {
@@ -305,26 +236,12 @@ xexpand_bwd_kernel(const uint16_t *__restrict__ dxe, float *__restrict__ din, in
         float acc[XB_MAXC];
 #pragma unroll
         for (int c = 0; c < XB_MAXC; ++c) acc[c] = 0.f;
-        // unpadded source positions that map to ix: ix itself, and its mirror images under reflection
-        int cand[3], nc = 0;
-        cand[nc++] = ix;
-        if (pad_mode) {
-            if (ix >= 1) cand[nc++] = -ix;
-            if (ix <= W - 2) cand[nc++] = 2 * W - 2 - ix;
-        }
-        for (int kx = 0; kx < KW; ++kx)
-            for (int q = 0; q < nc; ++q) {
-                const int t = cand[q] + px - kx;  // = ox * sx
-                if (t < 0 || (t % sx) != 0) continue;
-                const int ox = t / sx;
-                if (ox >= Wout) continue;
-                const int src = ox * sx + kx - px;  // must lie inside the padded range actually read in forward
-                if (src < -px || src > W - 1 + px) continue;
-                const uint16_t *row = dxe + ((n * H + y) * (long)Wout + ox) * 64 + kx;
+        xexpand_sources(ix, W, Wout, KW, sx, px, pad_mode, [&](int kx, int ox) {
+            const uint16_t *row = dxe + ((n * H + y) * (long)Wout + ox) * 64 + kx;
 #pragma unroll
-                for (int c = 0; c < XB_MAXC; ++c)
-                    if (c < Cin) acc[c] += h2f(row[c * KW], dt);
-            }
+            for (int c = 0; c < XB_MAXC; ++c)
+                if (c < Cin) acc[c] += h2f(row[c * KW], dt);
+        });
 #pragma unroll
         for (int c = 0; c < XB_MAXC; ++c)
             if (c < Cin) din[((n * Cin + c) * H + y) * (long)W + ix] = acc[c];
@@ -375,31 +292,18 @@ xexpand_bwd_tile_kernel(const uint4 *__restrict__ dxe, float *__restrict__ din, 
     float acc[XB_MAXC / 2];
 #pragma unroll
     for (int j = 0; j < XB_MAXC / 2; ++j) acc[j] = 0.f;
-    int cand[3], nc = 0;
-    cand[nc++] = ix;
-    if (pad_mode) {
-        if (ix >= 1) cand[nc++] = -ix;
-        if (ix <= W - 2) cand[nc++] = 2 * W - 2 - ix;
-    }
-    for (int kx = 0; kx < KW; ++kx)
-        for (int q = 0; q < nc; ++q) {
-            const int t = cand[q] + px - kx;  // = ox * sx
-            if (t < 0 || (t % sx) != 0) continue;
-            const int ox = t / sx;
-            if (ox >= Wout) continue;
-            const int s = ox * sx + kx - px;  // must lie inside the padded range actually read in forward
-            if (s < -px || s > W - 1 + px) continue;
-            const uint32_t *r = xrows + (ox - oxlo) * XB_PITCH;
+    xexpand_sources(ix, W, Wout, KW, sx, px, pad_mode, [&](int kx, int ox) {
+        const uint32_t *r = xrows + (ox - oxlo) * XB_PITCH;
 #pragma unroll
-            for (int j = 0; j < XB_MAXC / 2; ++j) {
-                const int c = par + 2 * j;
-                if (c < Cin) {
-                    const int e = c * KW + kx;
-                    const uint32_t w = r[e >> 1];
-                    acc[j] += h2f((uint16_t)((e & 1) ? (w >> 16) : (w & 0xffff)), dt);
-                }
+        for (int j = 0; j < XB_MAXC / 2; ++j) {
+            const int c = par + 2 * j;
+            if (c < Cin) {
+                const int e = c * KW + kx;
+                const uint32_t w = r[e >> 1];
+                acc[j] += h2f((uint16_t)((e & 1) ? (w >> 16) : (w & 0xffff)), dt);
             }
         }
+    });
 #pragma unroll
     for (int j = 0; j < XB_MAXC / 2; ++j) {
         const int c = par + 2 * j;
@@ -456,14 +360,9 @@ thin_grad_expand_kernel(const float *__restrict__ gz, uint4 *__restrict__ g64, u
     }
 }
 
-// R pixel ranges per 64-channel group: about 512 blocks of 512 threads in all, at least 128 pixels
-// per range and at most 128 ranges (bn_bwd_finalize_kernel's 8 slices x 16 rows).
-static int bn_bwd_ranges(long npix, int C) {
-    long want = 512 / (C / 64);
-    want = want < 8 ? 8 : (want > 128 ? 128 : want);
-    const long cap = (npix + 127) / 128;
-    return (int)(want < cap ? want : cap);
-}
+// R pixel ranges per 64-channel group for bn_bwd_reduce_kernel: about 512 blocks of 512 threads in all, at least 128
+// pixels per range and at most 128 ranges (bn_bwd_slice_sum's 8 slices x 16 rows).
+static BnChunks bn_bwd_ranges(long npix, int C) { return bn_chunks(npix, C, 512, 8, 128); }
 
 // ----------------------------------------------------------------------------------------
 // BatchNorm backward in ONE launch for layers with few pixels (the 1024-channel residual blocks at 32x64, the deep
@@ -477,6 +376,9 @@ static int bn_bwd_ranges(long npix, int C) {
 //   thread t: channel octet t % (CPB/8), pixels t / (CPB/8) + k * (512 / (CPB/8)), k < K
 // Sums: per thread in fp32, across the lanes of a wave by shuffles, across the 8 waves in wave order in double.
 // ----------------------------------------------------------------------------------------
+// (This kernel writes the sums, the coefficients and gy out itself instead of calling bn.h: built from the shared device
+// functions it computed the same bits but took 1 % longer at 1024 ch x 32x64 -- 11.20 -> 11.31 us, 30 instructions and
+// 5 waits more at K = 4 -- so it keeps the code hipcc schedules best.  Its gy contracts fma(cA, g', cB*y) + cC.)
 template <int K, int CPB>
 __global__ void __launch_bounds__(512)
 bn_bwd_onepass_kernel(const uint4 *__restrict__ gz, const uint4 *__restrict__ y, const float *__restrict__ scale,
@@ -584,64 +486,54 @@ static bool bn_bwd_onepass_launch(int K, dim3 grid, hipStream_t s, const uint4 *
 
 extern "C" int ir2rgb_bn_bwd_blocks(long npix, int C) {
     if (npix < 1 || C < 64 || (C & (C - 1)) || C > 2048) return IR2RGB_EINVAL;
-    const int R = bn_bwd_ranges(npix, C);
-    const long per = (npix + R - 1) / R;
-    return (int)((npix + per - 1) / per);
+    return bn_bwd_ranges(npix, C).n;
 }
 
 extern "C" int ir2rgb_bn_bwd(const void *gz, const void *y, const float *scale, const float *shift, const float *mean,
                              const float *invstd, void *gy, float *dgamma, float *dbeta, float *partial, long npix,
                              int C, int act, int dtype, void *stream) {
-    const int R = ir2rgb_bn_bwd_blocks(npix, C);
-    if (R < 0) return R;
+    const int rc = ir2rgb_bn_bwd_blocks(npix, C);
+    if (rc < 0) return rc;
     if (dtype != IR2RGB_BF16 && dtype != IR2RGB_F16) return IR2RGB_ENOSUP;
-    const bool frozen = act >= 0 && (act & 16);   // evaluation-mode BatchNorm: the mean / variance terms vanish
-    const int acc = act >= 0 && (act & 32) ? 1 : 0;   // dgamma / dbeta += (a later sample group of a batched forward)
+    const bool frozen = act >= 0 && (act & IR2RGB_BN_BWD_FROZEN);   // evaluation-mode BatchNorm: the mean / variance terms vanish
+    const int acc = act >= 0 && (act & IR2RGB_BN_BWD_ACCUMULATE) ? 1 : 0;   // dgamma / dbeta += (a later sample group of a batched forward)
     if (act >= 0) act &= 15;
     if (!gz || !y || !gy || !dgamma || !dbeta || !partial || act < 0 || act > 2) return IR2RGB_EINVAL;
-    const int R0 = bn_bwd_ranges(npix, C);
-    const long per = (npix + R0 - 1) / R0;
+    const bool norm = scale != nullptr;      // a BatchNorm stage hands over all four vectors, a norm-less stage none
+    if ((shift != nullptr) != norm || (mean != nullptr) != norm || (invstd != nullptr) != norm) return IR2RGB_EINVAL;
     hipStream_t s = as_stream(stream);
+    const uint4 *gz4 = (const uint4 *)gz, *y4 = (const uint4 *)y;
+    uint4 *gy4 = (uint4 *)gy;
+    const float inv_n = frozen ? 0.f : 1.0f / (float)npix;
     // few pixels per channel: the one-launch form (a workgroup owns CPB channels over all pixels, slabs in registers).
     // 8 channels per workgroup while that gives at most 8 loads per tensor and thread, else not applicable; wider
     // groups (better coalescing, fewer workgroups) when the layer still yields >= 128 workgroups.
-    {
-        if (scale && shift && mean && invstd && !frozen && npix <= 8 * 512) {
-            const float inv_n = 1.0f / (float)npix;
-            bool done;
-            const int min_wg = 128;
-            if (C / 32 >= min_wg && npix * 4 <= 8 * 512)
-                done = bn_bwd_onepass_launch<32>((int)((npix * 4 + 511) / 512), dim3(C / 32), s, (const uint4 *)gz, (const uint4 *)y, scale, shift,
-                                                 mean, invstd, (uint4 *)gy, dgamma, dbeta, npix, C, act, dtype, inv_n, acc);
-            else if (C / 16 >= min_wg && npix * 2 <= 8 * 512)
-                done = bn_bwd_onepass_launch<16>((int)((npix * 2 + 511) / 512), dim3(C / 16), s, (const uint4 *)gz, (const uint4 *)y, scale, shift,
-                                                 mean, invstd, (uint4 *)gy, dgamma, dbeta, npix, C, act, dtype, inv_n, acc);
-            else
-                done = bn_bwd_onepass_launch<8>((int)((npix + 511) / 512), dim3(C / 8), s, (const uint4 *)gz, (const uint4 *)y, scale, shift,
-                                                mean, invstd, (uint4 *)gy, dgamma, dbeta, npix, C, act, dtype, inv_n, acc);
-            if (done) return ir2rgb_launch_status();
-        }
+    if (norm && !frozen && npix <= 8 * 512) {
+        const int min_wg = 128;
+        auto onepass = [&](auto cpb) {
+            constexpr int CPB = decltype(cpb)::value;
+            return bn_bwd_onepass_launch<CPB>((int)((npix * (CPB / 8) + 511) / 512), dim3(C / CPB), s, gz4, y4, scale, shift, mean,
+                                              invstd, gy4, dgamma, dbeta, npix, C, act, dtype, inv_n, acc);
+        };
+        bool done;
+        if (C / 32 >= min_wg && npix * 4 <= 8 * 512) done = onepass(std::integral_constant<int, 32>{});
+        else if (C / 16 >= min_wg && npix * 2 <= 8 * 512) done = onepass(std::integral_constant<int, 16>{});
+        else done = onepass(std::integral_constant<int, 8>{});
+        if (done) return ir2rgb_launch_status();
     }
-    // partial holds R*2*C floats followed by 3*C coefficient floats (see ir2rgb_hip.h)
-    float *coef = partial + (long)R * 2 * C;
-    bn_bwd_reduce_kernel<<<R * (C / 64), 512, 0, s>>>((const uint4 *)gz, (const uint4 *)y, scale, shift, mean, invstd,
-                                                      partial, npix, C, act, dtype, per);
-    if (scale && shift && mean && invstd) {
-        long chunks = 2048 / (C / 64);
-        const long cap = (npix + 127) / 128;
-        chunks = chunks < 1 ? 1 : (chunks > cap ? cap : chunks);
-        const long pp = (npix + chunks - 1) / chunks;
-        dim3 grid((unsigned)(C / 64), (unsigned)((npix + pp - 1) / pp));
-        bn_bwd_finalize_apply_kernel<<<grid, 256, 0, s>>>(partial, R, C, scale, shift, mean, invstd,
-                                                          frozen ? 0.f : 1.0f / (float)npix, dgamma, dbeta, (const uint4 *)gz,
-                                                          (const uint4 *)y, (uint4 *)gy, npix, act, dtype, pp, acc);
+    // partial holds R*2*C floats (and a reserved tail of 3*C, see ir2rgb_hip.h)
+    const BnChunks ranges = bn_bwd_ranges(npix, C);
+    const int R = ranges.n;
+    bn_bwd_reduce_kernel<<<R * (C / 64), 512, 0, s>>>(gz4, y4, scale, shift, mean, invstd, partial, npix, C, act, dtype, ranges.per);
+    if (norm) {
+        const BnChunks ch = bn_apply_chunks(npix, C);
+        bn_bwd_finalize_apply_kernel<<<dim3((unsigned)(C / 64), (unsigned)ch.n), 256, 0, s>>>(
+            partial, R, C, scale, shift, mean, invstd, inv_n, dgamma, dbeta, gz4, y4, gy4, npix, act, dtype, ch.per, acc);
         return ir2rgb_launch_status();
     }
-    bn_bwd_finalize_kernel<<<C / 64, 1024, 0, s>>>(partial, R, C, scale, mean, invstd, frozen ? 0.f : 1.0f / (float)npix, dgamma, dbeta,
-                                                  coef, acc);
-    long total8 = npix * (C / 8);
-    bn_bwd_apply_kernel<<<stream_grid(total8, 256), 256, 0, s>>>((const uint4 *)gz, (const uint4 *)y, scale, shift, coef,
-                                                                 (uint4 *)gy, total8, C / 8, act, dtype);
+    bn_bwd_finalize_kernel<<<C / 64, 1024, 0, s>>>(partial, R, C, dgamma, dbeta, acc);
+    const long total8 = npix * (C / 8);
+    bn_bwd_apply_kernel<<<stream_grid(total8, 256), 256, 0, s>>>(gz4, y4, gy4, total8, act, dtype);
     return ir2rgb_launch_status();
 }
 

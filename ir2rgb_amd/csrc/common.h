@@ -89,6 +89,29 @@ static __device__ __forceinline__ uint16_t f2h(float f, int dt) {
     return __builtin_bit_cast(uint16_t, h);
 }
 
+// 8 halfs of a 16-byte lane <-> 8 floats (the NHWC side of the HBM-bound kernels)
+__device__ __forceinline__ void unpack8(const uint4 &v, float *f, int dt) {
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        f[2 * j] = h2f((uint16_t)(w[j] & 0xffff), dt);
+        f[2 * j + 1] = h2f((uint16_t)(w[j] >> 16), dt);
+    }
+}
+__device__ __forceinline__ uint4 pack8(const float *f, int dt) {
+    uint32_t w[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) w[j] = (uint32_t)f2h(f[2 * j], dt) | ((uint32_t)f2h(f[2 * j + 1], dt) << 16);
+    return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+// g' = gz * act'(pre) where pre = y*scale+shift (BN output) or y itself (scale == nullptr)
+__device__ __forceinline__ float act_grad(float g, float pre, int act) {
+    if (act == 1) return pre > 0.f ? g : 0.f;
+    if (act == 2) return pre > 0.f ? g : 0.2f * g;
+    return g;
+}
+
 __device__ __forceinline__ unsigned fdiv(unsigned n, FastDiv f) {
     if (f.sh == 32) return n;
     const unsigned t = __umulhi(f.m, n);

@@ -6,7 +6,7 @@
 //   * xexpand: x-direction im2col for the small-Cin first layers (7x7 on 9/6 channels, 4x4 on
 //     6/13 channels) so they run on the same MFMA kernel as a k x 1 convolution over 64 channels.
 // All kernels move 16 bytes per lane on the NHWC side.
-#include "common.h"
+#include "bn.h"
 
 // ----------------------------------------------------------------------------------------
 // BatchNorm statistics: reduce the per-tile partials written by the conv epilogue.
@@ -57,30 +57,8 @@ bn_finalize_kernel(const float *__restrict__ partial, int rows, int C, double co
     // compiler spilled 7 of them (a kernel with scratch pays for it at every dispatch)
 #pragma unroll 8
     for (int r = 0; r < RG; ++r) { s1 += red[0][r][cl]; s2 += red[1][r][cl]; }
-    double mean = s1 / count;
-    double var = s2 / count - mean * mean;
-    var = (var > 0.0 || var != var) ? var : 0.0;      // (a NaN variance -- an overflowed forward -- stays NaN)
-    float invstd = (float)(1.0 / sqrt(var + (double)eps));
-    float g = gamma ? gamma[c] : 1.f, b = beta ? beta[c] : 0.f;
-    float sc = g * invstd;
-    scale[c] = sc;
-    shift[c] = b - (float)mean * sc;
-    if (mean_out) mean_out[c] = (float)mean;
-    if (invstd_out) invstd_out[c] = invstd;
-    // stat_updates > 1: this forward stands for that many identical forwards of the reference.
-    // conv_bias: the statistics are those of the bias-free convolution output; nn.BatchNorm2d saw y + bias
-    if (running_mean) {
-        float r = running_mean[c];
-        const float m = (float)mean + (conv_bias ? conv_bias[c] : 0.f);
-        for (int u = 0; u < stat_updates; ++u) r = (1.f - momentum) * r + momentum * m;
-        running_mean[c] = r;
-    }
-    if (running_var) {
-        double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
-        float r = running_var[c];
-        for (int u = 0; u < stat_updates; ++u) r = (1.f - momentum) * r + momentum * (float)unbiased;
-        running_var[c] = r;
-    }
+    bn_channel_stats(s1, s2, count, c, gamma, beta, conv_bias, running_mean, running_var, momentum, eps, stat_updates, true,
+                     scale, shift, mean_out, invstd_out);
 }
 
 // Evaluation-mode BatchNorm2d (module.eval(), running statistics): scale / shift for a bias-free input y,
@@ -177,32 +155,10 @@ bn_finalize_apply_kernel(const float *__restrict__ partial, int rows, int C, dou
     if (threadIdx.x < 64) {
         const int cl = threadIdx.x, c = c0 + cl;
         const double s1 = red[0][0][cl] + red[1][0][cl], s2 = red[0][1][cl] + red[1][1][cl];
-        const double mean = s1 / count;
-        double var = s2 / count - mean * mean;
-        var = (var > 0.0 || var != var) ? var : 0.0;      // as bn_finalize_kernel: NaN stays NaN
-        const float invstd = (float)(1.0 / sqrt(var + (double)eps));
-        const float g = gamma ? gamma[c] : 1.f, b = beta ? beta[c] : 0.f;
-        const float sc = g * invstd, sh = b - (float)mean * sc;
-        ssc[cl] = sc;
-        ssh[cl] = sh;
-        if (blockIdx.y == 0) {
-            scale_out[c] = sc;
-            shift_out[c] = sh;
-            if (mean_out) mean_out[c] = (float)mean;
-            if (invstd_out) invstd_out[c] = invstd;
-            if (running_mean) {
-                float r = running_mean[c];
-                const float m = (float)mean + (conv_bias ? conv_bias[c] : 0.f);
-                for (int u = 0; u < stat_updates; ++u) r = (1.f - momentum) * r + momentum * m;
-                running_mean[c] = r;
-            }
-            if (running_var) {
-                const double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
-                float r = running_var[c];
-                for (int u = 0; u < stat_updates; ++u) r = (1.f - momentum) * r + momentum * (float)unbiased;
-                running_var[c] = r;
-            }
-        }
+        const BnScaleShift ss = bn_channel_stats(s1, s2, count, c, gamma, beta, conv_bias, running_mean, running_var, momentum,
+                                                 eps, stat_updates, blockIdx.y == 0, scale_out, shift_out, mean_out, invstd_out);
+        ssc[cl] = ss.sc;
+        ssh[cl] = ss.sh;
     }
     __syncthreads();
     // apply: lane = (pixel row within 32, channel octet of the slice); 16 bytes per lane, 128 bytes per pixel
@@ -225,6 +181,8 @@ bn_finalize_apply_kernel(const float *__restrict__ partial, int rows, int C, dou
         for (int u = 0; u < 4; ++u) {
             const long q = p + 32 * u;
             if (q >= p_end) break;
+            // (the body of bn_apply_kernel, written out: as a device function shared by the two, hipcc takes 102 VGPRs for
+            // the bf16 kernel instead of 93 -- 4 waves per SIMD instead of 5 -- whichever way its operands are passed)
             const uint32_t w[4] = {vx[u].x, vx[u].y, vx[u].z, vx[u].w}, a[4] = {va[u].x, va[u].y, va[u].z, va[u].w},
                            b[4] = {vb[u].x, vb[u].y, vb[u].z, vb[u].w};
             uint32_t o[4];
@@ -252,10 +210,11 @@ bn_finalize_apply_kernel(const float *__restrict__ partial, int rows, int C, dou
 //   NCHW fp32 [N][C][HW]  <->  NHWC half [N][HW][C]
 // tile = 64 pixels x 64 channels per workgroup of 256 threads.
 // ----------------------------------------------------------------------------------------
-template <int DT>
+// SLICE: into channels [c_off, c_off + C) of pixels of ld channels, with LeakyReLU(0.1) when act == 2; otherwise dense
+template <int DT, bool SLICE>
 __global__ void __launch_bounds__(256)
-nchw_to_nhwc_slice_kernel(const float *__restrict__ in, uint16_t *__restrict__ out, int C, long HW, int ld, int c_off,
-                          int act) {
+nchw_to_nhwc_kernel(const float *__restrict__ in, uint16_t *__restrict__ out, int C, long HW, int ld, int c_off, int act) {
+    if (!SLICE) { ld = C; c_off = 0; act = 0; }
     __shared__ float tile[64][65];
     const long p0 = (long)blockIdx.x * 64;
     const int c0 = blockIdx.y * 64, n = blockIdx.z;
@@ -270,24 +229,6 @@ nchw_to_nhwc_slice_kernel(const float *__restrict__ in, uint16_t *__restrict__ o
     for (int j = ty; j < 64; j += 4) {
         long p = p0 + j; int c = c0 + tx;
         if (p < HW && c < C) out[((long)n * HW + p) * ld + c_off + c] = f2h(tile[tx][j], DT);
-    }
-}
-
-template <int DT>
-__global__ void __launch_bounds__(256)
-nchw_to_nhwc_kernel(const float *__restrict__ in, uint16_t *__restrict__ out, int C, long HW) {
-    __shared__ float tile[64][65];
-    const long p0 = (long)blockIdx.x * 64;
-    const int c0 = blockIdx.y * 64, n = blockIdx.z;
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-    for (int j = ty; j < 64; j += 4) {
-        int c = c0 + j; long p = p0 + tx;
-        tile[j][tx] = (c < C && p < HW) ? in[((long)n * C + c) * HW + p] : 0.f;
-    }
-    __syncthreads();
-    for (int j = ty; j < 64; j += 4) {
-        long p = p0 + j; int c = c0 + tx;
-        if (p < HW && c < C) out[((long)n * HW + p) * C + c] = f2h(tile[tx][j], DT);
     }
 }
 
@@ -425,17 +366,13 @@ extern "C" int ir2rgb_bn_finalize_apply(const float *stats_partial, int rows, in
         return IR2RGB_EINVAL;
     if (dtype != IR2RGB_BF16 && dtype != IR2RGB_F16) return IR2RGB_ENOSUP;
     if ((((uintptr_t)x | (uintptr_t)y | (uintptr_t)res1 | (uintptr_t)res2) & 15)) return IR2RGB_EALIGN;
-    // about 2048 blocks in all, at least 128 pixels each
-    long chunks = 2048 / (C / 64);
-    const long cap = (npix + 127) / 128;
-    chunks = chunks < 1 ? 1 : (chunks > cap ? cap : chunks);
-    const long per = (npix + chunks - 1) / chunks;
-    dim3 grid((unsigned)(C / 64), (unsigned)((npix + per - 1) / per));
+    const BnChunks ch = bn_apply_chunks(npix, C);
+    dim3 grid((unsigned)(C / 64), (unsigned)ch.n);
     hipStream_t s = as_stream(stream);
     with_dtype(dtype, [&](auto dt) {
         bn_finalize_apply_kernel<dt.value><<<grid, 256, 0, s>>>(stats_partial, rows, C, (double)count, gamma, beta, conv_bias,
             running_mean, running_var, momentum, eps, scale, shift, mean_out, invstd_out, stat_updates, (const uint4 *)x,
-            (const uint4 *)res1, (const uint4 *)res2, (uint4 *)y, npix, act, per);
+            (const uint4 *)res1, (const uint4 *)res2, (uint4 *)y, npix, act, ch.per);
     });
     return ir2rgb_launch_status();
 }
@@ -456,26 +393,38 @@ extern "C" int ir2rgb_bn_apply(const void *x, const float *scale, const float *s
     return ir2rgb_launch_status();
 }
 
-extern "C" int ir2rgb_nchw_f32_to_nhwc_half(const float *in, void *out, int N, int C, int H, int W, int dtype,
-                                            void *stream) {
+// The three converter entry points: the checks they share, the tile grid, then launch(dt, grid, stream).
+template <class L>
+static int convert_launch(int N, int C, int H, int W, int dtype, void *stream, L &&launch) {
     if (N < 0 || C < 1 || H < 1 || W < 1) return IR2RGB_EINVAL;
     if (dtype != IR2RGB_BF16 && dtype != IR2RGB_F16) return IR2RGB_ENOSUP;
     if (N == 0) return IR2RGB_OK;
-    long HW = (long)H * W;
-    dim3 grid((unsigned)cdiv(HW, 64), (unsigned)cdiv(C, 64), (unsigned)N);
-    with_dtype(dtype, [&](auto dt) { nchw_to_nhwc_kernel<dt.value><<<grid, 256, 0, as_stream(stream)>>>(in, (uint16_t *)out, C, HW); });
+    const long HW = (long)H * W;
+    const dim3 grid((unsigned)cdiv(HW, 64), (unsigned)cdiv(C, 64), (unsigned)N);
+    with_dtype(dtype, [&](auto dt) { launch(dt, grid, HW, as_stream(stream)); });
     return ir2rgb_launch_status();
+}
+
+extern "C" int ir2rgb_nchw_f32_to_nhwc_half(const float *in, void *out, int N, int C, int H, int W, int dtype,
+                                            void *stream) {
+    return convert_launch(N, C, H, W, dtype, stream, [&](auto dt, dim3 grid, long HW, hipStream_t s) {
+        nchw_to_nhwc_kernel<dt.value, false><<<grid, 256, 0, s>>>(in, (uint16_t *)out, C, HW, C, 0, 0);
+    });
+}
+
+extern "C" int ir2rgb_nchw_f32_to_nhwc_half_slice(const float *in, void *out, int N, int C, int H, int W, int ld,
+                                                  int c_off, int act, int dtype, void *stream) {
+    if (ld < C || c_off < 0 || c_off + C > ld || (act != 0 && act != 2)) return IR2RGB_EINVAL;
+    return convert_launch(N, C, H, W, dtype, stream, [&](auto dt, dim3 grid, long HW, hipStream_t s) {
+        nchw_to_nhwc_kernel<dt.value, true><<<grid, 256, 0, s>>>(in, (uint16_t *)out, C, HW, ld, c_off, act);
+    });
 }
 
 extern "C" int ir2rgb_nhwc_half_to_nchw_f32(const void *in, float *out, int N, int C, int H, int W, int dtype,
                                             void *stream) {
-    if (N < 0 || C < 1 || H < 1 || W < 1) return IR2RGB_EINVAL;
-    if (dtype != IR2RGB_BF16 && dtype != IR2RGB_F16) return IR2RGB_ENOSUP;
-    if (N == 0) return IR2RGB_OK;
-    long HW = (long)H * W;
-    dim3 grid((unsigned)cdiv(HW, 64), (unsigned)cdiv(C, 64), (unsigned)N);
-    with_dtype(dtype, [&](auto dt) { nhwc_to_nchw_kernel<dt.value><<<grid, 256, 0, as_stream(stream)>>>((const uint16_t *)in, out, C, HW); });
-    return ir2rgb_launch_status();
+    return convert_launch(N, C, H, W, dtype, stream, [&](auto dt, dim3 grid, long HW, hipStream_t s) {
+        nhwc_to_nchw_kernel<dt.value><<<grid, 256, 0, s>>>((const uint16_t *)in, out, C, HW);
+    });
 }
 
 extern "C" int ir2rgb_xexpand_cx(const float *in, void *out, int N, int Cin, int H, int W, int Wout, int KW,
@@ -503,18 +452,6 @@ extern "C" int ir2rgb_xexpand(const float *in, void *out, int N, int Cin, int H,
                               int pad_w, int pad_mode, int dtype, void *stream) {
     return ir2rgb_xexpand_cx(in, out, N, Cin, H, W, Wout, KW, stride_w, pad_w, pad_mode, 64, dtype, stream);
 }
-
-extern "C" int ir2rgb_nchw_f32_to_nhwc_half_slice(const float *in, void *out, int N, int C, int H, int W, int ld,
-                                                  int c_off, int act, int dtype, void *stream) {
-    if (N < 0 || C < 1 || H < 1 || W < 1 || ld < C || c_off < 0 || c_off + C > ld || (act != 0 && act != 2)) return IR2RGB_EINVAL;
-    if (dtype != IR2RGB_BF16 && dtype != IR2RGB_F16) return IR2RGB_ENOSUP;
-    if (N == 0) return IR2RGB_OK;
-    long HW = (long)H * W;
-    dim3 grid((unsigned)cdiv(HW, 64), (unsigned)cdiv(C, 64), (unsigned)N);
-    with_dtype(dtype, [&](auto dt) { nchw_to_nhwc_slice_kernel<dt.value><<<grid, 256, 0, as_stream(stream)>>>(in, (uint16_t *)out, C, HW, ld, c_off, act); });
-    return ir2rgb_launch_status();
-}
-
 
 // ------------------------------------------------------------------------------------------
 // AvgPool2d(3, stride 2, padding 1, count_include_pad=False) on fp32 planes -- the image pyramids of the multi-scale

@@ -195,6 +195,17 @@ def _bn_ptrs(bn):
     return hit
 
 
+def _bn_params(bn):
+    """-> (weight, bias, running_mean, running_var, momentum, eps, tracks) of a BatchNorm module (through _bn_ptrs) or of a
+    padded shadow (autograd._PaddedBN: fresh tensors every call); tracks: it keeps running statistics."""
+    if isinstance(bn, nn.Module):
+        _, w, b, rm, rv, has_rm, momentum, eps, trs = _bn_ptrs(bn)
+    else:
+        w, b, rm, rv, has_rm = bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.running_mean is not None
+        momentum, eps, trs = 0.1 if bn.momentum is None else float(bn.momentum), float(bn.eps), bn.track_running_stats
+    return w, b, rm, rv, momentum, eps, bool(trs and has_rm)
+
+
 def bn_frozen(bn, training):
     """True when nn.BatchNorm2d would normalise with its running statistics (module.eval() and tracked stats)."""
     return (not training) and bn.track_running_stats and bn.running_mean is not None
@@ -205,9 +216,10 @@ def bn_finalize(stats, count, bn, training=True, conv_bias=None, outs=None):
     convolution in front; BatchNorm cancels it, see ir2rgb_bn_finalize_ex).  Training mode: batch statistics
     from the convolution's partial sums, running statistics updated like nn.BatchNorm2d.  Evaluation mode
     (``training=False`` with tracked statistics): the running statistics, nothing updated; ``stats`` may be None."""
-    frozen = bn_frozen(bn, training)
+    w, b, rm, rv, momentum, eps, tracks = _bn_params(bn)
+    frozen = (not training) and tracks
     ch = bn.num_features
-    dev = bn.weight.device if bn.weight is not None else stats.device
+    dev = w.device if w is not None else stats.device
     rows = 0 if stats is None else stats.shape[0]
     if outs is not None:        # caller-owned fp32 [C] vectors (a sample group's rows of ConvStageFn's [4][G][C] block)
         scale, shift, mean, invstd = outs
@@ -216,16 +228,15 @@ def bn_finalize(stats, count, bn, training=True, conv_bias=None, outs=None):
         shift = torch.empty_like(scale)
         mean = torch.empty_like(scale)
         invstd = torch.empty_like(scale)
-    track = training and bn.track_running_stats and bn.running_mean is not None
-    momentum = 0.1 if bn.momentum is None else bn.momentum
+    track = training and tracks
     use_running = track or frozen
     if SC.ENABLED and use_running:
         SC.consumed(bn.running_mean, "BatchNorm running statistics")
         if track:
             SC.produced(bn.running_mean, "BatchNorm running statistics")
-    _lib.launch("ir2rgb_bn_finalize_ex", scale, stats, rows, ch, int(count), bn.weight, bn.bias, conv_bias,
-                bn.running_mean if use_running else None, bn.running_var if use_running else None, float(momentum),
-                float(bn.eps), scale, shift, mean, invstd, _STAT_UPDATES, int(frozen))
+    _lib.launch("ir2rgb_bn_finalize_ex", scale, stats, rows, ch, int(count), w, b, conv_bias,
+                rm if use_running else None, rv if use_running else None, momentum, eps, scale, shift, mean, invstd,
+                _STAT_UPDATES, int(frozen))
     if track and bn.num_batches_tracked is not None:
         _PENDING_COUNTERS.append((bn.num_batches_tracked, _STAT_UPDATES))
     return scale, shift, mean, invstd
@@ -245,12 +256,7 @@ def bn_finalize_apply(stats, count, bn, y, act, res1=None, res2=None, conv_bias=
         vec = torch.empty((4, ch), dtype=torch.float32, device=y.device)   # scale | shift | mean | invstd: one allocation
         scale, shift, mean, invstd = vec[0], vec[1], vec[2], vec[3]
     z = out if out is not None else torch.empty_like(y, memory_format=torch.channels_last)
-    if isinstance(bn, nn.Module):
-        _, pw, pb, prm, prv, has_rm, momentum, eps, trs = _bn_ptrs(bn)
-    else:       # a padded shadow (autograd._PaddedBN): fresh tensors every call
-        pw, pb, prm, prv, has_rm = bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.running_mean is not None
-        momentum, eps, trs = 0.1 if bn.momentum is None else float(bn.momentum), float(bn.eps), bn.track_running_stats
-    track = trs and has_rm
+    pw, pb, prm, prv, momentum, eps, track = _bn_params(bn)
     if SC.ENABLED and track:
         SC.consumed(bn.running_mean, "BatchNorm running statistics")
         SC.produced(bn.running_mean, "BatchNorm running statistics")

@@ -6,6 +6,7 @@ A replay takes a record in the format of tests/window_geometries.json -- a launc
 record, launches the entry point, compares every element with an fp64 reference under a bound of oracle/bounds.py and
 returns the worst err/bound ratio per number format.  Nothing here loads the library before a launch asks for it.
 """
+import hashlib
 import time
 import zlib
 
@@ -32,9 +33,45 @@ def gen(rec):
     return torch.Generator().manual_seed(zlib.crc32(WG.canon(rec).encode()))
 
 
+RECORDER = None     # off unless digests() below installs one
+
+
+def hand(role, name, t):
+    """The one point a replay passes when it hands an operand to a launch (role "in") or a device output to its check
+    ("out"): RECORDER(role, name, t) if a recorder is installed.  -> t"""
+    if RECORDER is not None:
+        RECORDER(role, name, t)
+    return t
+
+
+def digests(fn, *a):
+    """fn(*a) (a replay of one record) under a recorder -> {"in": sha1 of the bytes of every operand handed in, in order,
+    "out": [[name, sha1 of the bytes of that output], ...] in the order the outputs were checked}.  The names carry the
+    number format.  tests/test_pointwise_bits_gpu.py holds the kernels to a table of these, bit for bit."""
+    global RECORDER
+    h_in, out = hashlib.sha1(), []
+
+    def rec(role, name, t):
+        raw = t.detach().cpu().contiguous().reshape(-1).view(torch.uint8).numpy().tobytes()
+        if role == "in":
+            h_in.update(f"{name} {tuple(t.shape)} {t.dtype};".encode() + raw)
+        else:
+            out.append([name, hashlib.sha1(raw).hexdigest()])
+    assert RECORDER is None
+    RECORDER = rec
+    try:
+        fn(*a)
+    finally:
+        RECORDER = None
+    return {"in": h_in.hexdigest(), "out": out}
+
+
 def call(entry, *a):
     from ir2rgb_amd import _lib
     ref = next(x for x in a if isinstance(x, torch.Tensor))
+    for i, x in enumerate(a):
+        if isinstance(x, torch.Tensor):
+            hand("in", f"{entry} argument {i}", x)
     rc = getattr(_lib.lib(), entry)(*a, _lib.current_stream(ref))
     _lib.check(rc, entry)
 
@@ -61,7 +98,7 @@ def differs(g, want):
 def exact(name, got, ref_t):
     """got (device half / fp32) == the fp64 reference rounded to nearest even into got's format, bit for bit."""
     want = ref_t.to(got.dtype)
-    g = got.cpu()
+    g = hand("out", name, got).cpu()
     bad = differs(g, want)
     assert not bool(bad.any()), f"{name}: {int(bad.sum())} elements differ from the rounded fp64 result " \
                                 f"(first at {tuple(int(v) for v in bad.nonzero()[0])})"

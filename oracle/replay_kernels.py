@@ -13,7 +13,7 @@ import torch
 from oracle import bounds as B
 from oracle import conv_ref as R
 from oracle import window as WG
-from oracle.replay import DTYPES, gen
+from oracle.replay import DTYPES, gen, hand
 
 
 def _desc(d, dt):
@@ -228,13 +228,13 @@ def bn_case(dev, rec, shifted=False, mode=None):
     else:
         P, C = a[3], a[2]
         act = a[21] if entry == "ir2rgb_bn_finalize_apply" else 1
-    y = _bn_data(P, C, g, shifted)
+    y = hand("in", "y", _bn_data(P, C, g, shifted))
     yd = y.double().numpy()
     worst = {}
     for fmt, dtype, dt in DTYPES:
         def check(name, got, rb):
             ref, bnd = rb
-            got = got.double().cpu().numpy().reshape(ref.shape)
+            got = hand("out", f"{fmt} {name}", got).double().cpu().numpy().reshape(ref.shape)
             assert np.isfinite(got).all(), f"{fmt} {name}: non-finite"
             err = np.abs(got - ref)
             # (a sum whose every term is zero -- one pixel, a channel the activation switches off -- has the bound 0 and
@@ -259,7 +259,7 @@ def bn_case(dev, rec, shifted=False, mode=None):
             else:
                 ref = BR.finalize(rows.double().numpy(), float(P), gamma.double().numpy(), beta.double().numpy(),
                                   cb0, rm.double().numpy(), rv.double().numpy(), mom, eps, upd)
-            dv = [t.to(dev) for t in (rows, gamma, beta, cb, rm, rv)]
+            dv = [hand("in", f"{fmt} statistics operand {i}", t).to(dev) for i, t in enumerate((rows, gamma, beta, cb, rm, rv))]
             if not a[6]:
                 dv[3] = None
             outs = [torch.empty(C, **f32) for _ in range(4)]
@@ -273,7 +273,7 @@ def bn_case(dev, rec, shifted=False, mode=None):
                 _lib.check(rc, "bn_finalize_ex")
                 z = None
             else:
-                res = [R.draw((P, C), g) if a[17 + i] else None for i in range(2)]
+                res = [hand("in", f"{fmt} residual", R.draw((P, C), g)) if a[17 + i] else None for i in range(2)]
                 x = y.to(dev, dtype)
                 rdev = [r.to(dev, dtype) if r is not None else None for r in res]
                 z = torch.empty_like(x)
@@ -315,8 +315,8 @@ def bn_case(dev, rec, shifted=False, mode=None):
                 bn_bwd_check(dev, fmt, dtype, y, g, sc, sh, outs[2].double().cpu().numpy(),
                               outs[3].double().cpu().numpy(), 1, False, check)
         elif entry == "ir2rgb_bn_apply":
-            scale, shift = _vec(C, g, 0.5, 1.5), _vec(C, g)
-            res = [R.draw((P, C), g) if a[3 + i] else None for i in range(2)]
+            scale, shift = hand("in", f"{fmt} scale", _vec(C, g, 0.5, 1.5)), hand("in", f"{fmt} shift", _vec(C, g))
+            res = [hand("in", f"{fmt} residual", R.draw((P, C), g)) if a[3 + i] else None for i in range(2)]
             z = torch.empty(P, C, device=dev, dtype=dtype)
             rc = lib.ir2rgb_bn_apply(y.to(dev, dtype), scale.to(dev), shift.to(dev),
                                      *[r.to(dev, dtype) if r is not None else None for r in res], z, P, C, act, dt, stream)
@@ -348,6 +348,10 @@ def bn_bwd_check(dev, fmt, dtype, y, g, scale, shift, mean, invstd, act, acc, ch
     yd = y.double().numpy()
     gz = R.draw((P, C), g)
     gz[torch.from_numpy(~BR.sign_safe(yd, scale, shift))] = 0
+    hand("in", f"{fmt} gz", gz)
+    for name, v in (("scale", scale), ("shift", shift), ("mean", mean), ("invstd", invstd)):
+        if v is not None:
+            hand("in", f"{fmt} {name}", torch.from_numpy(np.asarray(v, dtype=np.float32)))
     base = (torch.randn(C, generator=g), torch.randn(C, generator=g)) if acc else None
     ref = BR.bwd(gz.double().numpy(), yd, scale, shift, mean, invstd, act, fmt,
                  None if base is None else (base[0].double().numpy(), base[1].double().numpy()), frozen=frozen)

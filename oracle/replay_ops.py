@@ -16,7 +16,7 @@ from oracle import bounds as B
 from oracle import conv_ref as R
 from oracle import flow_ops_ref as F
 from oracle import window_ops_ref as O
-from oracle.replay import DTYPES, assert_bound, bits, call, exact, np64, sentinel
+from oracle.replay import DTYPES, assert_bound, bits, call, exact, hand, np64, sentinel
 
 ARGS = {    # argument names of the header's prototypes, without the stream
     "ir2rgb_gather_f32": "src idx dst n",
@@ -122,7 +122,7 @@ def replay_xexpand_bwd(dev, rec, g, mode=None):
         call(rec["entry"], dxe.to(dev, dtype), din, N, Cin, H, W, Wout, KW, s, p, pm, dt)
         torch.cuda.synchronize()
         bnd = B.bound_sum(ref, S, "f32", int(cnt.max()))
-        out[fmt] = assert_bound(f"{fmt} xexpand_bwd", *B.check_bound(np64(din), ref, bnd), ref.shape)
+        out[fmt] = assert_bound(f"{fmt} xexpand_bwd", *B.check_bound(np64(hand("out", f"{fmt} din", din)), ref, bnd), ref.shape)
     return out
 
 
@@ -140,7 +140,7 @@ def replay_fold(dev, rec, g, mode=None):
         call(rec["entry"], dxpad.to(dev, dtype), dx, N, H, W, C, ph, pw, dt)
         torch.cuda.synchronize()
         bnd = B.bound_sum(ref, S, fmt, int(cnt.max()))
-        out[fmt] = assert_bound(f"{fmt} fold_reflect", *B.check_bound(np64(dx), ref, bnd), ref.shape)
+        out[fmt] = assert_bound(f"{fmt} fold_reflect", *B.check_bound(np64(hand("out", f"{fmt} dx", dx)), ref, bnd), ref.shape)
     return out
 
 
@@ -170,8 +170,8 @@ def replay_thin_grad(dev, rec, g, mode=None):
         exact(f"{fmt} g64 (channels < 8)", g64[..., :8], want)
         assert not bool(g64[..., 8:].ne(0).any()), f"{fmt}: g64 channels >= 8 are not zero"
         assert torch.equal(bits(runs[0]), bits(runs[1])), f"{fmt}: dbias differs between two runs"
-        out[fmt] = assert_bound(f"{fmt} dbias", *B.check_bound(np64(runs[0]), ref, B.bound_rw(ref, S, "f32", chain, 0)),
-                           ref.shape)
+        out[fmt] = assert_bound(f"{fmt} dbias", *B.check_bound(np64(hand("out", f"{fmt} dbias", runs[0])), ref,
+                                                                B.bound_rw(ref, S, "f32", chain, 0)), ref.shape)
     return out
 
 

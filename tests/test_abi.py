@@ -89,6 +89,20 @@ def test_fastcall_bindings_cover_the_prototypes_and_agree_with_ctypes(built_lib)
         fast.ir2rgb_bn_bwd(*args[:11], 1 << 40, 0, 1, None)
 
 
+def test_bn_bwd_refuses_a_partial_set_of_vectors(built_lib):
+    """ir2rgb_bn_bwd takes scale / shift / mean / invstd together (a BatchNorm stage) or not at all (a norm-less one): any
+    other set returns IR2RGB_EINVAL through both bindings before anything is launched -- the kernels read mean and invstd
+    wherever scale is given.  npix, C and dtype are valid; the pointers are never dereferenced (no GPU here)."""
+    import torch
+    lib = _lib.lib()
+    fast, handle = lib.fast_module, lib.ctypes_handle
+    p = torch.zeros(64).data_ptr()
+    full = (p, p, p, p, p, p, p, p, p, p, 100, 64, 0, 1, None)
+    for missing in ((4,), (2,), (2, 3, 5), (3,)):       # mean; scale; all but mean; shift
+        part = tuple(None if i in missing else v for i, v in enumerate(full))
+        assert fast.ir2rgb_bn_bwd(*part) == handle.ir2rgb_bn_bwd(*part) == -1, missing
+
+
 def test_query_returns_the_count_and_raises_under_the_entry_name(built_lib):
     """_lib.query: the raw entry's answer, and a ValueError naming the entry for a channel count ir2rgb_bn_bwd_blocks
     refuses up front (csrc/backward.hip: C < 64)."""
