@@ -474,6 +474,37 @@ int ir2rgb_loss_scale_update(void *scaler_state, const void *opt_states, int cou
                              int growth_interval, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Device loss log (loss_log.hip): one launch per training window records the window's loss scalars without a host
+ * round trip.  ring is fp32 [capacity][IR2RGB_LOSS_LOG_SLOTS]; state is an ir2rgb_loss_log_state, 8-byte aligned,
+ * zeroed by the caller before the first push.  Both are written by the kernel only.
+ *   srcs    : HOST array of `count` device addresses, each one fp32 value (4-byte aligned); they are copied into the
+ *             kernel's argument block, so the array is free again when the call returns
+ *   present : bit i set = slot i has a value this window; an entry of srcs whose bit is clear is not looked at
+ *   opt_states, n_opts : HOST array of the ir2rgb_adam_state addresses of the optimizers stepped this window with a
+ *             loss scaler (n_opts 0: no scaler).  If any of them holds found_inf the window was skipped
+ * The kernel writes row `state->count % capacity`: the value of every present slot, IR2RGB_LOSS_LOG_ABSENT in the
+ * others (a finite number no loss takes, so the ring holds a NaN only where a loss was one).  Unless the window was
+ * skipped, each present value is added to sum[slot] in double and n[slot] is incremented; a skipped window increments
+ * `skipped` instead.  `count` is incremented.  Values are passed through as they are, inf and NaN included.
+ * IR2RGB_EINVAL: NULL srcs / ring / state, count outside [0, 32], a bit of `present` at or above `count`, a NULL
+ * source whose bit is set, capacity <= 0, n_opts outside [0, 8], a NULL optimizer state; IR2RGB_EALIGN: a source or
+ * ring off a 4-byte boundary, state or an optimizer state off an 8-byte one.  Both before any launch.
+ * ------------------------------------------------------------------------------------------ */
+#define IR2RGB_LOSS_LOG_SLOTS 32
+#define IR2RGB_LOSS_LOG_OPTIMIZERS 8
+#define IR2RGB_LOSS_LOG_ABSENT (-3.402823466e+38f) /* -FLT_MAX */
+
+typedef struct ir2rgb_loss_log_state {
+    double sum[IR2RGB_LOSS_LOG_SLOTS];  /* per slot: sum of the values pushed since the caller last zeroed it */
+    long long n[IR2RGB_LOSS_LOG_SLOTS]; /* per slot: how many values that sum holds */
+    long long skipped;                  /* windows left out of the sums because their optimizer steps were skipped */
+    long long count;                    /* windows pushed so far; the caller's reset leaves it alone (ring position) */
+} ir2rgb_loss_log_state;
+
+int ir2rgb_loss_log_push(const void *const *srcs, unsigned present, int count, float *ring, int capacity, void *state,
+                         const void *const *opt_states, int n_opts, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Frame I/O of frame-by-frame inference (frame_io.hip): the 8-bit image boundary and the recurrence state
  * as device-resident histories.  A history is fp32 [T][C][H][W], oldest frame first; both entry points move
  * slots 1..T-1 down to 0..T-2 in place (same element index, same thread) and fill slot T-1.  Rows whose

@@ -7,7 +7,7 @@ first use and its absence is an error (there is no CPU fallback).
 __version__ = "0.1.0"
 
 __all__ = ["VideoTranslator", "VideoScore", "video_metrics", "ssim_reference", "FrameScaler", "img_params", "resample_coeffs",
-           "resize_reference"]
+           "resize_reference", "TrainingSchedule", "LossLog", "fit"]
 
 
 def __getattr__(name):
@@ -21,4 +21,13 @@ def __getattr__(name):
     if name in ("FrameScaler", "img_params", "resample_coeffs", "resize_reference"):
         from . import transform
         return getattr(transform, name)
+    if name == "TrainingSchedule":
+        from .schedule import TrainingSchedule
+        return TrainingSchedule
+    if name == "LossLog":
+        from .losslog import LossLog
+        return LossLog
+    if name == "fit":
+        from .training import fit
+        return fit
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

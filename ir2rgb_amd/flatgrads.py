@@ -49,7 +49,7 @@ class FlatGrads:
         # early chunks: [lo, hi) ranges of the sink region, each a list of parameter indices; a chunk is all-reduced from
         # the autograd hook of the parameter whose gradient completes it (all_reduce_async picks up what is left)
         self.chunks, self._fired, self._pending, self._issued, self._world = [], set(), [], [], world
-        self._direct_capable, self._sink_ids = self.direct, []
+        self._direct_capable, self._sink_ids, self._hooks = self.direct, [], []
         if self.direct:
             cur, lo = [], 0
             sink_ids = self._sink_ids = [i for i in order if is_sink[i]]
@@ -64,7 +64,7 @@ class FlatGrads:
             for i in sink_ids:
                 p = self.params[i]
                 autograd.GRAD_SINKS[p] = self.views[i]
-                p.register_post_accumulate_grad_hook(self._make_hook(i, chunk_of[i]))
+                self._hooks.append(p.register_post_accumulate_grad_hook(self._make_hook(i, chunk_of[i])))
         else:
             self.sink_end = 0
 
@@ -83,6 +83,18 @@ class FlatGrads:
             else:
                 autograd.GRAD_SINKS.pop(self.params[i], None)
         self._pending, self._issued = [], []
+
+    def close(self):
+        """Releases what this buffer holds on its parameters -- the in-place sinks, the post-accumulate hooks and the
+        .grad views -- so that another FlatGrads can take them over (Vid2VidTrainer.update_fixed_params).  Outstanding
+        all-reduces are waited for first."""
+        self.wait()
+        self.set_direct(False)
+        for h in self._hooks:
+            h.remove()
+        self._hooks, self._sink_ids, self._direct_capable, self.chunks = [], [], False, []
+        for p in self.params:
+            p.grad = None
 
     def _make_hook(self, i, c):
         def hook(p):

@@ -243,6 +243,16 @@ class LossScaler:
                                              device=self.device)
         return self._tables[key]
 
+    def forget_tables(self):
+        """Drops every registered table: for a trainer that replaces an optimizer (the tables are keyed by the optimizers'
+        identities, and hold the addresses of their device state)."""
+        self._tables = {}
+        self._last = []
+
+    def last_optimizers(self):
+        """The optimizers of the last ``update``: the ones stepped in the last window."""
+        return list(self._last)
+
     def update(self, optimizers):
         """Once per window, after the ``step(scaler)`` of every optimizer in ``optimizers``."""
         optimizers = list(optimizers)

@@ -52,6 +52,10 @@ DEFAULTS = dict(  # options/base_options.py, options/train_options.py (SURVEY se
     build_flow_net=True,  # False: trainer.flow_net is left None for the caller to set (tests plug a stand-in for FlowNet2)
     branch_streams_fine_scales=True,   # the finer spatial scales' generators run their two branches on two HIP streams, forward
                                        # and backward (the coarsest scale's kernels are what bench.py brackets: one stream)
+    niter_fix_global=0,  # != 0 with n_scales_spatial > 1: only the finest spatial scale trains until update_fixed_params() (generator.py:64-72)
+    TTUR=False,          # two time-scale update rule: G at lr / 2, D at lr * 2, both with betas (0, 0.9) (generator.py:74-79, discriminator.py:77-82)
+    lr_policy="reference",   # update_learning_rate: "reference" = what the reference does (G and D get the one decayed value, the temporal
+                             # discriminators keep theirs); "all" = every optimizer decays and keeps its TTUR factor
     discriminator_streams=True,        # the image discriminator's scales and the temporal discriminators each on their own HIP stream (forward and, through autograd, backward): independent networks of small layers that fill a fraction of the chip one at a time
 )
 
@@ -126,6 +130,8 @@ class Vid2VidTrainer:
         o = dict(DEFAULTS)
         o.update(overrides)
         check_loss_scale_option(o["loss_scale"], o["fused_adam"])     # (a ValueError before anything is built)
+        if o["lr_policy"] not in ("reference", "all"):
+            raise ValueError(f"lr_policy: \"reference\" or \"all\", got {o['lr_policy']!r}")
         self.opt, self.device, self.world = o, device, world_size
         tG = o["n_input_gen_frames"]
         self.n_scales, self.t_scales, self.tD = o["n_scales_spatial"], o["n_scales_temporal"], o["n_frames_D"]
@@ -164,6 +170,8 @@ class Vid2VidTrainer:
         if o["build_flow_net"]:
             self.flow_net = FlowNet(o["flownet_dtype"], use_graph=None).to(device)
         self._side_wgrad = None          # set per window in generate(): safe only when n_load == 1
+        self.schedule = self._batch_state = None    # attach_schedule()
+        self.old_lr = o["lr"]            # the rate without any TTUR factor (base_model.py:98-99, :105)
         self.last_outputs = None         # (fake_B, fake_B_raw, flow, weight) of the last train_window
         self.vgg_loss = None
         if not o["no_vgg"]:
@@ -171,27 +179,103 @@ class Vid2VidTrainer:
             self.vgg_loss = VGGLoss().to(device)
             self.vgg_loss.vgg.compute_dtype = o["compute_dtype"]
 
-        g_params = [p for g in self.netG for p in g.parameters()]  # niter_fix_global = 0: all scales train
-        # NOT fused=True: torch's fused Adam updates the parameters without bumping their version counters,
-        # and the packed MFMA weights (ir2rgb_amd.layers.packed_weight) are refreshed on a version change
-        adam = dict(lr=o["lr"], betas=(o["beta1"], 0.999), foreach=True)
-        # (generators: one use per parameter and pass when one frame is generated per window, see generate())
-        self.grads_G = FlatGrads(g_params, chunk_elems=o["allreduce_chunk_elems"], world=world_size, direct=o["max_frames_per_gpu"] == 1)
+        # finest-scale-only epochs (generator.py:64-72): the coarser generators get no gradient buffer and no moments
+        self.finetune_all = o["niter_fix_global"] == 0 or self.n_scales == 1
+        # TTUR (generator.py:74-79, discriminator.py:77-82); the temporal discriminators keep lr and (beta1, 0.999)
+        plain = (1.0, (o["beta1"], 0.999))
+        self._rule_G, self._rule_D = ((0.5, (0.0, 0.9)), (2.0, (0.0, 0.9))) if o["TTUR"] else (plain, plain)
+        self._rule_DT = plain
+        self.grads_G = self._make_grads_G()
         self.grads_D = FlatGrads(self.netD.parameters())
         self.grads_DT = [FlatGrads(d.parameters()) for d in self.netD_T]
-        if o["fused_adam"]:
-            make = lambda ps: FusedAdam(ps, lr=o["lr"], betas=(o["beta1"], 0.999))  # noqa: E731
-        else:
-            make = lambda ps: torch.optim.Adam(ps, **adam)  # noqa: E731
-        self.optimizer_G = make(self.grads_G.params)
-        self.optimizer_D = make(self.grads_D.params)
-        self.optimizer_D_T = [make(g.params) for g in self.grads_DT]
+        self.optimizer_G = self._make_optimizer(self.grads_G.params, o["lr"] * self._rule_G[0], self._rule_G[1])
+        self.optimizer_D = self._make_optimizer(self.grads_D.params, o["lr"] * self._rule_D[0], self._rule_D[1])
+        self.optimizer_D_T = [self._make_optimizer(g.params, o["lr"], self._rule_DT[1]) for g in self.grads_DT]
         self.loss_scaler = make_loss_scaler(o["loss_scale"], device)
+        self._register_scaler_tables()
+        self.repacker = layers.WeightRepacker(list(self.netG) + [self.netD] + list(self.netD_T)) if o["batched_repack"] else None
+        self.reset_sequence()
+
+    def _make_grads_G(self):
+        """The generator optimizer's gradient buffer: every scale, or the finest one alone while the coarser ones are fixed."""
+        o = self.opt
+        nets = self.netG if self.finetune_all else self.netG[-1:]
+        g_params = [p for g in nets for p in g.parameters()]
+        # (generators: one use per parameter and pass when one frame is generated per window, see generate())
+        return FlatGrads(g_params, chunk_elems=o["allreduce_chunk_elems"], world=self.world, direct=o["max_frames_per_gpu"] == 1)
+
+    def _make_optimizer(self, params, lr, betas):
+        if self.opt["fused_adam"]:
+            return FusedAdam(params, lr=lr, betas=betas)
+        # NOT fused=True: torch's fused Adam updates the parameters without bumping their version counters,
+        # and the packed MFMA weights (ir2rgb_amd.layers.packed_weight) are refreshed on a version change
+        return torch.optim.Adam(params, lr=lr, betas=betas, foreach=True)
+
+    def _register_scaler_tables(self):
         if self.loss_scaler is not None:        # the device tables of every window's optimizer set, ahead of the loop
             for n in range(self.t_scales + 1):
                 self.loss_scaler.register([self.optimizer_G, self.optimizer_D] + self.optimizer_D_T[:n])
-        self.repacker = layers.WeightRepacker(list(self.netG) + [self.netD] + list(self.netD_T)) if o["batched_repack"] else None
-        self.reset_sequence()
+
+    # ------------------------------------------------------------------ between epochs (ir2rgb_amd.schedule, ir2rgb_amd.training)
+    def update_fixed_params(self):
+        """Model.update_fixed_params (base_model.py:101-107): from here on every scale trains.  A new ``optimizer_G`` over
+        all scales with fresh moments and step count 0, as the reference builds it: at ``old_lr`` -- the initial rate or the
+        last decayed one -- with betas (beta1, 0.999), i.e. without TTUR's factor and betas.  ``lr_policy="all"`` keeps both.
+        The gradient buffer, the side-stream / in-place weight-gradient arrangement and the loss scaler's device tables
+        are rebuilt to match."""
+        if self.finetune_all:
+            return
+        o = self.opt
+        keep = o["lr_policy"] == "all"
+        lr = self.old_lr * (self._rule_G[0] if keep else 1.0)
+        betas = self._rule_G[1] if keep else (o["beta1"], 0.999)
+        self.grads_G.close()
+        self.finetune_all = True
+        self.grads_G = self._make_grads_G()
+        self.optimizer_G = self._make_optimizer(self.grads_G.params, lr, betas)
+        self._side_wgrad = None                 # generate() re-runs enable_side_wgrad / set_direct for the next window
+        if self.loss_scaler is not None:
+            self.loss_scaler.forget_tables()
+            self._register_scaler_tables()
+
+    def attach_schedule(self, schedule):
+        """The ``ir2rgb_amd.schedule.TrainingSchedule`` whose arithmetic ``update_learning_rate`` and ``update_training_batch``
+        apply (``ir2rgb_amd.training.fit`` attaches its own).  Its ``lr`` has to be the trainer's."""
+        if schedule.lr != self.opt["lr"]:
+            raise ValueError(f"schedule.lr {schedule.lr!r} differs from the trainer's lr {self.opt['lr']!r}")
+        self.schedule = schedule
+        self._batch_state = schedule.initial_training_batch()
+
+    def update_learning_rate(self, epoch):
+        """Model.update_learning_rate (base_model.py:94-99) as models.py:112-116 calls it for G and D: the schedule's
+        ``lr_after(epoch)`` assigned to ``param_groups[...]["lr"]``, which the optimizers read per step.
+        ``lr_policy="reference"``: exactly that -- optimizer_G and optimizer_D get the one value (a TTUR factor is gone from
+        then on) and the temporal discriminators' optimizers are never touched.  ``lr_policy="all"``: every optimizer gets
+        the value times its own factor.  -> the decayed value."""
+        lr = self.old_lr = self.schedule.lr_after(epoch)
+        if self.opt["lr_policy"] == "reference":
+            targets = [(self.optimizer_G, 1.0), (self.optimizer_D, 1.0)]
+        else:
+            targets = [(self.optimizer_G, self._rule_G[0]), (self.optimizer_D, self._rule_D[0])] + \
+                      [(d, self._rule_DT[0]) for d in self.optimizer_D_T]
+        for opt, factor in targets:
+            for group in opt.param_groups:
+                group["lr"] = lr * factor
+        return lr
+
+    def update_training_batch(self, ratio, resume=False):
+        """Model.update_training_batch (base_model.py:109-120), the arithmetic being the schedule's: the number of frames
+        the loss is backpropagated through becomes ``opt["n_frames_bp"]``; -> ``n_frames_load``, the frames per window the
+        slicer is to cut (``generate`` reads it off the window it is given).  ``resume``: the state an uninterrupted run
+        holds after the call for ``ratio``, from the initial one."""
+        if resume:
+            self._batch_state = self.schedule.initial_training_batch()
+            for r in range(1, ratio + 1):
+                self._batch_state = self.schedule.update_training_batch(*self._batch_state, r)
+        else:
+            self._batch_state = self.schedule.update_training_batch(*self._batch_state, ratio)
+        self.opt["n_frames_bp"] = self._batch_state[1]
+        return self._batch_state[0]
 
     def _flow_stream(self, t):
         """The side stream FlowNet2 runs on (None: same stream as everything else)."""
@@ -244,8 +328,13 @@ class Vid2VidTrainer:
                 prev = fake_pyr[si][:, t:t + tG - 1]
                 if t % self.opt["n_frames_bp"] == 0:
                     prev = prev.detach()
-                out = self.netG[s](A_in, prev.reshape(b, -1, h, w), None, feat, flow_feat, None,
-                                   self.opt["no_first_img"] and first)
+                # finest-scale-only epochs: the coarser scales' results enter the next scale detached (generator.py:166-172).
+                # They run in training mode (their BatchNorm running statistics advance) but without a tape: same kernels,
+                # same bits, no saved activations and no backward pass
+                fixed = s != ns - 1 and not self.finetune_all
+                with (torch.no_grad() if fixed else contextlib.nullcontext()):
+                    out = self.netG[s](A_in, prev.reshape(b, -1, h, w), None, feat, flow_feat, None,
+                                       self.opt["no_first_img"] and first)
                 fake_B, flow, weight, raw, feat, flow_feat, _ = out
                 fake_pyr[si] = torch.cat([fake_pyr[si], fake_B.unsqueeze(1)], 1)
                 if s == ns - 1:
