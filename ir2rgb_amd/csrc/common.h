@@ -24,7 +24,7 @@ template <class F> static inline void with_dtype(int dtype, F &&f) {
     else f(std::integral_constant<int, IR2RGB_F16>{});
 }
 
-// An integer environment switch (IR2RGB_CONV3X3P, IR2RGB_CONV3X3P_SPLIT, IR2RGB_CONV_DOT): unset = dflt.  Callers keep
+// An integer environment switch (IR2RGB_CONV3X3P, IR2RGB_CONV3X3P_SPLIT, IR2RGB_CONV_DOT, IR2RGB_CONV_HALF_TILE): unset = dflt.  Callers keep
 // the value in a function-local static: the environment is read once per process.
 static inline int env_switch(const char *name, int dflt) {
     const char *e = getenv(name);

@@ -2,7 +2,7 @@
 // ReflectionPad2d(3) + Conv2d(ngf, 3 | 2 | 1, 7); ir2rgb_amd.layers.head_stage evaluates the 7x7 kernel as a 1x7 pass
 // producing Cout*7 <= 24 row responses per pixel, then a 7-tap vertical gather with bias / tanh / sigmoid).
 //
-// On the general kernel (conv_igemm_kernel<.., 1, 7, THIN>) this layer re-staged the 128-channel activations once per
+// On the general kernel (conv_igemm_kernel<.., 1, 7, 32>) this layer re-staged the 128-channel activations once per
 // tap -- 7 x 134 MB through L2 -> LDS for 22 GFLOP -- and ran 195 us inside the forward where its tensors are 30 us of
 // HBM time.  Here:
 //   * a workgroup (4 waves, one per SIMD, the whole 512-register file each) walks row segments of 128 output pixels;

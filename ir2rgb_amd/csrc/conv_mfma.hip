@@ -20,7 +20,8 @@
 //
 // Workgroup = 512 threads = 8 waves (2 per SIMD), tile TC=128 couts x TP pixels, BK = 64.
 // Wave grid 2 (cout) x 4 (pixel); each wave owns 64 x TP/4 outputs as 4 x (TP/64)
-// v_mfma_f32_16x16x32 tiles.  Both operands are staged global -> LDS with 16-byte LDS-DMA
+// v_mfma_f32_16x16x32 tiles (layers of at most 64 couts: 32 x TP/4 per wave, no padding half tile -- MROWS
+// of conv_igemm_body).  Both operands are staged global -> LDS with 16-byte LDS-DMA
 // (global_load_lds_dwordx4; the per-lane SOURCE address carries the im2col gather -- reflection,
 // stride, sub-pixel phase -- and the XOR swizzle), three stages deep: loads for K-steps k+1
 // and k+2 are in flight while k is consumed; one raw s_barrier and one counted vmcnt per
@@ -78,17 +79,28 @@ template <int TP> struct ConvTile {
 
 // The kernel body; `block` is the workgroup's index inside its launch (or inside its class of a
 // multi-class launch) and `smem` the workgroup's LDS ring (ConvTile<TP>::LDS bytes, 1024-aligned).
-// THIN: at most 32 output channels (the 24-response 1x7 head pass, the 1-channel PatchGAN logits): only
-// the waves of the first 64-row half multiply, and only its first two 16-row fragments -- an eighth of
-// the MFMAs of the full 128-row tile; staging and epilogue are unchanged.
-template <int DT, int TP, int NTY, int NTX, bool THIN = false>
+// MROWS: the output-channel rows of the tile that exist; the wave grid is 2 (cout) x 4 (pixel) in every form.
+// 128: the full tile, a wave owns 64 couts x TP/4 pixels.
+// 64 (Cout <= 64): only weight rows 0..63 are staged and a wave owns 32 couts x TP/4 pixels -- all eight waves
+// multiply, where the full tile's four wc == 1 waves would multiply clamped duplicate rows that are never stored.
+// (A 1 x 8 grid of 64 couts x TP/8 pixels, with the wc == 1 waves idle at TP = 64, measured 8-20 % slower than
+// this: a wave then reads four weight fragments per pixel fragment.)
+// 32 (the 24-response 1x7 head pass, the 1-channel PatchGAN logits): rows 0..63 staged, only the wc == 0 waves
+// multiply, and only their first two 16-row fragments -- an eighth of the MFMAs of the full tile.
+// Every output accumulates its K-steps in the same order in all three, so y is bit-identical across MROWS; the
+// epilogue tile and the BatchNorm partial sums are 64 couts wide when MROWS <= 64.
+template <int DT, int TP, int NTY, int NTX, int MROWS = 128>
 __device__ __forceinline__ void
 conv_igemm_body(const uint16_t *__restrict__ X, const uint16_t *__restrict__ Wp, const float *__restrict__ bias,
                 uint16_t *__restrict__ Y, float *__restrict__ stats_partial, const ConvGeom &g, const int block,
                 unsigned char *const smem) {
     constexpr int TC = 128;
+    static_assert(MROWS == 128 || MROWS == 64 || MROWS == 32, "tile rows");
+    constexpr int CW = MROWS == 64 ? 32 : 64;  // couts between the two wave rows (wc)
+    constexpr int MI = MROWS == 128 ? 4 : 2;   // 16-row output-channel fragments a wave multiplies
     constexpr int NI = TP / 64;            // 16-pixel MFMA tiles per wave along pixels
-    constexpr int WROWS = THIN ? 1 : TC / 64;  // weight rows staged per thread per K-step (THIN: rows 0..63 only)
+    constexpr int OC = MROWS <= 64 ? 64 : TC;  // couts of the epilogue's tile
+    constexpr int WROWS = OC / 64;         // weight rows staged per thread per K-step (MROWS <= 64: rows 0..63 only)
     constexpr int PROWS = TP / 64;         // pixel rows staged per thread per K-step
     constexpr int LOADS = WROWS + PROWS;   // LDS-DMA instructions per thread per K-step
     constexpr int STAGE = (TC + TP) * 128; // bytes per stage
@@ -223,15 +235,16 @@ conv_igemm_body(const uint16_t *__restrict__ X, const uint16_t *__restrict__ Wp,
 
     // ---------------- per-wave compute roles ----------------
     const int wc = wave & 1, wp = wave >> 1;
+    const bool idle = MROWS == 32 && wc != 0;   // wave-uniform: rows 64..127 of the tile do not exist
     const int l15 = lane & 15, lq = lane >> 4;
     const int sw0 = (lq ^ (l15 >> 1)) << 4;  // byte offset of k-group lq      in a swizzled row
     const int sw1 = sw0 ^ 64;                // byte offset of k-group lq + 4
-    const int offA = (wc * 64 + l15) * 128;                  // + mi * 2048
+    const int offA = (wc * CW + l15) * 128;                  // + mi * 2048
     const int offB = TC * 128 + (wp * (TP / 4) + l15) * 128; // + ni * 2048
 
-    f32x4 acc[4][NI];
+    f32x4 acc[MI][NI];
 #pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
+    for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
         for (int ni = 0; ni < NI; ++ni) acc[mi][ni] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
@@ -252,11 +265,8 @@ conv_igemm_body(const uint16_t *__restrict__ X, const uint16_t *__restrict__ Wp,
         else                           asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();  // ... and for every wave; also: everyone is done reading stage ks-1
     };
-    constexpr int MI = THIN ? 2 : 4;       // 16-row output-channel fragments a wave multiplies
     auto compute = [&](int buf) {
-        if constexpr (THIN) {
-            if (wc != 0) return;           // wave-uniform: rows 64..127 of the tile do not exist
-        }
+        if (idle) return;
         const unsigned char *s = smem + buf * STAGE;
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk) {
@@ -319,10 +329,10 @@ conv_igemm_body(const uint16_t *__restrict__ X, const uint16_t *__restrict__ Wp,
     }
 
     // ---------------- epilogue: bias, activation, BN statistics, NHWC store ----------------
-    // acc[mi][ni][r]: cout = ct*TC + wc*64 + mi*16 + lq*4 + r ; pixel = pt*TP + wp*(TP/4) + ni*16 + l15
+    // acc[mi][ni][r]: cout = ct*TC + wc*CW + mi*16 + lq*4 + r ; pixel = pt*TP + wp*(TP/4) + ni*16 + l15
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // (this wave's last fragment reads have returned, see wait_stage)
     __builtin_amdgcn_s_barrier();  // all waves are past their last LDS read: smem is reusable
-    const int co_base = ct * TC + wc * 64 + lq * 4;
+    const int co_base = ct * TC + wc * CW + lq * 4;
     long opix[NI];
     bool oval[NI];
 #pragma unroll
@@ -336,14 +346,18 @@ conv_igemm_body(const uint16_t *__restrict__ X, const uint16_t *__restrict__ Wp,
         opix[ni] = ((long)n * g.Hout + (sy * g.s_out_y + g.off_y)) * g.Wout + (sx * g.s_out_x + g.off_x);
     }
     // Half outputs with Cout % 8 == 0 leave through LDS: each lane parks its 4-cout groups in a
-    // [TP pixels][128 couts] half tile (16-byte slot s of row r at s ^ (r & 15): conflict-free 8-byte
-    // writes), then the workgroup streams the tile out as 16-byte stores, 16 lanes per 256-byte pixel row
-    // -- full-line coalescing instead of 8-byte scattered stores.  `red` (BatchNorm partials) sits behind it.
+    // [TP pixels][OC couts] half tile (16-byte slot s of row r at s ^ (r & 15), in the 64-cout tile at
+    // s ^ ((r >> 1) & 7): conflict-free 8-byte writes), then the workgroup streams the tile out as 16-byte stores,
+    // OC/8 lanes per pixel row -- full-line coalescing instead of 8-byte scattered stores.  `red` (BatchNorm
+    // partials) sits behind it.
     const bool staged = !g.out_f32 && (g.Cout & 7) == 0 && (g.ldy & 7) == 0 && (g.co_off & 7) == 0;
-    unsigned char *otile = smem;                                   // TP * 256 B
-    float *red = reinterpret_cast<float *>(smem + TP * 256);       // [4 wp][TC][2]
+    constexpr int OROW = OC * 2, LPR = OC / 8;                     // bytes and 16-byte slots of a tile row
+    auto oslot = [](int prow, int s) { return (OC == 128 ? s ^ (prow & 15) : s ^ ((prow >> 1) & 7)) << 4; };
+    unsigned char *otile = smem;                                   // TP * OROW B
+    float *red = reinterpret_cast<float *>(smem + TP * OROW);      // [4 wp][OC][2]
+    if (!idle)
 #pragma unroll
-    for (int mi = 0; mi < 4; ++mi) {
+    for (int mi = 0; mi < MI; ++mi) {
         const int co = co_base + mi * 16;
         float bv[4];
 #pragma unroll
@@ -360,11 +374,11 @@ conv_igemm_body(const uint16_t *__restrict__ X, const uint16_t *__restrict__ Wp,
             }
             if (staged) {
                 const int prow = wp * (TP / 4) + ni * 16 + l15;      // pixel row in the tile
-                const int cl = wc * 64 + mi * 16 + lq * 4;           // cout in the tile (multiple of 4)
+                const int cl = wc * CW + mi * 16 + lq * 4;           // cout in the tile (multiple of 4)
                 uint2 pk;
                 pk.x = (uint32_t)H::cvt(v[0]) | ((uint32_t)H::cvt(v[1]) << 16);
                 pk.y = (uint32_t)H::cvt(v[2]) | ((uint32_t)H::cvt(v[3]) << 16);
-                *reinterpret_cast<uint2 *>(otile + prow * 256 + (((cl >> 3) ^ (prow & 15)) << 4) + (cl & 4) * 2) = pk;
+                *reinterpret_cast<uint2 *>(otile + prow * OROW + oslot(prow, cl >> 3) + (cl & 4) * 2) = pk;
             } else if (oval[ni] && g.out_f32) {
                 float *dst = reinterpret_cast<float *>(Y) + opix[ni] * g.ldy + g.co_off + co;
                 if (co + 3 < g.Cout && (g.Cout & 3) == 0) {
@@ -398,51 +412,51 @@ conv_igemm_body(const uint16_t *__restrict__ X, const uint16_t *__restrict__ Wp,
             if (l15 == 0) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    int cl = wc * 64 + mi * 16 + lq * 4 + r;  // cout within the tile
-                    red[(wp * TC + cl) * 2 + 0] = s1[r];
-                    red[(wp * TC + cl) * 2 + 1] = s2[r];
+                    int cl = wc * CW + mi * 16 + lq * 4 + r;  // cout within the tile
+                    red[(wp * OC + cl) * 2 + 0] = s1[r];
+                    red[(wp * OC + cl) * 2 + 1] = s2[r];
                 }
             }
         }
     }
     if (staged) {
         __syncthreads();
-        // 512 threads: 16 lanes per pixel row, 32 rows per pass
-        const int c16 = tid & 15;
+        // 512 threads: LPR lanes per pixel row, 512 / LPR rows per pass
+        const int c16 = tid & (LPR - 1);
         const bool cok = ct * TC + c16 * 8 < g.Cout;   // Cout % 8 == 0: a 16-byte chunk is all-in or all-out
 #pragma unroll
-        for (int pass = 0; pass < TP / 32; ++pass) {
-            const int prow = pass * 32 + (tid >> 4);
+        for (int pass = 0; pass < TP * LPR / 512; ++pass) {
+            const int prow = pass * (512 / LPR) + tid / LPR;
             unsigned p = p0 + prow;
             if (p < plim && cok) {
                 unsigned n, rem;
                 pix_decode(p, n, rem);
                 unsigned sy = fdiv(rem, g.div_w), sx = rem - sy * g.Wsub;
                 long op = ((long)n * g.Hout + (sy * g.s_out_y + g.off_y)) * g.Wout + (sx * g.s_out_x + g.off_x);
-                const uint4 v = *reinterpret_cast<const uint4 *>(otile + prow * 256 + ((c16 ^ (prow & 15)) << 4));
+                const uint4 v = *reinterpret_cast<const uint4 *>(otile + prow * OROW + oslot(prow, c16));
                 *reinterpret_cast<uint4 *>(Y + op * g.ldy + g.co_off + ct * TC + c16 * 8) = v;
             }
         }
     }
     if (stats_partial != nullptr) {
         __syncthreads();
-        if (tid < TC * 2) {
+        if (tid < OC * 2) {
             const int cl = tid >> 1, which = tid & 1, co = ct * TC + cl;
             if (co < g.Cout) {
-                float t = red[(0 * TC + cl) * 2 + which] + red[(1 * TC + cl) * 2 + which] +
-                          red[(2 * TC + cl) * 2 + which] + red[(3 * TC + cl) * 2 + which];
+                float t = red[(0 * OC + cl) * 2 + which] + red[(1 * OC + cl) * 2 + which] +
+                          red[(2 * OC + cl) * 2 + which] + red[(3 * OC + cl) * 2 + which];
                 stats_partial[((long)(g.stats_row0 + pt) * 2 + which) * g.Cout + co] = t;
             }
         }
     }
 }
 
-template <int DT, int TP, int NTY, int NTX, bool THIN = false>
+template <int DT, int TP, int NTY, int NTX, int MROWS = 128>
 __global__ void __launch_bounds__(512, (TP == 256 ? 2 : 4))
 conv_igemm_kernel(const uint16_t *__restrict__ X, const uint16_t *__restrict__ Wp, const float *__restrict__ bias,
                   uint16_t *__restrict__ Y, float *__restrict__ stats_partial, const ConvGeom g) {
     __shared__ __attribute__((aligned(1024))) unsigned char smem[ConvTile<TP>::LDS];
-    conv_igemm_body<DT, TP, NTY, NTX, THIN>(X, Wp, bias, Y, stats_partial, g, (int)blockIdx.x, smem);
+    conv_igemm_body<DT, TP, NTY, NTX, MROWS>(X, Wp, bias, Y, stats_partial, g, (int)blockIdx.x, smem);
 }
 
 // Dot-product convolution for ONE fp32 output channel (the PatchGAN logit layers, 512 -> 1, 4x4, zero padding;
@@ -530,7 +544,7 @@ struct ConvClasses {
     int n;
 };
 
-template <int DT, int TP>
+template <int DT, int TP, int MROWS>
 __global__ void __launch_bounds__(512, (TP == 256 ? 2 : 4))
 conv_igemm_classes_kernel(const uint16_t *__restrict__ X, const uint16_t *__restrict__ Wp,
                           const float *__restrict__ bias, uint16_t *__restrict__ Y,
@@ -542,11 +556,11 @@ conv_igemm_classes_kernel(const uint16_t *__restrict__ X, const uint16_t *__rest
     const uint16_t *wp = Wp + cs.w_off[c];
     const int b = (int)blockIdx.x - cs.first[c];
     const int nty = g.ntaps / g.ntx;
-    if (nty == 2 && g.ntx == 2)      conv_igemm_body<DT, TP, 2, 2>(X, wp, bias, Y, stats_partial, g, b, smem);
-    else if (nty == 2 && g.ntx == 1) conv_igemm_body<DT, TP, 2, 1>(X, wp, bias, Y, stats_partial, g, b, smem);
-    else if (nty == 1 && g.ntx == 2) conv_igemm_body<DT, TP, 1, 2>(X, wp, bias, Y, stats_partial, g, b, smem);
-    else if (nty == 1 && g.ntx == 1) conv_igemm_body<DT, TP, 1, 1>(X, wp, bias, Y, stats_partial, g, b, smem);
-    else                             conv_igemm_body<DT, TP, 0, 0>(X, wp, bias, Y, stats_partial, g, b, smem);
+    if (nty == 2 && g.ntx == 2)      conv_igemm_body<DT, TP, 2, 2, MROWS>(X, wp, bias, Y, stats_partial, g, b, smem);
+    else if (nty == 2 && g.ntx == 1) conv_igemm_body<DT, TP, 2, 1, MROWS>(X, wp, bias, Y, stats_partial, g, b, smem);
+    else if (nty == 1 && g.ntx == 2) conv_igemm_body<DT, TP, 1, 2, MROWS>(X, wp, bias, Y, stats_partial, g, b, smem);
+    else if (nty == 1 && g.ntx == 1) conv_igemm_body<DT, TP, 1, 1, MROWS>(X, wp, bias, Y, stats_partial, g, b, smem);
+    else                             conv_igemm_body<DT, TP, 0, 0, MROWS>(X, wp, bias, Y, stats_partial, g, b, smem);
 }
 
 // ----------------------------------------------------------------------------------------
@@ -1085,24 +1099,38 @@ template <class F> static void with_tile(int tp, F &&f) {
     }
 }
 
-template <int NTY, int NTX, bool THIN = false> struct Taps {};
+template <int NTY, int NTX> struct Taps {};
+
+// The rows of the tile that a layer of Cout channels gets (conv_igemm_body's MROWS).  IR2RGB_CONV_HALF_TILE=0 gives layers
+// of 33..64 channels, and every layer of up to 64 on the sub-pixel classes, the full 128-row tile again (A/B runs; y is
+// bit-identical either way).  Launch-time only: no host query depends on it.
+static int tile_rows(int Cout, bool thin_ok) {
+    static const int half = env_switch("IR2RGB_CONV_HALF_TILE", 1);
+    return Cout <= 32 && thin_ok ? 32 : Cout <= 64 && half != 0 ? 64 : 128;
+}
 
 static void launch_conv(const ClassPlan &c, int dtype, const uint16_t *x, const uint16_t *wp, const float *bias, uint16_t *y,
                         float *stats, hipStream_t s) {
     const ConvGeom &g = c.geom;
     const unsigned grid = (unsigned)(c.npt * ((g.Cout + 127) / 128));
     const int nty = g.ntaps / g.ntx;
-    const bool thin = g.Cout <= 32;
-    auto launch = [&]<int NTY, int NTX, bool THIN>(Taps<NTY, NTX, THIN>) {
+    // the 32-row form exists for the two tap grids of the thin layers (1x7 head pass, 4x4 PatchGAN logits)
+    const int mrows = tile_rows(g.Cout, (nty == 4 && g.ntx == 4) || (nty == 1 && g.ntx == 7));
+    auto launch = [&]<int NTY, int NTX>(Taps<NTY, NTX>) {
         with_dtype(dtype, [&](auto dt) {
             with_tile(c.tp, [&](auto tp) {
-                conv_igemm_kernel<dt.value, tp.value, NTY, NTX, THIN><<<grid, 512, 0, s>>>(x, wp, bias, y, stats, g);
+                auto go = [&](auto mr) {
+                    conv_igemm_kernel<dt.value, tp.value, NTY, NTX, mr.value><<<grid, 512, 0, s>>>(x, wp, bias, y, stats, g);
+                };
+                if constexpr ((NTY == 4 && NTX == 4) || (NTY == 1 && NTX == 7)) {
+                    if (mrows == 32) return go(std::integral_constant<int, 32>{});
+                }
+                if (mrows == 64) go(std::integral_constant<int, 64>{});
+                else             go(std::integral_constant<int, 128>{});
             });
         });
     };
-    if (thin && nty == 4 && g.ntx == 4)      launch(Taps<4, 4, true>{});
-    else if (thin && nty == 1 && g.ntx == 7) launch(Taps<1, 7, true>{});
-    else if (nty == 3 && g.ntx == 3) launch(Taps<3, 3>{});
+    if (nty == 3 && g.ntx == 3)      launch(Taps<3, 3>{});
     else if (nty == 4 && g.ntx == 4) launch(Taps<4, 4>{});
     else if (nty == 7 && g.ntx == 1) launch(Taps<7, 1>{});
     else if (nty == 1 && g.ntx == 7) launch(Taps<1, 7>{});
@@ -1136,7 +1164,10 @@ static void launch_classes(const ClassPlan *plans, int n, int dtype, const uint1
     cs.n = n;
     with_dtype(dtype, [&](auto dt) {
         with_tile(plans[0].tp, [&](auto tp) {
-            conv_igemm_classes_kernel<dt.value, tp.value><<<first, 512, 0, s>>>(x, wp, bias, y, stats, cs);
+            if (tile_rows(plans[0].geom.Cout, false) == 64)
+                conv_igemm_classes_kernel<dt.value, tp.value, 64><<<first, 512, 0, s>>>(x, wp, bias, y, stats, cs);
+            else
+                conv_igemm_classes_kernel<dt.value, tp.value, 128><<<first, 512, 0, s>>>(x, wp, bias, y, stats, cs);
         });
     });
 }
