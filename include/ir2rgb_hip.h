@@ -474,6 +474,37 @@ int ir2rgb_loss_scale_update(void *scaler_state, const void *opt_states, int cou
                              int growth_interval, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Exponential moving average of the generator's parameters (ema.hip): e <- e + alpha * (p - e) for every tensor
+ * of a table, one streaming launch per window after the generator's optimizer step.  The three operations are
+ * rounded one by one in fp32 (no fused multiply-add), so p == e leaves e unchanged bit for bit; inf and NaN
+ * propagate as IEEE has them.
+ *   table  : device array of { const float *p; float *e; long n; } (24 bytes each); p is only read
+ *   blocks : device array of int pairs (tensor index, chunk index), as for ir2rgb_adam_step, with the same
+ *            chunk size ir2rgb_adam_chunk_elems()
+ *   ema_state : ir2rgb_ema_state, 4-byte aligned, zeroed (or seeded) by the caller, written by the kernels only
+ *   opt_state : the generator optimizer's ir2rgb_adam_state (8-byte aligned) or NULL.  When it is given and its
+ *            found_inf is set, the window's step was skipped: e and `updates` stay as they are and `skipped` is
+ *            incremented.  NULL: every call updates.  The host never reads the decision.
+ *   beta, warmup : for the n-th update taken (n = `updates` after its increment) the decay is
+ *            beta_n = min(beta, (1 + n) / (10 + n)) while warmup != 0 and n < 2^20, else beta -- the quotient one
+ *            correctly rounded fp32 division of the two integers -- and alpha = 1 - beta_n, one rounded fp32
+ *            subtraction, evaluated on the device.
+ * IR2RGB_EINVAL: NULL table / blocks / ema_state, nblocks < 0, beta outside [0, 1); IR2RGB_EALIGN: ema_state off
+ * a 4-byte boundary, opt_state off an 8-byte one.  Both before any launch.  nblocks 0: IR2RGB_OK, nothing is
+ * launched and the state is not touched.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct ir2rgb_ema_state {
+    int updates;         /* averages taken so far */
+    int skipped;         /* windows left out because the optimizer's step was skipped */
+    float alpha;         /* 1 - beta_n of the last update taken */
+    int reserved;
+} ir2rgb_ema_state;
+
+long ir2rgb_ema_state_bytes(void);
+int ir2rgb_ema_step(const void *table, const void *blocks, int nblocks, void *ema_state, const void *opt_state,
+                    float beta, int warmup, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Device loss log (loss_log.hip): one launch per training window records the window's loss scalars without a host
  * round trip.  ring is fp32 [capacity][IR2RGB_LOSS_LOG_SLOTS]; state is an ir2rgb_loss_log_state, 8-byte aligned,
  * zeroed by the caller before the first push.  Both are written by the kernel only.

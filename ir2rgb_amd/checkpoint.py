@@ -5,6 +5,9 @@
                                                   discriminator.py:250-253)
     {label}_loss_scaler.pth                       the loss scaler's state when the trainer has one (no reference
                                                   counterpart: apex keeps its scale in the amp state)
+    {label}_net_G{s}_ema.pth, {label}_ema.pth     a trainer with ``ema_decay``: the averaged generators, plain
+                                                  ``state_dict`` with the keys of {label}_net_G{s}.pth (they load into the
+                                                  reference's generator as well), and ParamEMA.state_dict()
     iter.txt                                      "epoch,epoch_iter" written with np.savetxt(fmt='%d')
                                                   (models/models.py:62-68, :96-110)
 
@@ -88,6 +91,10 @@ def save_trainer(trainer, label, save_dir, epoch=None, epoch_iter=None):
     scaler = getattr(trainer, "loss_scaler", None)
     if scaler is not None:          # (scale, growth tracker, skipped windows: ir2rgb_amd.optim.LossScaler.state_dict)
         torch.save(scaler.state_dict(), os.path.join(save_dir, f"{label}_loss_scaler.pth"))
+    if getattr(trainer, "ema", None) is not None:
+        for s, g in enumerate(trainer.ema_generators()):
+            save_network(g, f"G{s}_ema", label, save_dir)
+        torch.save(trainer.ema.state_dict(), os.path.join(save_dir, f"{label}_ema.pth"))
     if epoch is not None:
         write_iter(save_dir, epoch, epoch_iter or 0)
 
@@ -107,4 +114,35 @@ def load_trainer(trainer, label, save_dir, log=print):
         scaler.load_state_dict(torch.load(path, map_location="cpu", weights_only=True))
     elif scaler is not None:
         log(f"{path} not exists yet!")
+    if getattr(trainer, "ema", None) is not None:
+        _load_ema(trainer, label, save_dir, log)
     return read_iter(save_dir)
+
+
+def _load_ema(trainer, label, save_dir, log):
+    """The averaged generators and the average's counts, after the networks are loaded.  Unless every ``_ema`` file is
+    there and loads in full, the average restarts from the parameters just loaded (``ParamEMA.reseed``): an average of
+    other weights, or of a part of them, must not be carried on."""
+    paths = [network_path(save_dir, f"G{s}_ema", label) for s in range(len(trainer.netG))]
+    paths.append(os.path.join(save_dir, f"{label}_ema.pth"))
+    missing = [p for p in paths if not os.path.isfile(p)]
+    for p in missing:
+        log(f"{p} not exists yet!")
+    found = not missing
+    if found:
+        for s, g in enumerate(trainer.ema_generators()):
+            sd = torch.load(paths[s], map_location="cpu", weights_only=True)
+            names = {k for k, _ in g.named_parameters()}
+            try:                            # (the buffers are the live generators': ema_generators() copies them per call)
+                found = names <= set(sd)
+                g.load_state_dict({k: v for k, v in sd.items() if k in names}, strict=False)
+            except RuntimeError:
+                found = False
+            if not found:
+                log(f"{paths[s]} does not fit generator {s}; the average restarts from the loaded parameters")
+                break
+    if found:
+        # (the modules' load_state_dict copied into the shadow views in place: their version counters have moved)
+        trainer.ema.load_state_dict(torch.load(paths[-1], map_location="cpu", weights_only=True))
+    else:
+        trainer.ema.reseed()

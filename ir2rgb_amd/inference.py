@@ -25,6 +25,8 @@ batch statistics.  What this module adds is what a frame loop needs around that 
 
 There is no CPU path: a CPU device raises, as everywhere in this package.
 """
+import os
+
 import torch
 
 from . import _lib, autograd, checkpoint, layers, networks
@@ -126,7 +128,9 @@ class VideoTranslator:
     ``**opt`` takes the option names and defaults of ``Vid2VidTrainer`` (``n_scales_spatial``, ``first_layer_gen_filters``
     (alias ``ngf``), ``n_input_gen_frames``, ``no_flow``, ``compute_dtype`` ...).  ``netG``: a trainer's generator list, used
     as it is (shared parameters, nothing copied); otherwise the generators are built and ``checkpoint_dir`` loads
-    ``{which_epoch}_net_G{s}.pth`` through ir2rgb_amd.checkpoint.
+    ``{which_epoch}_net_G{s}.pth`` through ir2rgb_amd.checkpoint.  ``weights="ema"`` loads ``{which_epoch}_net_G{s}_ema.pth``
+    instead -- the moving average of the generators' parameters a trainer with ``ema_decay`` saves (a missing file raises
+    ``FileNotFoundError``); with ``netG`` pass ``trainer.ema_generators()``, and ``weights`` only names what they are.
 
     ``first_frame``: ``"zeros"`` is the reference's ``no_first_img`` (the model also generates the first frame from a zero
     history, raw image only); ``"real"`` is ``use_real_img`` (the first tG-1 RGB frames are given: ``real_rgb_u8`` of
@@ -149,8 +153,11 @@ class VideoTranslator:
     the static buffers the graph works on)."""
 
     def __init__(self, device, height, width, netG=None, checkpoint_dir=None, which_epoch="latest", first_frame="zeros",
-                 norm_stats="batch", use_graph=True, source_size=None, scaler=None, scale_opt=None, scale_rng=None, **opt):
+                 norm_stats="batch", use_graph=True, source_size=None, scaler=None, scale_opt=None, scale_rng=None,
+                 weights="raw", **opt):
         device = torch.device(device)
+        if weights not in ("raw", "ema"):
+            raise ValueError(f"weights: 'raw' (the last step's parameters) or 'ema' (their moving average), got {weights!r}")
         if device.type != "cuda":
             raise ValueError("VideoTranslator runs on an AMD GPU only (ir2rgb_amd has no CPU fallback)")
         o = _defaults()
@@ -180,7 +187,11 @@ class VideoTranslator:
             netG = self._build_generators(o)
             if checkpoint_dir is not None:
                 for s, g in enumerate(netG):
-                    checkpoint.load_network(g, f"G{s}", which_epoch, checkpoint_dir)
+                    label = f"G{s}_ema" if weights == "ema" else f"G{s}"
+                    if weights == "ema" and not os.path.isfile(checkpoint.network_path(checkpoint_dir, label, which_epoch)):
+                        raise FileNotFoundError(f"weights='ema': {checkpoint.network_path(checkpoint_dir, label, which_epoch)} is "
+                                                "missing (written by save_trainer for a trainer with ema_decay)")
+                    checkpoint.load_network(g, label, which_epoch, checkpoint_dir)
         elif checkpoint_dir is not None:
             raise ValueError("VideoTranslator: give netG or checkpoint_dir, not both")
         if len(netG) != self.n_scales:

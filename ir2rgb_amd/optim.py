@@ -9,6 +9,9 @@ every step (one small asynchronous copy from pinned memory).
 f16 training scales its losses (``LossScaler``; libir2rgb_hip.so: loss_scale.hip): ``FusedAdam.step(scaler)`` then checks
 the scaled gradient on the device, steps on ``g * inv_scale`` or skips, and ``LossScaler.update`` applies
 ``torch._amp_update_scale_``'s rule -- the decision, the step count and the scale never visit the host.
+
+``ParamEMA`` (libir2rgb_hip.so: ema.hip) keeps an exponential moving average of a parameter list in one more launch per
+step; after a loss-scaled step it reads that step's skip decision from the optimizer's device state.
 """
 import ctypes
 import math
@@ -61,6 +64,7 @@ class FusedAdam:
         # loss-scaled steps only (scaled_state): ir2rgb_adam_state on the device and the check kernel's partial rows
         self._state = self._partial = None
         self._on_device = False          # the step count lives in _state[0] (loss-scaled steps) / in step_count
+        self.last_step_scaled = False    # the last step() took a scaler: its skip decision is in scaled_state() (ParamEMA.update)
 
     @property
     def lr(self):
@@ -177,6 +181,7 @@ class FusedAdam:
         (ir2rgb_adam_step_scaled); the host learns neither."""
         self._refresh_table()
         nblocks = self._blocks.shape[0]
+        self.last_step_scaled = scaler is not None
         if scaler is None:
             if self._on_device:              # loss-scaled steps came before: their count moves back to the host
                 self._read_step_count()
@@ -324,8 +329,151 @@ def make_loss_scaler(value, device):
     return LossScaler(device, init_scale=float(value), growth_interval=0)
 
 
+EMA_WARMUP_END = 1 << 20          # csrc/ema.hip: from this update on the decay is beta itself
+
+
+def check_ema_option(value):
+    """Validates the trainer's ``ema_decay`` option -- None (no average) or a number in [0, 1) -- without touching a
+    device.  -> the decay as the fp32 number the kernel receives, or None."""
+    if value is None:
+        return None
+    if isinstance(value, bool) or not isinstance(value, (int, float)) or not 0.0 <= float(np.float32(value)) < 1.0:
+        raise ValueError(f"ema_decay: None or a number in [0, 1) (as fp32), got {value!r}")
+    return float(np.float32(value))
+
+
+class ParamEMA:
+    """Exponential moving average of a parameter list as ONE launch per update (libir2rgb_hip.so: ema.hip):
+    ``e <- e + alpha * (p - e)`` with ``alpha = 1 - beta_n`` and ``beta_n = min(beta, (1 + n) / (10 + n))`` for the n-th
+    update while ``warmup`` is on.  The averages live in one flat fp32 shadow buffer (each tensor at an offset that is a
+    multiple of 4 elements: 16-byte loads for every row), seeded as a bit copy of the parameters.  The count of updates
+    and the coefficient live on the device; ``update(optimizer)`` after a loss-scaled ``FusedAdam.step(scaler)`` leaves
+    the average alone when that step was skipped -- decided on the device from the optimizer's state.  ``update`` never
+    synchronises; ``stats`` / ``state_dict`` / ``load_state_dict`` do."""
+
+    def __init__(self, params, beta, warmup=True):
+        self.params = list(params)
+        if not self.params:
+            raise ValueError("ParamEMA: no parameters")
+        self.beta = check_ema_option(beta)
+        if self.beta is None:
+            raise ValueError("ParamEMA: beta is a number in [0, 1)")
+        self.warmup = bool(warmup)
+        dev = self.params[0].device
+        if dev.type != "cuda":
+            raise ValueError("ParamEMA: GPU parameters only (no CPU fallback; ema_reference restates the arithmetic)")
+        for p in self.params:
+            if p.dtype != torch.float32 or not p.is_contiguous() or p.device != dev:
+                raise ValueError("ParamEMA: contiguous fp32 parameters on one device")
+        self.device = dev
+        lib = _lib.lib()
+        chunk = lib.ir2rgb_adam_chunk_elems()
+        self._offsets, off = [], 0
+        for p in self.params:
+            self._offsets.append(off)
+            off += (p.numel() + 3) // 4 * 4
+        self.buf = torch.zeros(max(off, 4), dtype=torch.float32, device=dev)
+        rows = np.zeros((len(self.params), 3), dtype=np.int64)
+        blocks = []
+        for i, (p, o) in enumerate(zip(self.params, self._offsets)):
+            k = p.numel()
+            rows[i] = (p.data_ptr(), self.buf.data_ptr() + 4 * o, k)
+            blocks += [(i, c) for c in range((k + chunk - 1) // chunk)]
+        self._rows_dev = torch.from_numpy(rows).to(dev)
+        self._blocks = torch.tensor(blocks, dtype=torch.int32, device=dev).reshape(-1, 2)
+        self._ptrs = [p.data_ptr() for p in self.params]
+        self._views = [self.buf[o:o + p.numel()].view_as(p) for p, o in zip(self.params, self._offsets)]
+        nbytes = _lib.query("ir2rgb_ema_state_bytes")
+        assert ctypes.sizeof(_lib.EmaState) == nbytes
+        self.state = torch.zeros(nbytes // 4, dtype=torch.int32, device=dev)
+        self.reseed()
+
+    def shadow(self, i):
+        """The average of parameter i: a view of the shadow buffer in the parameter's shape."""
+        return self._views[i]
+
+    def _write(self, updates, skipped, alpha=0.0):
+        st = _lib.EmaState(updates=int(updates), skipped=int(skipped), alpha=float(alpha))
+        self.state.copy_(torch.frombuffer(bytearray(bytes(st)), dtype=torch.int32))
+
+    def _read(self):
+        return _lib.EmaState.from_buffer_copy(self.state.cpu().numpy().tobytes())
+
+    def _touched(self):
+        # the shadow changed behind autograd's back: caches keyed on the version counter (the packed MFMA weights of
+        # modules whose parameters alias the shadow, Vid2VidTrainer.ema_generators) are refreshed on their next use
+        torch.autograd.graph.increment_version(self._views)
+        if SC.ENABLED:
+            for v in self._views:
+                SC.produced(v, "fp32 parameter average (EMA)")
+
+    @torch.no_grad()
+    def reseed(self):
+        """The average becomes a bit copy of the current parameters and ``updates`` 0 (``skipped`` is kept)."""
+        skipped = self._read().skipped
+        torch._foreach_copy_(self._views, [p.detach() for p in self.params])
+        self._write(0, skipped)
+        self._touched()
+
+    @torch.no_grad()
+    def update(self, optimizer=None):
+        """One update, on the current stream.  ``optimizer``: the ``FusedAdam`` that has just stepped these parameters; if
+        that step was loss-scaled, its device state tells the kernel whether the step was taken (a skipped step skips the
+        average and counts in ``skipped``).  Anything else: the average is always taken."""
+        for p, ptr in zip(self.params, self._ptrs):
+            if p.data_ptr() != ptr:
+                raise RuntimeError("ParamEMA.update: parameter storage moved since construction")
+        opt_state = optimizer.scaled_state() if getattr(optimizer, "last_step_scaled", False) else None
+        if SC.ENABLED:
+            for p in self.params:
+                SC.consumed(p, "fp32 parameter (Adam step)")
+        _lib.launch("ir2rgb_ema_step", self.buf, self._rows_dev, self._blocks, self._blocks.shape[0], self.state, opt_state,
+                    self.beta, int(self.warmup))
+        self._touched()
+
+    def stats(self):
+        """{updates, skipped, alpha}: averages taken, windows skipped, the coefficient of the last one taken (synchronises)."""
+        st = self._read()
+        return {"updates": st.updates, "skipped": st.skipped, "alpha": st.alpha}
+
+    def state_dict(self):
+        """The counts and the settings they were taken under; the averages themselves are saved as networks
+        (ir2rgb_amd.checkpoint)."""
+        st = self._read()
+        return {"updates": st.updates, "skipped": st.skipped, "beta": self.beta, "warmup": self.warmup}
+
+    def load_state_dict(self, sd):
+        """Restores the counts (the warm-up continues where it was).  ``beta`` and ``warmup`` stay this instance's."""
+        updates, skipped = int(sd["updates"]), int(sd.get("skipped", 0))
+        if updates < 0 or skipped < 0:
+            raise ValueError("ParamEMA.load_state_dict: negative counts")
+        self._write(updates, skipped, self._read().alpha)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
-# plain-torch restatements, usable on a CPU (what the kernels are tested against; never on the training path)
+# plain torch / numpy restatements, usable on a CPU (what the kernels are tested against; never on the training path)
+def ema_beta(n, beta, warmup=True):
+    """beta_n of the n-th update (n >= 1) as ema_prepare_kernel evaluates it, in numpy float32."""
+    f = np.float32
+    if warmup and n < EMA_WARMUP_END:
+        return min(f(beta), f(1 + n) / f(10 + n))
+    return f(beta)
+
+
+def ema_reference(e, p, n, beta, warmup=True):
+    """ema_kernel's arithmetic in numpy float32, operation by operation: the n-th update (n >= 1) of the average ``e``
+    towards ``p`` -> the new average.  ``alpha = 1 - beta_n``, ``d = p - e``, ``t = alpha * d``, ``e + t``, each rounded
+    to fp32; inf and NaN propagate."""
+    f = np.float32
+    e, p = np.asarray(e, dtype=f), np.asarray(p, dtype=f)
+    with np.errstate(all="ignore"):
+        alpha = f(f(1.0) - ema_beta(n, beta, warmup))
+        d = (p - e).astype(f)
+        t = (alpha * d).astype(f)
+        return (e + t).astype(f)
+
+
+
 def loss_scale_update_reference(scale, growth_tracker, found_inf, growth_factor, backoff_factor, growth_interval):
     """loss_scale_update_kernel's rule, in place on a 1-element fp32 ``scale`` and int32 ``growth_tracker``;
     ``found_inf``: any non-zero element means an optimizer skipped.  For ``growth_interval > 0`` this is

@@ -29,7 +29,7 @@ from .flownet import FlowNet
 from .frames import FrameHistory
 from .losses import _SplitGroupsFn, drop_grad_dsts, fused_losses, split_groups  # noqa: F401  (re-exported)
 from .networks import SLOT_D_TEMPORAL, SLOT_FLOWNET, _Branch, side_stream
-from .optim import FusedAdam, LossScaler, check_loss_scale_option, make_loss_scaler  # noqa: F401
+from .optim import FusedAdam, LossScaler, ParamEMA, check_ema_option, check_loss_scale_option, make_loss_scaler  # noqa: F401
 
 DEFAULTS = dict(  # options/base_options.py, options/train_options.py
     input_nc=3, output_nc=3, n_input_gen_frames=3, first_layer_gen_filters=128, gen_network="composite", gen_ds_layers=3,
@@ -47,6 +47,10 @@ DEFAULTS = dict(  # options/base_options.py, options/train_options.py (SURVEY se
     fused_adam=True,     # one-launch HIP Adam (ir2rgb_amd.optim); False = torch.optim.Adam(foreach=True)
     loss_scale=None,     # f16 training: a number (static scale), "dynamic" (2^16, halved on overflow, doubled after 2000 clean
                          # windows) or an ir2rgb_amd.optim.LossScaler; overflowed windows are skipped on the device.  Needs fused_adam
+    ema_decay=None,      # a number in [0, 1): trainer.ema (ir2rgb_amd.optim.ParamEMA) averages every generator's parameters after each
+                         # generator step, one launch per window; a loss-scaled window that was skipped skips the average too (decided
+                         # on the device).  trainer.ema_generators() are the averaged networks for inference.  None: nothing is allocated
+    ema_warmup=True,     # the n-th average uses min(ema_decay, (1 + n) / (10 + n)): the first ones follow the parameters closely
     fused_losses=True,   # grouped HIP loss kernels (ir2rgb_amd.losses); False = the same terms through torch ops
     batched_repack=True,  # all packed weight copies refreshed by one launch after the optimizer steps (layers.WeightRepacker)
     build_flow_net=True,  # False: trainer.flow_net is left None for the caller to set (tests plug a stand-in for FlowNet2)
@@ -130,6 +134,7 @@ class Vid2VidTrainer:
         o = dict(DEFAULTS)
         o.update(overrides)
         check_loss_scale_option(o["loss_scale"], o["fused_adam"])     # (a ValueError before anything is built)
+        check_ema_option(o["ema_decay"])
         if o["lr_policy"] not in ("reference", "all"):
             raise ValueError(f"lr_policy: \"reference\" or \"all\", got {o['lr_policy']!r}")
         self.opt, self.device, self.world = o, device, world_size
@@ -193,6 +198,11 @@ class Vid2VidTrainer:
         self.optimizer_D_T = [self._make_optimizer(g.params, o["lr"], self._rule_DT[1]) for g in self.grads_DT]
         self.loss_scaler = make_loss_scaler(o["loss_scale"], device)
         self._register_scaler_tables()
+        # the average of ALL generators' parameters, whatever niter_fix_global says: a fixed scale's average equals its
+        # parameters (p == e leaves e as it is) until update_fixed_params(), which leaves the average alone
+        self.ema = self._ema_netG = None
+        if o["ema_decay"] is not None:
+            self.ema = ParamEMA([p for g in self.netG for p in g.parameters()], o["ema_decay"], o["ema_warmup"])
         self.repacker = layers.WeightRepacker(list(self.netG) + [self.netD] + list(self.netD_T)) if o["batched_repack"] else None
         self.reset_sequence()
 
@@ -237,6 +247,36 @@ class Vid2VidTrainer:
         if self.loss_scaler is not None:
             self.loss_scaler.forget_tables()
             self._register_scaler_tables()
+
+    def ema_generators(self):
+        """The averaged generators (``ema_decay``): modules built once with the trainer's options whose parameters ARE the
+        views of ``trainer.ema``'s shadow buffer (``requires_grad=False``; nothing is copied per window, and their packed
+        half weights refresh on their next forward because every update moves the version counters).  BatchNorm running
+        statistics and ``num_batches_tracked`` are not averaged: they are copied from the live generators at each call."""
+        if self.ema is None:
+            raise ValueError("ema_generators: the trainer was built without ema_decay")
+        if self._ema_netG is None:
+            from .inference import VideoTranslator
+            with torch.random.fork_rng(devices=[]):         # (the modules' initialisation draws: not from the trainer's stream)
+                gens = VideoTranslator._build_generators(self.opt)
+            i = 0
+            for g in gens:
+                for name, p in list(g.named_parameters()):
+                    owner, _, leaf = name.rpartition(".")
+                    view = self.ema.shadow(i)
+                    assert view.shape == p.shape, name
+                    (g.get_submodule(owner) if owner else g)._parameters[leaf] = torch.nn.Parameter(view, requires_grad=False)
+                    i += 1
+                g.to(self.device).train()                   # (moves the buffers; the parameters are on the device already)
+                g.compute_dtype = self.opt["compute_dtype"]
+            assert i == len(self.ema.params)
+            self._ema_netG = gens
+        layers.flush_bn_counters()
+        with torch.no_grad():
+            for g, live in zip(self._ema_netG, self.netG):
+                for b, src in zip(g.buffers(), live.buffers()):
+                    b.copy_(src)
+        return self._ema_netG
 
     def attach_schedule(self, schedule):
         """The ``ir2rgb_amd.schedule.TrainingSchedule`` whose arithmetic ``update_learning_rate`` and ``update_training_batch``
@@ -698,6 +738,8 @@ class Vid2VidTrainer:
         # (world > 1: the averaged gradient is the same on every rank, so every rank takes the same skip decision)
         self.grads_G.wait()
         step(self.optimizer_G)
+        if self.ema is not None:     # (world > 1: every rank averages the same parameters; no traffic)
+            self.ema.update(self.optimizer_G)
         self.grads_D.wait()
         step(self.optimizer_D)
         for s in range(n_temporal):
