@@ -11,9 +11,8 @@
 // The contraction index (pixels) is the SLOW index of both operands in memory, so both MFMA
 // operands need a transpose: tiles are staged pixel-major into LDS with 16-byte LDS-DMA and the
 // fragments are read with ds_read_b64_tr_b16 (hardware 4x16 transpose).  LDS rows are 256 B
-// (128 channels); 32-byte channel pair P of row r is stored at pair P ^ f(r),
-// f(r) = (r & 3) | ((r >> 3) & 1) << 2, which makes the eight rows touched by one transposed read
-// (two 16-lane groups x 4 rows) hit 8 disjoint 32-byte bank windows.
+// (128 channels); 32-byte channel pair P of row r is stored at pair P ^ f(r), f = swz256 below, which makes
+// the eight rows touched by one transposed read (two 16-lane groups x 4 rows) hit 8 disjoint 32-byte bank windows.
 //
 // Workgroup = 512 threads (4 multiplying waves, 2x2, and 4 staging waves), tile 128 (a) x 128 (b) for ONE tap
 // and one K-split, K-step = 64 pixels, two LDS stages (64 KB -> 2 workgroups per CU).  Split-K partial tiles go to
@@ -46,6 +45,83 @@ __device__ __forceinline__ f32x4 mfma_s16(s16x8 a, s16x8 b, f32x4 c) {
 
 __device__ __forceinline__ s16x4 lds_tr(const unsigned char *p) {
     return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4 *)p);
+}
+
+// ----------------------------------------------------------------------------------------
+// What the kernels below share.  Staging side (which source chunk a lane's LDS slot holds) and reading side (where a
+// lane's transposed read finds a channel pair) meet in the swizzle and in nothing else.
+// ----------------------------------------------------------------------------------------
+// Swizzle term of LDS row r: 32-byte channel pair P of the row is stored at pair P ^ f(r).
+//   256-byte rows (one-tap kernel; 8 pairs, 3 bits): a row spans all 64 banks, so the eight rows of a transposed read
+//     (two 16-lane groups x 4 rows, first row a multiple of 4) need 8 different pairs: bits 0, 1 and 3 of r.
+//   128-byte rows (the 64 x 64 kernels; 4 pairs, 2 bits): bit 0 of r already picks the half of the bank span, so bits 1 and
+//     3 of r choose the pair -- and the rows {r0+0..3, r0+8..11} then fall into 8 distinct 32-byte bank windows for ANY r0,
+//     which is what lets the tap offsets shift the read rows freely.
+__device__ __forceinline__ int swz256(int r) { return (r & 3) | (((r >> 3) & 1) << 2); }
+__device__ __forceinline__ int swz128(int r) { return ((r >> 1) & 1) | (((r >> 3) & 1) << 1); }
+// staging: the source 16-byte chunk held by LDS slot `sl` of a row with swizzle term f
+__device__ __forceinline__ int slot_chunk(int sl, int f) { return (((sl >> 1) ^ f) << 1) | (sl & 1); }
+
+// one MFMA operand (8 K values per lane) from the transposed reads of two 4-row groups
+__device__ __forceinline__ s16x8 join(s16x4 lo, s16x4 hi) { return (s16x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]}; }
+__device__ __forceinline__ s16x8 frag_pair(const unsigned char *lo, const unsigned char *hi) { return join(lds_tr(lo), lds_tr(hi)); }
+
+// The two-stage loader loop of a staging wave: issue(ks, buf) starts the LDS-DMA of K-step ks into stage buf.
+template <class Issue>
+__device__ __forceinline__ void stage_two(int kbeg, int kend, Issue &&issue) {
+    issue(kbeg, 0);
+    int lb = 0;
+    for (int ks = kbeg; ks < kend; ++ks) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // step ks has landed
+        __builtin_amdgcn_s_barrier();                         // ... and step ks-1 has been consumed
+        if (ks + 1 < kend) issue(ks + 1, lb ^ 1);
+        lb ^= 1;
+    }
+}
+
+// ---- the 64 (a) x 64 (b) tile kernels: 128-byte LDS rows, four multiplying waves of 16 b-channels each ----
+// block id -> K-split and tile origin
+struct Tile64 { int split, a0, b0; };
+__device__ __forceinline__ Tile64 tile64(int Ca, int Cb) {
+    const int ntb = Cb >> 6, nta = Ca >> 6;
+    int bid = blockIdx.x;
+    const int tb = bid % ntb; bid /= ntb;
+    return {bid / nta, (bid % nta) * 64, tb * 64};
+}
+
+// A multiplying lane.  Transposed read: lane 4q+p of a 16-lane group reads LDS row q, channels 4p..4p+3 of a 16-channel
+// pair; group grp takes the rows 8*grp.. of a 32-row K block (half h: + 4*h).  The accumulator tile holds rows grp*4 + r,
+// column l15.  A tap's B fragment (patch row R, this wave's pair) is at R * 128 + ((wave ^ swz128(R)) << 5) + sub behind
+// the kernel's patch base; the three kernels write that sum out: with it as a function of (R, pair)
+// conv_wgrad_line_kernel came out with other VGPR counts (tools/kernel_digest.py).
+struct Lane64 {
+    int grp, l15, sub, rl;      // sub: byte offset inside the pair; rl: row of this lane inside a K block (h = 0)
+    int aoff[4];                // the four 16-channel pairs of the gradient tile (rows 0..63 of a stage)
+};
+__device__ __forceinline__ Lane64 lane64(int lane) {
+    Lane64 l;
+    l.grp = lane >> 4; l.l15 = lane & 15;
+    const int qd = l.l15 >> 2, pp = l.l15 & 3;
+    l.sub = (pp >> 1) * 16 + (pp & 1) * 8;
+    l.rl = 8 * l.grp + qd;
+#pragma unroll
+    for (int mi = 0; mi < 4; ++mi) l.aoff[mi] = l.rl * 128 + ((mi ^ swz128(l.rl)) << 5) + l.sub;
+    return l;
+}
+
+// epilogue of the line and column kernels: D[split][tap][a][b] (fp32 slab of this K-split)
+template <int NT>
+__device__ __forceinline__ void store_slabs(float *D, const f32x4 (&acc)[NT][4], const Tile64 &t64, const Lane64 &l, int wave,
+                                            int Ca, int Cb) {
+    const int b = t64.b0 + wave * 16 + l.l15;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        float *Dt = D + ((long)t64.split * NT + t) * Ca * Cb;
+#pragma unroll
+        for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) Dt[(long)(t64.a0 + mi * 16 + l.grp * 4 + r) * Cb + b] = acc[t][mi][r];
+    }
 }
 
 // 512 threads: waves 0..3 multiply and waves 4..7 only stage (as in conv_wgrad3x3_kernel): the eight LDS-DMA issues of a
@@ -87,8 +163,7 @@ conv_wgrad_kernel(const uint16_t *__restrict__ U, const uint16_t *__restrict__ V
 
     // ---------------- staging roles: 16 lanes per 256-B pixel row, 4 rows per wave instruction ----------------
     const int slot = tid & 15, r0 = tid >> 4;                   // rows r0 + 16*i, i = 0..3
-    const int f = (r0 & 3) | (((r0 >> 3) & 1) << 2);            // same for r0 + 16*i
-    const int chunk = ((((slot >> 1) ^ f) << 1) | (slot & 1));  // source 16-B chunk held by this LDS slot
+    const int chunk = slot_chunk(slot, swz256(r0));             // (swz256 is the same for r0 + 16*i)
     // this thread's V chunk: tap and channel offset (tpb == 2: chunks 0..7 = first tap of the pair, 8..15 = second)
     const int vtap = g.tpb == 2 ? tapg * 2 + (chunk >> 3) : tapg;
     const int vch = g.tpb == 2 ? (chunk & 7) * 8 : b0 + chunk * 8;
@@ -151,11 +226,11 @@ conv_wgrad_kernel(const uint16_t *__restrict__ U, const uint16_t *__restrict__ V
     const int grp = lane >> 4, l15 = lane & 15;
     const int qd = l15 >> 2, pp = l15 & 3;          // transposed read: lane 4q+p -> LDS row q, channels 4p..4p+3
     // Row read by this lane in K32-step kk, half h: r = kk*32 + 4*h + (8*grp + qd).  Its swizzle term
-    // f(r) = (r&3) | ((r>>3)&1)<<2 = qd | (grp&1)<<2 does not depend on (kk, h): a per-lane constant.  So
+    // swz256(r) = qd | (grp&1)<<2 does not depend on (kk, h): a per-lane constant.  So
     //   address = [ (8*grp+qd)*256 + (pp>>1)*16 + (pp&1)*8 + ((col0>>4) ^ fr)*32 ]   per lane and per m
     //           + (kk*32 + 4*h)*256                                                  instruction immediate
     //           + tile base                                                          one add per K-step and m
-    const int fr = qd | ((grp & 1) << 2);
+    const int fr = swz256(8 * grp + qd);
     const int lane_off = (8 * grp + qd) * 256 + (pp >> 1) * 16 + (pp & 1) * 8;
     int aoff[4], boff[4];
 #pragma unroll
@@ -163,11 +238,7 @@ conv_wgrad_kernel(const uint16_t *__restrict__ U, const uint16_t *__restrict__ V
         aoff[m] = lane_off + ((((wr * 64 + m * 16) >> 4) ^ fr) << 5);
         boff[m] = lane_off + ((((wc * 64 + m * 16) >> 4) ^ fr) << 5) + 16384;
     }
-    auto frag = [&](const unsigned char *p, int kk) -> s16x8 {
-        const s16x4 lo = lds_tr(p + (kk * 32) * 256);
-        const s16x4 hi = lds_tr(p + (kk * 32 + 4) * 256);
-        return (s16x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    };
+    auto frag = [&](const unsigned char *p, int kk) { return frag_pair(p + (kk * 32) * 256, p + (kk * 32 + 4) * 256); };
 
     f32x4 acc[4][4];
 #pragma unroll
@@ -176,14 +247,7 @@ conv_wgrad_kernel(const uint16_t *__restrict__ U, const uint16_t *__restrict__ V
         for (int ni = 0; ni < 4; ++ni) acc[mi][ni] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
     if (loader) {
-        issue(kbeg, 0);
-        int lb = 0;
-        for (int ks = kbeg; ks < kend; ++ks) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // step ks has landed
-            __builtin_amdgcn_s_barrier();                         // ... and step ks-1 has been consumed
-            if (ks + 1 < kend) issue(ks + 1, lb ^ 1);
-            lb ^= 1;
-        }
+        stage_two(kbeg, kend, issue);
         return;
     }
     int buf = 0;
@@ -240,10 +304,8 @@ conv_wgrad_kernel(const uint16_t *__restrict__ U, const uint16_t *__restrict__ V
 // offset ky*66 + kx -- no extra staging.  Four waves split b (16 channels each) and share a (64):
 // 36 accumulator tiles per wave, 26 transposed LDS reads per 36 MFMAs.
 //
-// LDS rows are 128 B (64 channels = four 32-byte pairs); pair P of row r is stored at P ^ f(r),
-// f(r) = ((r>>1)&1) | ((r>>3)&1)<<1: the 8 rows {r0+0..3, r0+8..11} touched by two 16-lane groups of a
-// transposed read then fall into 8 distinct 32-byte bank windows for ANY r0, which is what lets the
-// tap offsets shift the read rows freely.
+// LDS rows are 128 B (64 channels = four 32-byte pairs), swizzled by swz128 (above), which holds for any first row:
+// that is what lets the tap offsets shift the read rows freely.
 // 512 threads: four multiplying waves and four loader waves (one of each per SIMD).
 // Four LDS stages of 36 KB (one workgroup per CU), three K-steps in flight; every loader wave issues exactly
 // nine 1-KB LDS-DMA instructions per K-step (the last three of the 36 are padding into a dummy area)
@@ -257,8 +319,14 @@ struct Wgrad9Geom {
     unsigned u_bytes, v_bytes;
 };
 
-#define W9_STAGE 36864
-#define W9_NST 4
+constexpr int W9_NST = 4;                        // LDS stages: one being multiplied, one landing, W9_NST - 2 further in flight
+constexpr int W9_ROWS = 64 + 3 * 66;             // rows of a K-step: gradient segment + patch
+constexpr int W9_DMA = 9;                        // LDS-DMA instructions (8 rows of 128 B each) per loader wave and K-step
+constexpr int W9_STAGE = 4 * W9_DMA * 1024;
+constexpr int W9_INFLIGHT = (W9_NST - 2) * W9_DMA;   // the counted wait: all but the newest W9_NST - 2 K-steps have landed
+static_assert(4 * W9_DMA * 8 >= W9_ROWS && 4 * (W9_DMA - 1) * 8 < W9_ROWS, "four loader waves x W9_DMA x 8 rows cover a K-step");
+static_assert((W9_NST & (W9_NST - 1)) == 0 && W9_INFLIGHT + W9_DMA < 64, "ring index by mask; vmcnt is a 6-bit counter");
+static_assert(W9_NST * W9_STAGE <= 160 * 1024, "the stages must fit the LDS");
 
 template <int IMM>
 __device__ __forceinline__ s16x4 tr_read(unsigned lds_addr) {
@@ -279,43 +347,38 @@ conv_wgrad3x3_kernel(const uint16_t *__restrict__ U, const uint16_t *__restrict_
     // same SIMD hides them.
     const bool loader = wave8 >= 4;
     const int wave = wave8 & 3;
-    const int ntb = g.Cb >> 6, nta = g.Ca >> 6;
-    int bid = blockIdx.x;
-    const int tb = bid % ntb; bid /= ntb;
-    const int ta = bid % nta;
-    const int split = bid / nta;
-    const int a0 = ta * 64, b0 = tb * 64;
+    const Tile64 t64 = tile64(g.Ca, g.Cb);
+    const int a0 = t64.a0, b0 = t64.b0;
     const int per = (g.ksteps + g.ksplit - 1) / g.ksplit;
-    const int kbeg = split * per, kend = min(g.ksteps, kbeg + per);
+    const int kbeg = t64.split * per, kend = min(g.ksteps, kbeg + per);
 
-    // ---------------- staging: 9 LDS-DMA instructions per wave and K-step; instruction id = wave + 4*j ----------
+    // ---------------- staging: W9_DMA LDS-DMA instructions per wave and K-step; instruction id = wave + 4*j ----------
     // id 0..7: gradient rows id*8 + (lane>>3); id 8..32: patch rows (id-8)*8 + (lane>>3) (< 198 valid);
-    // id 33..35: padding.  Lane slot s = lane & 7 of a 128-B row holds source chunk ((s>>1) ^ f(r))*2 + (s&1).
+    // id 33..35: padding.  Lane slot s = lane & 7 of a 128-B row holds source chunk slot_chunk(s, swz128(row)).
+    constexpr int PJ = W9_DMA - 2;   // patch instructions per wave (j = 2..)
     const rsrc_t ru = make_rsrc(U, g.u_bytes), rv = make_rsrc(V, g.v_bytes);
     const int rin = lane >> 3, sl = lane & 7;
-    auto fsw = [](int r) { return ((r >> 1) & 1) | (((r >> 3) & 1) << 1); };
     unsigned u_off[2];           // byte offset inside the 64-pixel segment of U, j = 0, 1
     // Patch row R -> (dy, dx) relative to (y, x0).  The gather offset of a lane is
     //   base(row, x0) + L0 + [edge fixes], L0 = (dy*W + dx)*Cb*2 + channel bytes,
     // where the fixes only apply on the image border (uniform per K-step: top / bottom row, first / last
     // segment): reflection moves dy = -1 -> +1 (top), +1 -> -1 (bottom), dx = -1 -> +1, 64 -> 62; zero
     // padding turns the lane off.  So a K-step costs a handful of VALU per DMA, no divisions.
-    int v_L0[7], v_fixU[7], v_fixD[7], v_fixL[7], v_fixR[7], v_edge[7];
-    bool v_dead[7];
+    int v_L0[PJ], v_fixU[PJ], v_fixD[PJ], v_fixL[PJ], v_fixR[PJ], v_edge[PJ];
+    bool v_dead[PJ];
     const int cb2i = g.Cb * 2;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const int r = (wave + 4 * j) * 8 + rin;
-        const int chunk = (((sl >> 1) ^ fsw(r)) << 1) | (sl & 1);
-        u_off[j] = (unsigned)r * (unsigned)g.Ca * 2u + (unsigned)(a0 + chunk * 8) * 2u;
+        u_off[j] = (unsigned)r * (unsigned)g.Ca * 2u + (unsigned)(a0 + slot_chunk(sl, swz128(r)) * 8) * 2u;
     }
 #pragma unroll
-    for (int j = 0; j < 7; ++j) {
+    for (int j = 0; j < PJ; ++j) {
         const int id = wave + 4 * (j + 2);
         const int R = (id - 8) * 8 + rin;
-        const bool real = id < 33 && R < 198;
+        const bool real = id < 33 && R < W9_ROWS - 64;
         const int pr = R / 66, pxl = R - pr * 66;
-        const int chunk = (((sl >> 1) ^ fsw(R)) << 1) | (sl & 1);
+        const int chunk = slot_chunk(sl, swz128(R));
         const int dy = pr - 1, dx = pxl - 1;
         v_dead[j] = !real;
         v_L0[j] = (dy * g.W + dx) * cb2i + (b0 + chunk * 8) * 2;
@@ -341,7 +404,7 @@ conv_wgrad3x3_kernel(const uint16_t *__restrict__ U, const uint16_t *__restrict_
 #pragma unroll
         for (int j = 0; j < 2; ++j) lds_dma16(ru, live ? ubase + u_off[j] : IR2RGB_OOB, 0, dst + 4096 * j);
 #pragma unroll
-        for (int j = 0; j < 7; ++j) {
+        for (int j = 0; j < PJ; ++j) {
             const int o = vbase + v_L0[j] + (top ? v_fixU[j] : 0) + (bot ? v_fixD[j] : 0) + (first ? v_fixL[j] : 0) +
                           (last ? v_fixR[j] : 0);
             const bool off = v_dead[j] | !live | (!refl & ((v_edge[j] & edge) != 0));
@@ -356,20 +419,14 @@ conv_wgrad3x3_kernel(const uint16_t *__restrict__ U, const uint16_t *__restrict_
     };
 
     // ---------------- compute roles ----------------
-    const int grp = lane >> 4, l15 = lane & 15;
-    const int qd = l15 >> 2, pp = l15 & 3;
-    const int sub = (pp >> 1) * 16 + (pp & 1) * 8;
-    const int rl = 8 * grp + qd;                       // row of this lane inside a 32-row K block (h = 0)
-    int aoff[4];
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi) aoff[mi] = rl * 128 + ((mi ^ fsw(rl)) << 5) + sub;
+    const Lane64 l = lane64(lane);
     int boff[9][2];
 #pragma unroll
     for (int t = 0; t < 9; ++t)
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-            const int R = (t / 3) * 66 + (t % 3) + rl + 4 * h;
-            boff[t][h] = 8192 + R * 128 + ((wave ^ fsw(R)) << 5) + sub;
+            const int R = (t / 3) * 66 + (t % 3) + l.rl + 4 * h;
+            boff[t][h] = 8192 + R * 128 + ((wave ^ swz128(R)) << 5) + l.sub;
         }
 
     f32x4 acc[9][4];
@@ -381,15 +438,14 @@ conv_wgrad3x3_kernel(const uint16_t *__restrict__ U, const uint16_t *__restrict_
 
     if (kbeg < kend) {
         if (loader) {
-            issue(0);
-            issue(1);
-            issue(2);
+#pragma unroll
+            for (int s = 0; s < W9_NST - 1; ++s) issue(s);
             int st = 0;
             for (int ks = kbeg; ks < kend; ++ks) {
-                asm volatile("s_waitcnt vmcnt(18)" ::: "memory");   // step ks has landed (ks+1, ks+2 may be in flight)
-                __builtin_amdgcn_s_barrier();                         // ... and step ks-1 has been consumed
-                issue((st + 3) & 3);
-                st = (st + 1) & 3;
+                asm volatile("s_waitcnt vmcnt(%0)" ::"n"(W9_INFLIGHT) : "memory");   // step ks has landed (ks+1, ks+2 may be in flight)
+                __builtin_amdgcn_s_barrier();                                         // ... and step ks-1 has been consumed
+                issue((st + W9_NST - 1) & (W9_NST - 1));
+                st = (st + 1) & (W9_NST - 1);
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // drain the padding DMAs before LDS goes away
         } else {
@@ -402,7 +458,7 @@ conv_wgrad3x3_kernel(const uint16_t *__restrict__ U, const uint16_t *__restrict_
                 const unsigned tbase = lds_base + (unsigned)st * W9_STAGE;
                 unsigned av[4], bv[9][2];
     #pragma unroll
-                for (int mi = 0; mi < 4; ++mi) av[mi] = tbase + (unsigned)aoff[mi];
+                for (int mi = 0; mi < 4; ++mi) av[mi] = tbase + (unsigned)l.aoff[mi];
     #pragma unroll
                 for (int t = 0; t < 9; ++t) { bv[t][0] = tbase + (unsigned)boff[t][0]; bv[t][1] = tbase + (unsigned)boff[t][1]; }
                 // 18 fragment steps s = kk*9 + tap, B fragments fetched three steps ahead (LDS latency is
@@ -442,31 +498,26 @@ conv_wgrad3x3_kernel(const uint16_t *__restrict__ U, const uint16_t *__restrict_
                                      : "memory");
                     else
                         asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(blo[cur]), "+v"(bhi[cur]) : "n"(after) : "memory");
-                    const s16x8 b = (s16x8){blo[cur][0], blo[cur][1], blo[cur][2], blo[cur][3],
-                                            bhi[cur][0], bhi[cur][1], bhi[cur][2], bhi[cur][3]};
+                    const s16x8 b = join(blo[cur], bhi[cur]);
 #pragma unroll
-                    for (int mi = 0; mi < 4; ++mi) {
-                        const s16x8 a = (s16x8){alo[KK][mi][0], alo[KK][mi][1], alo[KK][mi][2], alo[KK][mi][3],
-                                                ahi[KK][mi][0], ahi[KK][mi][1], ahi[KK][mi][2], ahi[KK][mi][3]};
-                        acc[T][mi] = mfma_s16<DT>(a, b, acc[T][mi]);
-                    }
+                    for (int mi = 0; mi < 4; ++mi) acc[T][mi] = mfma_s16<DT>(join(alo[KK][mi], ahi[KK][mi]), b, acc[T][mi]);
                 };
                 [&]<int... Ss>(std::integer_sequence<int, Ss...>) { (step(std::integral_constant<int, Ss>{}), ...); }
                 (std::make_integer_sequence<int, 18>{});
-                st = (st + 1) & 3;
+                st = (st + 1) & (W9_NST - 1);
             }
         }
     }
     if (loader) return;
 
     // ---------------- epilogue: [a][b][tap], 9 consecutive floats per (a, b) ----------------
-    float *Dt = D + (long)split * 9 * g.Ca * g.Cb;
-    const int b = b0 + wave * 16 + l15;
+    float *Dt = D + (long)t64.split * 9 * g.Ca * g.Cb;
+    const int b = b0 + wave * 16 + l.l15;
 #pragma unroll
     for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const int a = a0 + mi * 16 + grp * 4 + r;
+            const int a = a0 + mi * 16 + l.grp * 4 + r;
             float *o = Dt + ((long)a * g.Cb + b) * 9;
 #pragma unroll
             for (int t = 0; t < 9; ++t) o[t] = acc[t][mi][r];
@@ -515,14 +566,9 @@ conv_wgrad_line_kernel(const uint16_t *__restrict__ U, const uint16_t *__restric
     const int wave8 = __builtin_amdgcn_readfirstlane(tid >> 6);
     const bool loader = wave8 >= 4;
     const int wave = wave8 & 3;
-    const int ntb = g.Cb >> 6, nta = g.Ca >> 6;
-    int bid = blockIdx.x;
-    const int tb = bid % ntb; bid /= ntb;
-    const int ta = bid % nta;
-    const int split = bid / nta;
-    const int a0 = ta * 64, b0 = tb * 64;
-    const int kbeg = split * g.per, kend = min(g.ksteps, kbeg + g.per);   // (the host leaves no split empty)
-    auto fsw = [](int r) { return ((r >> 1) & 1) | (((r >> 3) & 1) << 1); };
+    const Tile64 t64 = tile64(g.Ca, g.Cb);
+    const int a0 = t64.a0, b0 = t64.b0;
+    const int kbeg = t64.split * g.per, kend = min(g.ksteps, kbeg + g.per);   // (the host leaves no split empty)
 
     if (loader) {
         const rsrc_t ru = make_rsrc(U, g.u_bytes), rv = make_rsrc(V, g.v_bytes);
@@ -530,7 +576,7 @@ conv_wgrad_line_kernel(const uint16_t *__restrict__ U, const uint16_t *__restric
         const unsigned ca2 = (unsigned)g.Ca * 2u, cb2 = (unsigned)g.Cb * 2u;
         // (row, seg) of the next K-step to issue, advanced incrementally; row = n * Hq + qy
         int is_row = kbeg / g.segs, is_seg = kbeg - is_row * g.segs, is_n = is_row / g.Hq, is_y = is_row - is_n * g.Hq;
-        auto issue = [&](int buf) {
+        auto issue = [&](int, int buf) {
             unsigned char *dst = smem + buf * STAGE + wave * 1024;
             const int x0 = is_seg * 64;
 #pragma unroll
@@ -540,7 +586,7 @@ conv_wgrad_line_kernel(const uint16_t *__restrict__ U, const uint16_t *__restric
                 unsigned off = IR2RGB_OOB;
                 if (id < 8) {                           // gradient rows: output pixels x0 + r of this row
                     const int r = id * 8 + rin;
-                    const int chunk = (((sl >> 1) ^ fsw(r)) << 1) | (sl & 1);
+                    const int chunk = slot_chunk(sl, swz128(r));
                     if (x0 + r < g.Wq)
                         off = ((unsigned)is_row * (unsigned)g.Wq + (unsigned)(x0 + r)) * ca2 + (unsigned)(a0 + chunk * 8) * 2u;
                     lds_dma16(ru, off, 0, dst + 4096 * j);
@@ -548,7 +594,7 @@ conv_wgrad_line_kernel(const uint16_t *__restrict__ U, const uint16_t *__restric
                     const int R = (id - 8) * 8 + rin;
                     const int run = R / PW, pxl = R - run * PW;
                     const int pr = SX == 2 ? run >> 1 : run;
-                    const int chunk = (((sl >> 1) ^ fsw(R)) << 1) | (sl & 1);
+                    const int chunk = slot_chunk(sl, swz128(R));
                     int iy = is_y * g.stride_y + g.dy0 + pr;
                     int ix = SX == 2 ? 2 * x0 + g.dx0 + 2 * pxl + (run & 1) : x0 + pxl + g.dx0;
                     const bool inb = ((unsigned)iy < (unsigned)g.Hv) & ((unsigned)ix < (unsigned)g.Wv);
@@ -570,33 +616,20 @@ conv_wgrad_line_kernel(const uint16_t *__restrict__ U, const uint16_t *__restric
                 if (++is_y == g.Hq) { is_y = 0; ++is_n; }
             }
         };
-        issue(0);
-        int lb = 0;
-        for (int ks = kbeg; ks < kend; ++ks) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // step ks has landed
-            __builtin_amdgcn_s_barrier();                         // ... and step ks-1 has been consumed
-            if (ks + 1 < kend) issue(lb ^ 1);
-            lb ^= 1;
-        }
+        stage_two(kbeg, kend, issue);
         return;
     }
 
     // ---------------- multiplying waves ----------------
-    const int grp = lane >> 4, l15 = lane & 15;
-    const int qd = l15 >> 2, pp = l15 & 3;
-    const int sub = (pp >> 1) * 16 + (pp & 1) * 8;
-    const int rl = 8 * grp + qd;                       // row of this lane inside a 32-row K block (h = 0)
-    int aoff[4];
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi) aoff[mi] = rl * 128 + ((mi ^ fsw(rl)) << 5) + sub;
+    const Lane64 l = lane64(lane);
     int boff[NT][2];
 #pragma unroll
     for (int t = 0; t < NT; ++t)
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             const int ty = t / NTX, tx = t % NTX;
-            const int R = (SX == 2 ? (ty * 2 + (tx & 1)) * PW + (tx >> 1) : ty * PW + tx) + rl + 4 * h;
-            boff[t][h] = 8192 + R * 128 + ((wave ^ fsw(R)) << 5) + sub;
+            const int R = (SX == 2 ? (ty * 2 + (tx & 1)) * PW + (tx >> 1) : ty * PW + tx) + l.rl + 4 * h;
+            boff[t][h] = 8192 + R * 128 + ((wave ^ swz128(R)) << 5) + l.sub;
         }
     f32x4 acc[NT][4];
 #pragma unroll
@@ -607,18 +640,16 @@ conv_wgrad_line_kernel(const uint16_t *__restrict__ U, const uint16_t *__restric
     for (int ks = kbeg; ks < kend; ++ks) {
         __builtin_amdgcn_s_barrier();
         const unsigned char *tile = smem + buf * STAGE;
+        // (conv_wgrad_col_kernel has the same loop with another tap address; as one function taking that address, this
+        // kernel's register allocation moved -- VGPRs 195 -> 206, 243 -> 229 -- so both stay written out)
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk) {
             s16x8 a[4];
 #pragma unroll
-            for (int mi = 0; mi < 4; ++mi) {
-                const s16x4 lo = lds_tr(tile + aoff[mi] + kk * 4096), hi = lds_tr(tile + aoff[mi] + kk * 4096 + 512);
-                a[mi] = (s16x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-            }
+            for (int mi = 0; mi < 4; ++mi) a[mi] = frag_pair(tile + l.aoff[mi] + kk * 4096, tile + l.aoff[mi] + kk * 4096 + 512);
 #pragma unroll
             for (int t = 0; t < NT; ++t) {
-                const s16x4 lo = lds_tr(tile + boff[t][0] + kk * 4096), hi = lds_tr(tile + boff[t][1] + kk * 4096);
-                const s16x8 b = (s16x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+                const s16x8 b = frag_pair(tile + boff[t][0] + kk * 4096, tile + boff[t][1] + kk * 4096);
 #pragma unroll
                 for (int mi = 0; mi < 4; ++mi) acc[t][mi] = mfma_s16<DT>(a[mi], b, acc[t][mi]);
             }
@@ -626,16 +657,7 @@ conv_wgrad_line_kernel(const uint16_t *__restrict__ U, const uint16_t *__restric
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this wave's reads of the stage have returned before it is handed back
         buf ^= 1;
     }
-    // ---------------- epilogue: D[split][tap][a][b] ----------------
-    const int b = b0 + wave * 16 + l15;
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        float *Dt = D + ((long)split * NT + t) * g.Ca * g.Cb;
-#pragma unroll
-        for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) Dt[(long)(a0 + mi * 16 + grp * 4 + r) * g.Cb + b] = acc[t][mi][r];
-    }
+    store_slabs(D, acc, t64, l, wave, g.Ca, g.Cb);
 }
 
 // The k x 1 layers again, walking DOWN the image: consecutive K-steps are the same 64-pixel column segment of consecutive
@@ -658,14 +680,9 @@ conv_wgrad_col_kernel(const uint16_t *__restrict__ U, const uint16_t *__restrict
     const int wave8 = __builtin_amdgcn_readfirstlane(tid >> 6);
     const bool loader = wave8 >= 4;
     const int wave = wave8 & 3;
-    const int ntb = g.Cb >> 6, nta = g.Ca >> 6;
-    int bid = blockIdx.x;
-    const int tb = bid % ntb; bid /= ntb;
-    const int ta = bid % nta;
-    const int split = bid / nta;
-    const int a0 = ta * 64, b0 = tb * 64;
-    const int kbeg = split * g.per, kend = min(g.ksteps, kbeg + g.per);   // K-step ks = (column = n * segs + seg, row y), y fastest
-    auto fsw = [](int r) { return ((r >> 1) & 1) | (((r >> 3) & 1) << 1); };
+    const Tile64 t64 = tile64(g.Ca, g.Cb);
+    const int a0 = t64.a0, b0 = t64.b0;
+    const int kbeg = t64.split * g.per, kend = min(g.ksteps, kbeg + g.per);   // K-step ks = (column = n * segs + seg, row y), y fastest
 
     if (loader) {
         const rsrc_t ru = make_rsrc(U, g.u_bytes), rv = make_rsrc(V, g.v_bytes);
@@ -673,7 +690,7 @@ conv_wgrad_col_kernel(const uint16_t *__restrict__ U, const uint16_t *__restrict
         const unsigned ca2 = (unsigned)g.Ca * 2u, cb2 = (unsigned)g.Cb * 2u;
         int col = kbeg / g.Hq, y = kbeg - col * g.Hq, n = col / g.segs, seg = col - n * g.segs, ub = 0;
         bool first = true;
-        auto issue = [&]() {
+        auto issue = [&](int, int) {   // (the gradient buffer alternates in ub; the patch ring is indexed by the row)
             const bool prime = first || y == 0;
             const int x0 = seg * 64, half = col & 1;
             const int total = 8 + (prime ? NTY : SY) * 8;
@@ -684,7 +701,7 @@ conv_wgrad_col_kernel(const uint16_t *__restrict__ U, const uint16_t *__restrict
                 unsigned off = IR2RGB_OOB;
                 if (id < 8) {                           // gradient pixels x0 + r of output row y
                     const int r = id * 8 + rin;
-                    const int chunk = (((sl >> 1) ^ fsw(r)) << 1) | (sl & 1);
+                    const int chunk = slot_chunk(sl, swz128(r));
                     if (x0 + r < g.Wq)
                         off = (((unsigned)n * (unsigned)g.Hq + (unsigned)y) * (unsigned)g.Wq + (unsigned)(x0 + r)) * ca2 +
                               (unsigned)(a0 + chunk * 8) * 2u;
@@ -693,7 +710,7 @@ conv_wgrad_col_kernel(const uint16_t *__restrict__ U, const uint16_t *__restrict
                     const int q = id - 8;
                     const int jt = (prime ? 0 : NTY - SY) + (q >> 3);
                     const int r = (q & 7) * 8 + rin;
-                    const int chunk = (((sl >> 1) ^ fsw(r)) << 1) | (sl & 1);
+                    const int chunk = slot_chunk(sl, swz128(r));
                     const int v = y * SY + jt;
                     int iy = v + g.dy0;
                     const int ix = x0 + r;
@@ -715,25 +732,15 @@ conv_wgrad_col_kernel(const uint16_t *__restrict__ U, const uint16_t *__restrict
                 if (++seg == g.segs) { seg = 0; ++n; }
             }
         };
-        issue();
-        for (int ks = kbeg; ks < kend; ++ks) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // step ks has landed
-            __builtin_amdgcn_s_barrier();                         // ... and step ks-1 has been consumed
-            if (ks + 1 < kend) issue();
-        }
+        stage_two(kbeg, kend, issue);
         return;
     }
 
     // ---------------- multiplying waves ----------------
-    const int grp = lane >> 4, l15 = lane & 15;
-    const int qd = l15 >> 2, pp = l15 & 3;
-    const int sub = (pp >> 1) * 16 + (pp & 1) * 8;
-    const int rl = 8 * grp + qd;
-    int aoff[4], boffl[2];
+    const Lane64 l = lane64(lane);
+    int boffl[2];
 #pragma unroll
-    for (int mi = 0; mi < 4; ++mi) aoff[mi] = rl * 128 + ((mi ^ fsw(rl)) << 5) + sub;
-#pragma unroll
-    for (int h = 0; h < 2; ++h) boffl[h] = PATCH0 + (rl + 4 * h) * 128 + ((wave ^ fsw(rl + 4 * h)) << 5) + sub;
+    for (int h = 0; h < 2; ++h) boffl[h] = PATCH0 + (l.rl + 4 * h) * 128 + ((wave ^ swz128(l.rl + 4 * h)) << 5) + l.sub;
     f32x4 acc[NTY][4];
 #pragma unroll
     for (int t = 0; t < NTY; ++t)
@@ -748,17 +755,13 @@ conv_wgrad_col_kernel(const uint16_t *__restrict__ U, const uint16_t *__restrict
         for (int kk = 0; kk < 2; ++kk) {
             s16x8 a[4];
 #pragma unroll
-            for (int mi = 0; mi < 4; ++mi) {
-                const s16x4 lo = lds_tr(ut + aoff[mi] + kk * 4096), hi = lds_tr(ut + aoff[mi] + kk * 4096 + 512);
-                a[mi] = (s16x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-            }
+            for (int mi = 0; mi < 4; ++mi) a[mi] = frag_pair(ut + l.aoff[mi] + kk * 4096, ut + l.aoff[mi] + kk * 4096 + 512);
 #pragma unroll
-            for (int t = 0; t < NTY; ++t) {
+            for (int t = 0; t < NTY; ++t) {     // tap t = ring slot (v0 + t) mod RC of this column parity
                 int slot = v0 + t;
                 slot = slot >= RC ? slot - RC : slot;
                 const unsigned char *pt = smem + (base + slot) * 8192 + kk * 4096;
-                const s16x4 lo = lds_tr(pt + boffl[0]), hi = lds_tr(pt + boffl[1]);
-                const s16x8 b = (s16x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+                const s16x8 b = frag_pair(pt + boffl[0], pt + boffl[1]);
 #pragma unroll
                 for (int mi = 0; mi < 4; ++mi) acc[t][mi] = mfma_s16<DT>(a[mi], b, acc[t][mi]);
             }
@@ -767,15 +770,7 @@ conv_wgrad_col_kernel(const uint16_t *__restrict__ U, const uint16_t *__restrict
         ub ^= 1;
         if (++y == g.Hq) { y = 0; ++col; }
     }
-    const int b = b0 + wave * 16 + l15;
-#pragma unroll
-    for (int t = 0; t < NTY; ++t) {
-        float *Dt = D + ((long)split * NTY + t) * g.Ca * g.Cb;
-#pragma unroll
-        for (int mi = 0; mi < 4; ++mi)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) Dt[(long)(a0 + mi * 16 + grp * 4 + r) * g.Cb + b] = acc[t][mi][r];
-    }
+    store_slabs(D, acc, t64, l, wave, g.Ca, g.Cb);
 }
 
 // out[i] = sum_split D[split][i]   (slabs already in the torch layout)
@@ -874,25 +869,33 @@ static void launch_wgrad_finish(const float *D, float *out, int Ca, int Cb, int 
 
 // U (channels a, whose pixels are the K axis) and V (channels b): the gradient of the output [N,Hout,Wout,Cout] and the
 // input [N,Hin,Win,Cin] -- for ConvTranspose2d the other way round.
-template <class Geom> static void orient_uv(const ir2rgb_conv_desc *d, Geom *g) {
-    g->N = d->N;
-    if (!d->transposed) { g->Hq = d->Hout; g->Wq = d->Wout; g->Hv = d->Hin; g->Wv = d->Win; g->Ca = d->Cout; g->Cb = d->Cin; }
-    else                { g->Hq = d->Hin; g->Wq = d->Win; g->Hv = d->Hout; g->Wv = d->Wout; g->Ca = d->Cin; g->Cb = d->Cout; }
-}
+struct WgradUV {
+    int N, Hq, Wq, Hv, Wv, Ca, Cb;
+    long Q;                     // pixels of U: the K axis
+    unsigned u_bytes, v_bytes;  // extents of U and V, both < 2^31 (32-bit buffer offsets)
+    // the kernels' geometries carry these under the same names
+    template <class Geom> void put(Geom *g) const {
+        g->N = N; g->Hq = Hq; g->Wq = Wq; g->Hv = Hv; g->Wv = Wv; g->Ca = Ca; g->Cb = Cb; g->u_bytes = u_bytes; g->v_bytes = v_bytes;
+    }
+};
 
-// The one-tap kernel, which runs every valid descriptor: its plan is also the descriptor's validation.
-static int plan(const ir2rgb_conv_desc *d, WgradGeom *g) {
+// Validates a descriptor (every valid one runs on the one-tap kernel) and orients it: *uv, and the one-tap kernel's plan.
+static int plan(const ir2rgb_conv_desc *d, WgradUV *uv, WgradGeom *g) {
     if (!d || d->N < 1 || d->Cin < 8 || d->Cout < 8 || (d->Cin % 8) || (d->Cout % 8) || d->kh < 1 || d->kw < 1 ||
         d->stride_h < 1 || d->stride_w < 1 || d->pad_h < 0 || d->pad_w < 0)
         return IR2RGB_EINVAL;
     if (d->dtype != IR2RGB_BF16 && d->dtype != IR2RGB_F16) return IR2RGB_ENOSUP;
     if (d->transposed && d->pad_mode != 0) return IR2RGB_ENOSUP;
+    if (!d->transposed) *uv = WgradUV{d->N, d->Hout, d->Wout, d->Hin, d->Win, d->Cout, d->Cin};
+    else                *uv = WgradUV{d->N, d->Hin, d->Win, d->Hout, d->Wout, d->Cin, d->Cout};
+    const long Q = (long)uv->N * uv->Hq * uv->Wq, Pv = (long)uv->N * uv->Hv * uv->Wv;
+    if (Q >= (1L << 31) || Pv >= (1L << 31)) return IR2RGB_EINVAL;
+    if (Q * uv->Ca * 2 >= (1L << 31) || Pv * uv->Cb * 2 >= (1L << 31)) return IR2RGB_EINVAL;  // 32-bit buffer offsets
+    uv->Q = Q; uv->u_bytes = (unsigned)(Q * uv->Ca * 2); uv->v_bytes = (unsigned)(Pv * uv->Cb * 2);
     *g = WgradGeom{};
-    orient_uv(d, g);
+    uv->put(g);
     g->stride_y = d->stride_h; g->stride_x = d->stride_w; g->pad_mode = d->pad_mode;
     g->nty = d->kh; g->ntx = d->kw; g->dy0 = -d->pad_h; g->dx0 = -d->pad_w;
-    long Q = (long)g->N * g->Hq * g->Wq;
-    if (Q >= (1L << 31) || (long)g->N * g->Hv * g->Wv >= (1L << 31)) return IR2RGB_EINVAL;
     g->ksteps = (int)((Q + 63) / 64);
     // K-split by a cost model: rounds of 512 resident workgroups (2 per CU) x (K-steps per split + pipeline
     // fill) against the extra slab traffic of the finish pass (split x elems x 8 bytes at ~4 TB/s).
@@ -909,32 +912,31 @@ static int plan(const ir2rgb_conv_desc *d, WgradGeom *g) {
     }
     g->ksplit = best;
     g->div_hw = make_fastdiv((unsigned)(g->Hq * g->Wq)); g->div_w = make_fastdiv((unsigned)g->Wq);
-    {
-        const long ub = Q * g->Ca * 2, vb = (long)g->N * g->Hv * g->Wv * g->Cb * 2;
-        if (ub >= (1L << 31) || vb >= (1L << 31)) return IR2RGB_EINVAL;  // 32-bit buffer offsets
-        g->u_bytes = (unsigned)ub; g->v_bytes = (unsigned)vb;
-    }
     return IR2RGB_OK;
 }
 
-static bool plan9(const ir2rgb_conv_desc *d, Wgrad9Geom *g) {
+// The 64 x 64 tile kernels run one workgroup per CU: split K until ~256 workgroups exist, keeping >= 8 K-steps per split,
+// at most 256 splits.
+static int split_per_cu(const WgradUV &uv, long ksteps) {
+    const long tiles = (long)(uv.Ca / 64) * (uv.Cb / 64);
+    long ks = (256 + tiles - 1) / tiles;
+    if (ks > ksteps / 8) ks = ksteps / 8;
+    if (ks < 1) ks = 1;
+    if (ks > 256) ks = 256;
+    return (int)ks;
+}
+
+// plan9 / plan_line: after plan() succeeded, which left the orientation and the (valid) extents in uv
+static bool plan9(const ir2rgb_conv_desc *d, const WgradUV &uv, Wgrad9Geom *g) {
     if (d->transposed || d->kh != 3 || d->kw != 3 || d->stride_h != 1 || d->stride_w != 1 || d->pad_h != 1 || d->pad_w != 1)
         return false;
     if (d->Hout != d->Hin || d->Wout != d->Win || (d->Win % 64) || (d->Cin % 64) || (d->Cout % 64) || d->Hin < 2) return false;
-    const long Q = (long)d->N * d->Hin * d->Win;
-    if (Q * d->Cout * 2 >= (1L << 31) || Q * d->Cin * 2 >= (1L << 31)) return false;
     *g = Wgrad9Geom{};
-    g->N = d->N; g->H = d->Hin; g->W = d->Win; g->Ca = d->Cout; g->Cb = d->Cin; g->pad_mode = d->pad_mode;
-    g->segs = d->Win / 64;
-    g->ksteps = (int)(Q / 64);
-    g->u_bytes = (unsigned)(Q * d->Cout * 2); g->v_bytes = (unsigned)(Q * d->Cin * 2);
-    // one workgroup per CU: split K until ~256 workgroups exist, keeping >= 8 K-steps per split
-    const long tiles = (long)(d->Cout / 64) * (d->Cin / 64);
-    long ks = (256 + tiles - 1) / tiles;
-    if (ks > g->ksteps / 8) ks = g->ksteps / 8;
-    if (ks < 1) ks = 1;
-    if (ks > 256) ks = 256;
-    g->ksplit = (int)ks;
+    g->N = uv.N; g->H = uv.Hq; g->W = uv.Wq; g->Ca = uv.Ca; g->Cb = uv.Cb; g->pad_mode = d->pad_mode;
+    g->segs = uv.Wq / 64;
+    g->ksteps = (int)(uv.Q / 64);
+    g->u_bytes = uv.u_bytes; g->v_bytes = uv.v_bytes;
+    g->ksplit = split_per_cu(uv, g->ksteps);
     return true;
 }
 
@@ -942,7 +944,7 @@ static bool plan9(const ir2rgb_conv_desc *d, Wgrad9Geom *g) {
 // along y for k x 1, where the stride enters the row index) and the stride-2 4x1; 64-multiples on both channel axes.
 // 7x1 at stride 1 and 4x1 at stride 2 have a ring kernel of their own (conv_wgrad_col_kernel).
 enum LineForm { LINE_3X3S2, LINE_COL7, LINE_COL4S2, LINE_7X1, LINE_1X7, LINE_4X1 };
-static bool plan_line(const ir2rgb_conv_desc *d, WgradLineGeom *g, LineForm *form) {
+static bool plan_line(const ir2rgb_conv_desc *d, const WgradUV &uv, WgradLineGeom *g, LineForm *form) {
     if ((d->Cin % 64) || (d->Cout % 64)) return false;
     // the stride-2 3x3 layers (measured against the one-tap kernel, us at the training sizes: 64->128 @512x1024 49 vs 60, 512->1024 @64x128 54 vs 60,
     // 1024->512 transposed 53 vs 58, 128->64 transposed 49 vs 56 -- but 128->256 52 vs 43, 256->512 48 vs 43: every 64 x 64
@@ -958,23 +960,15 @@ static bool plan_line(const ir2rgb_conv_desc *d, WgradLineGeom *g, LineForm *for
     if (d->pad_mode == 1 && (d->pad_h >= d->Hin || d->pad_w >= d->Win)) return false;
     *form = k3s2 ? LINE_3X3S2 : k7x1 ? (d->stride_h == 1 ? LINE_COL7 : LINE_7X1) : k1x7 ? LINE_1X7 : d->stride_h == 2 ? LINE_COL4S2 : LINE_4X1;
     *g = WgradLineGeom{};
-    orient_uv(d, g);
-    const long Q = (long)d->N * g->Hq * g->Wq, Pv = (long)d->N * g->Hv * g->Wv;
-    if (Q * g->Ca * 2 >= (1L << 31) || Pv * g->Cb * 2 >= (1L << 31)) return false;
+    uv.put(g);
     g->stride_y = d->stride_h; g->pad_mode = d->pad_mode; g->dy0 = -d->pad_h; g->dx0 = -d->pad_w;
     g->segs = (g->Wq + 63) / 64;
     const long ksteps = (long)d->N * g->Hq * g->segs;
     if (ksteps >= (1L << 30)) return false;
     g->ksteps = (int)ksteps;
-    // one workgroup per CU: ~256 workgroups, at least 8 K-steps each, no empty split
-    const long tiles = (long)(g->Ca / 64) * (g->Cb / 64);
-    long ks = (256 + tiles - 1) / tiles;
-    if (ks > ksteps / 8) ks = ksteps / 8;
-    if (ks < 1) ks = 1;
-    if (ks > 256) ks = 256;
-    g->per = (int)((ksteps + ks - 1) / ks);
+    const int ks = split_per_cu(uv, ksteps);
+    g->per = (int)((ksteps + ks - 1) / ks);                  // ... and no empty split
     g->ksplit = (int)((ksteps + g->per - 1) / g->per);
-    g->u_bytes = (unsigned)(Q * g->Ca * 2); g->v_bytes = (unsigned)(Pv * g->Cb * 2);
     return true;
 }
 
@@ -995,30 +989,31 @@ static void launch_line(LineForm form, const WgradLineGeom &g, const uint16_t *U
 enum WgradKernel { WGRAD_ONETAP, WGRAD_NINE, WGRAD_LINE };
 struct WgradRoute {
     WgradKernel kernel;
+    WgradUV uv;                 // orientation and extents, whichever kernel runs
     WgradGeom g;                // WGRAD_ONETAP
     Wgrad9Geom g9;              // WGRAD_NINE
     WgradLineGeom gl;           // WGRAD_LINE, in the form `line`
     LineForm line;
-    int Ca, Cb, ksplit;         // of the kernel that runs
-    long workspace_elems;       // ksplit slabs of taps * Ca * Cb floats; the unsplit nine-tap form writes dw itself (4: never empty)
+    int ksplit() const { return kernel == WGRAD_NINE ? g9.ksplit : kernel == WGRAD_LINE ? gl.ksplit : g.ksplit; }
+    // ksplit slabs of taps * Ca * Cb floats; the unsplit nine-tap form writes dw itself (4: never empty)
+    long workspace_elems(const ir2rgb_conv_desc *d) const {
+        return kernel == WGRAD_NINE && ksplit() == 1 ? 4 : (long)ksplit() * d->kh * d->kw * uv.Ca * uv.Cb;
+    }
 };
 
 static int wgrad_route(const ir2rgb_conv_desc *d, bool accumulate, WgradRoute *r) {
-    const int rc = plan(d, &r->g);
+    const int rc = plan(d, &r->uv, &r->g);
     if (rc) return rc;
     // accumulate mode (a parameter used several times per pass: the discriminators) sums in the finish pass; the nine-tap
     // kernel's direct-write form has no such pass, so those layers take the one-tap kernel
-    if (!accumulate && plan9(d, &r->g9)) { r->kernel = WGRAD_NINE; r->Ca = r->g9.Ca; r->Cb = r->g9.Cb; r->ksplit = r->g9.ksplit; }
-    else if (plan_line(d, &r->gl, &r->line)) { r->kernel = WGRAD_LINE; r->Ca = r->gl.Ca; r->Cb = r->gl.Cb; r->ksplit = r->gl.ksplit; }
-    else { r->kernel = WGRAD_ONETAP; r->Ca = r->g.Ca; r->Cb = r->g.Cb; r->ksplit = r->g.ksplit; }
-    r->workspace_elems = r->kernel == WGRAD_NINE && r->ksplit == 1 ? 4 : (long)r->ksplit * d->kh * d->kw * r->Ca * r->Cb;
+    r->kernel = !accumulate && plan9(d, r->uv, &r->g9) ? WGRAD_NINE : plan_line(d, r->uv, &r->gl, &r->line) ? WGRAD_LINE : WGRAD_ONETAP;
     return IR2RGB_OK;
 }
 
 static long wgrad_workspace(const ir2rgb_conv_desc *d, bool accumulate) {
     WgradRoute r;
     const int rc = wgrad_route(d, accumulate, &r);
-    return rc ? rc : r.workspace_elems;
+    return rc ? rc : r.workspace_elems(d);
 }
 extern "C" long ir2rgb_conv2d_wgrad_workspace_elems(const ir2rgb_conv_desc *d) { return wgrad_workspace(d, false); }
 extern "C" long ir2rgb_conv2d_wgrad_acc_workspace_elems(const ir2rgb_conv_desc *d) { return wgrad_workspace(d, true); }
@@ -1031,12 +1026,12 @@ static int wgrad_impl(const ir2rgb_conv_desc *d, const void *x, const void *gy, 
     if ((((uintptr_t)x | (uintptr_t)gy) & 15) || !dw || !workspace) return IR2RGB_EALIGN;
     if (r.kernel == WGRAD_NINE && (((uintptr_t)dw | (uintptr_t)workspace) & 15)) return IR2RGB_EALIGN;
     hipStream_t s = as_stream(stream);
-    const int ntaps = d->kh * d->kw;
+    const int ntaps = d->kh * d->kw, Ca = r.uv.Ca, Cb = r.uv.Cb, ksplit = r.ksplit();
     const uint16_t *U = (const uint16_t *)(d->transposed ? x : gy), *V = (const uint16_t *)(d->transposed ? gy : x);
     with_dtype(d->dtype, [&](auto dt) {
         if (r.kernel == WGRAD_NINE) {
-            const unsigned grid9 = (unsigned)((long)r.ksplit * (r.Ca / 64) * (r.Cb / 64));
-            conv_wgrad3x3_kernel<dt.value><<<grid9, 512, 0, s>>>(U, V, r.ksplit > 1 ? workspace : dw, r.g9);
+            const unsigned grid9 = (unsigned)((long)ksplit * (Ca / 64) * (Cb / 64));
+            conv_wgrad3x3_kernel<dt.value><<<grid9, 512, 0, s>>>(U, V, ksplit > 1 ? workspace : dw, r.g9);
         } else if (r.kernel == WGRAD_LINE) {    // k x 1 / 1 x k layers: all taps of a 64 x 64 tile per workgroup
             launch_line<dt.value>(r.line, r.gl, U, V, workspace, s);
         } else {
@@ -1046,10 +1041,10 @@ static int wgrad_impl(const ir2rgb_conv_desc *d, const void *x, const void *gy, 
         }
     });
     if (r.kernel != WGRAD_NINE) {
-        launch_wgrad_finish(workspace, dw, r.Ca, r.Cb, ntaps, r.ksplit, s, acc);
-    } else if (r.ksplit > 1) {
-        const long n4 = (long)ntaps * r.Ca * r.Cb / 4;
-        wgrad_sum_kernel<<<stream_grid(n4, 256), 256, 0, s>>>((const float4 *)workspace, (float4 *)dw, n4, r.ksplit);
+        launch_wgrad_finish(workspace, dw, Ca, Cb, ntaps, ksplit, s, acc);
+    } else if (ksplit > 1) {
+        const long n4 = (long)ntaps * Ca * Cb / 4;
+        wgrad_sum_kernel<<<stream_grid(n4, 256), 256, 0, s>>>((const float4 *)workspace, (float4 *)dw, n4, ksplit);
     }
     return ir2rgb_launch_status();
 }

@@ -146,9 +146,9 @@ def replay_wgrad(dev, rec, mode=None):
         return _ranged(dev, rec, mode, "wgrad_case")
     d = rec["desc"]
     g = gen(rec)
-    x = R.draw((d["N"], d["Cin"], d["Hin"], d["Win"]), g)
-    gy = R.draw((d["N"], d["Cout"], d["Hout"], d["Wout"]), g)
-    base = torch.randn(R.weight_shape(d), generator=g)
+    x = hand("in", "x", R.draw((d["N"], d["Cin"], d["Hin"], d["Win"]), g))
+    gy = hand("in", "gy", R.draw((d["N"], d["Cout"], d["Hout"], d["Wout"]), g))
+    base = hand("in", "base", torch.randn(R.weight_shape(d), generator=g))
     ref, S = R.wgrad(d, x, gy)
     ref, S = ref.numpy(), S.numpy()
     chain = B.chain_wgrad(d)
@@ -165,6 +165,8 @@ def replay_wgrad(dev, rec, mode=None):
         C.conv2d_wgrad(desc, xg, gg, out=acc2, accumulate=True)
         torch.cuda.synchronize()
         assert torch.equal(dw, dw2) and torch.equal(acc, acc2), f"{fmt}: weight gradient not bit-reproducible"
+        hand("out", f"{fmt} dw", dw)
+        hand("out", f"{fmt} acc", acc)
         ok, ratio, i, over = B.check(dw.double().cpu().numpy(), ref, S, "f32", chain)
         assert ok, f"{fmt}: {over} weight-gradient elements over the bound (worst {ratio:.3g} at {np.unravel_index(i, ref.shape)})"
         bd = base.double().numpy()
