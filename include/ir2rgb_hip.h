@@ -608,6 +608,42 @@ int ir2rgb_frame_scale_u8(const uint8_t *src, void *dst, uint8_t *workspace, lon
                           int Ws, int new_h, int new_w, int crop_y, int crop_x, int Hc, int Wc, int flip, int dst_f32,
                           void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Training snapshots (visuals.hip): the panels the reference's util.save_all_tensors (util/util.py:13-104) makes
+ * on the host, composed on the device.  Every source is fp32 [C][H][W], contiguous; out is uint8 [n][H][W][3],
+ * one panel per slot, a one-channel panel written to all three bytes.  Kinds:
+ *   IR2RGB_PANEL_IMAGE_NORM  C in {1, 3}: trunc(clip((x + 1) / 2 * 255, 0, 255))      util.tensor2im(x)
+ *   IR2RGB_PANEL_IMAGE_UNIT  C in {1, 3}: trunc(clip(x * 255, 0, 255))                util.tensor2im(x, normalize=False)
+ *   IR2RGB_PANEL_FLOW        C = 2: util.tensor2flow's coding, (u, v) -> HSV -> RGB with
+ *       mag = sqrt(u^2 + v^2), [mn, mx] = its range over the panel (NaN magnitudes ignored),
+ *       H = trunc(atan2(v, u) in [0, 2 pi) * 90 / pi) mod 180, S = 255,
+ *       V = trunc((mag - mn) * 255 / (mx - mn)); 0 everywhere when mx == mn, 0 for a NaN magnitude,
+ *       and the integer 8-bit HSV -> RGB with hue in [0, 180): i = H / 30, r = H % 30,
+ *       t = (2 V r + 30) / 60, q = (2 V (30 - r) + 30) / 60, p = 0, sectors (V,t,p) (q,V,p) (p,V,t) (p,q,V) (t,p,V) (V,p,q).
+ *   fp32 with correctly rounded operations in the order written (NaN -> 0 in all three kinds); results are
+ *   bit-reproducible.
+ * panels is a HOST array; it is copied into the launch's arguments, nothing is uploaded.  The workspace is the
+ * caller's: ir2rgb_visuals_workspace_bytes(number of FLOW panels, H, W) bytes of fp32 (min, max) rows (negative
+ * for invalid sizes), fully written before it is read; it may be NULL when no panel is a FLOW panel.  Two
+ * launches with a FLOW panel, one without.  16-byte aligned sources with W % 4 == 0 and a 4-byte aligned out take
+ * 16-byte loads and dword stores, everything else the scalar form.  No buffer may alias out or the workspace.
+ * IR2RGB_EINVAL: NULL panels / out / source, n outside [1, 16], H or W < 1, H * W * 3 > 2^31 - 1, an unknown
+ * kind, a channel count that does not fit the kind, a NULL workspace with a FLOW panel; IR2RGB_EALIGN: a source
+ * or the workspace off a 4-byte boundary.  Both before any launch.
+ * ------------------------------------------------------------------------------------------ */
+#define IR2RGB_VISUALS_MAX_PANELS 16
+#define IR2RGB_PANEL_IMAGE_NORM 0
+#define IR2RGB_PANEL_IMAGE_UNIT 1
+#define IR2RGB_PANEL_FLOW 2
+typedef struct ir2rgb_panel {
+    const float *src;
+    int kind;
+    int channels;
+} ir2rgb_panel;
+
+long ir2rgb_visuals_workspace_bytes(int n_flow_panels, int H, int W);
+int ir2rgb_visuals_u8(const ir2rgb_panel *panels, int n, int H, int W, float *workspace, uint8_t *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

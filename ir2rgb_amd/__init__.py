@@ -7,7 +7,7 @@ first use and its absence is an error (there is no CPU fallback).
 __version__ = "0.1.0"
 
 __all__ = ["VideoTranslator", "VideoScore", "video_metrics", "ssim_reference", "FrameScaler", "img_params", "resample_coeffs",
-           "resize_reference", "TrainingSchedule", "LossLog", "fit"]
+           "resize_reference", "TrainingSchedule", "LossLog", "fit", "Snapshots", "to_u8_reference", "flow_to_rgb_reference"]
 
 
 def __getattr__(name):
@@ -21,6 +21,9 @@ def __getattr__(name):
     if name in ("FrameScaler", "img_params", "resample_coeffs", "resize_reference"):
         from . import transform
         return getattr(transform, name)
+    if name in ("Snapshots", "to_u8_reference", "flow_to_rgb_reference"):
+        from . import visuals
+        return getattr(visuals, name)
     if name == "TrainingSchedule":
         from .schedule import TrainingSchedule
         return TrainingSchedule

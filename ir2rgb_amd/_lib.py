@@ -66,6 +66,17 @@ class LossLogState(ctypes.Structure):
                 ("count", ctypes.c_longlong)]
 
 
+VISUALS_MAX_PANELS = 16
+PANEL_IMAGE_NORM, PANEL_IMAGE_UNIT, PANEL_FLOW = 0, 1, 2
+
+
+class Panel(ctypes.Structure):
+    """ir2rgb_panel of include/ir2rgb_hip.h."""
+    _fields_ = [("src", c_void_p), ("kind", c_int), ("channels", c_int)]
+
+
+_ppanel = ctypes.POINTER(Panel)
+
 # name -> (restype, argtypes)
 PROTOTYPES = {
     "ir2rgb_version": (ctypes.c_char_p, []),
@@ -136,6 +147,8 @@ PROTOTYPES = {
     "ir2rgb_video_metrics_u8": (c_int, [P] * 5 + [c_long] + [c_int] * 3 + [P]),
     "ir2rgb_frame_scale_workspace_bytes": (c_long, [c_int] * 10),
     "ir2rgb_frame_scale_u8": (c_int, [P, P, P, c_long, P, P, c_int, P, P, c_int] + [c_int] * 12 + [P]),
+    "ir2rgb_visuals_workspace_bytes": (c_long, [c_int] * 3),
+    "ir2rgb_visuals_u8": (c_int, [_ppanel, c_int, c_int, c_int, P, P, P]),
 }
 
 _lib = None

@@ -17,17 +17,12 @@
 //   to 8 bit    trunc(clip((x + 1) / 2 * 255, 0, 255))       numpy: ((x + 1) / 2.0 * 255.0).clip(0, 255).astype(uint8)
 //   pooling     the statement order of avgpool3s2_fwd_kernel (pointwise.hip): rows outer, columns inner, one division
 #include "common.h"
+#include "u8.h"         // to_u8
 
 namespace {
 
 __device__ __forceinline__ float normalise_u8(unsigned v) {
     return __fdiv_rn(__fsub_rn(__fdiv_rn((float)v, 255.f), 0.5f), 0.5f);
-}
-
-__device__ __forceinline__ unsigned to_u8(float x) {
-    float v = __fmul_rn(__fdiv_rn(__fadd_rn(x, 1.f), 2.f), 255.f);
-    v = fminf(fmaxf(v, 0.f), 255.f);        // (NaN -> 0)
-    return (unsigned)(int)v;                 // truncation toward zero, as astype(uint8) on a value in [0, 255]
 }
 
 // history [T][plane] -> slots 1..T-1 move to 0..T-2 at element(s) e, the newest slot receives v

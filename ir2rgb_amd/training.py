@@ -2,9 +2,10 @@
 
 What happens between windows and between epochs is ``ir2rgb_amd.schedule.TrainingSchedule``'s host arithmetic; the loss
 record is ``ir2rgb_amd.losslog.LossLog``'s, on the device.  Nothing inside the loop synchronises with the GPU except
-``LossLog.read`` every ``print_freq`` sequences and the checkpoints.  Not carried over: the visualiser and its HTML
-output, ``sparse_D``, ``pool_size``, ``max_t_step``, and optimizer state in checkpoints (the reference saves none either:
-a resumed run restarts Adam's moments, models/utils.py:6-9).
+``LossLog.read`` every ``print_freq`` sequences and the checkpoints; the visualiser (``ir2rgb_amd.visuals.Snapshots``)
+composes its panels on the device and writes its files one snapshot late, when the copy has long finished.  Not carried
+over: ``sparse_D``, ``pool_size``, ``max_t_step``, and optimizer state in checkpoints (the reference saves none either: a
+resumed run restarts Adam's moments, models/utils.py:6-9).
 """
 import time
 
@@ -31,7 +32,14 @@ def format_errors(epoch, i, errors, t):
     return message
 
 
-def fit(trainer, sequences, schedule, save_dir=None, log=print, loss_log=None, continue_train=False, events=None):
+def _in_frame_history(trainer, t):
+    """Is ``t`` a view of one of the trainer's preallocated ``FrameHistory`` buffers (which later pushes overwrite)?"""
+    bufs = [h.buf for h in trainer.hist.values() if h.buf is not None]
+    return any(b.untyped_storage().data_ptr() == t.untyped_storage().data_ptr() for b in bufs)
+
+
+def fit(trainer, sequences, schedule, save_dir=None, log=print, loss_log=None, continue_train=False, events=None,
+        snapshots=None):
     """Trains ``trainer`` through ``schedule``'s epochs.
 
     ``sequences``: ``len()``, ``seq_len_max`` and ``sequence(index, n_frames_total) -> (ir, rgb)``, device tensors
@@ -39,7 +47,10 @@ def fit(trainer, sequences, schedule, save_dir=None, log=print, loss_log=None, c
     ``frames.scaled_sequence``).  ``save_dir``: where ``checkpoint.save_trainer`` writes at the schedule's save points
     (None: nowhere).  ``loss_log``: a ``LossLog`` (default: one over every term of the trainer).  ``continue_train``:
     resume from ``save_dir``'s ``latest`` networks and ``iter.txt`` (models.py:62-78).  ``events``: a list that receives
-    the schedule's ("print" | "save_latest" | "save_epoch", ...) tuples as they happen.
+    the schedule's ("print" | "save_latest" | "save_epoch", ...) tuples as they happen.  ``snapshots``: a
+    ``visuals.Snapshots``; after every sequence that brings ``total_steps`` to a multiple of its ``freq``
+    (train_vid2vid.py:46, :131-136) it draws the last window and the sequence's first generated frame.  Without one the loop
+    issues no launch and makes no allocation for it.
     -> (epoch, epoch_iter, total_steps) as the loop leaves them."""
     n = len(sequences)
     if n < 1:
@@ -99,10 +110,18 @@ def fit(trainer, sequences, schedule, save_dir=None, log=print, loss_log=None, c
             slicer = WindowSlicer(ir.reshape(b, t * c, h, w), rgb.reshape(b, t * rgb.shape[2], h, w), tG, n_frames_load,
                                   opt["input_nc"], opt["output_nc"])
             trainer.reset_sequence()
-            for input_A, input_B in slicer:
+            save_fake = snapshots is not None and snapshots.due(st.total_steps + 1)      # (schedule.step: one per sequence)
+            fake_B_first = None
+            for i, (input_A, input_B) in enumerate(slicer):
                 loss_log.push(trainer.train_window(input_A, input_B), trainer.loss_scaler)
+                if save_fake and i == 0:       # the first generated image of this sequence (train_vid2vid.py:113-114)
+                    fake_B_first = trainer.last_outputs[0][0, 0]
+                    if _in_frame_history(trainer, fake_B_first):
+                        fake_B_first = fake_B_first.clone()
             evs, over = schedule.step(st)
             emit(evs)
+            if fake_B_first is not None:        # queued before the next window: FlowNet2's next replay overwrites flow_ref
+                snapshots.take(trainer, st.epoch, fake_B_first)
             if over:
                 break
         log(f"End of epoch {st.epoch} / {schedule.last_epoch} \t Time Taken: {time.time() - epoch_start} sec")
@@ -118,4 +137,6 @@ def fit(trainer, sequences, schedule, save_dir=None, log=print, loss_log=None, c
         if changes.get("update_fixed_params"):
             trainer.update_fixed_params()
             log("------------ Now finetuning all scales -----------")
+    if snapshots is not None:
+        snapshots.flush()
     return st.epoch, st.epoch_iter, st.total_steps

@@ -178,6 +178,7 @@ class Vid2VidTrainer:
         self.schedule = self._batch_state = None    # attach_schedule()
         self.old_lr = o["lr"]            # the rate without any TTUR factor (base_model.py:98-99, :105)
         self.last_outputs = None         # (fake_B, fake_B_raw, flow, weight) of the last train_window
+        self.last_inputs = None          # (real_A, real_B, flow_ref, conf_ref) of the last train_window
         self.vgg_loss = None
         if not o["no_vgg"]:
             from .vgg import VGGLoss
@@ -754,7 +755,8 @@ class Vid2VidTrainer:
     def train_window(self, input_A, input_B):
         """train_vid2vid.py:54-111 for one window.  Returns a dict of detached scalar losses: the totals ``G``, ``D``,
         ``D_T{s}`` and every term under the reference's names (``G_GAN`` ... ``W``; temporal ones with the scale
-        appended, ``G_T_GAN0`` ...).  ``self.last_outputs`` keeps (fake_B, fake_B_raw, flow, weight), detached."""
+        appended, ``G_T_GAN0`` ...).  ``self.last_outputs`` keeps (fake_B, fake_B_raw, flow, weight), detached,
+        ``self.last_inputs`` (real_A, real_B, flow_ref, conf_ref): what ``ir2rgb_amd.visuals`` draws a snapshot from."""
         fake_prev_last = self.fake_B_prev
         drop_grad_dsts()                    # (gradient destinations of the previous window's discriminator outputs)
         # The reference flows depend on real frames only (train_vid2vid.py:62-65 computes them after the generator, from
@@ -819,6 +821,7 @@ class Vid2VidTrainer:
         self.backward_passes(loss_G, loss_D, loss_D_T)
         self.optimizer_steps(len(loss_D_T))
         self.last_outputs = tuple(t.detach() for t in (fake_B, fake_B_raw, flow, weight))
+        self.last_inputs = tuple(t.detach() for t in (real_A, real_B, flow_ref, conf_ref))     # (references: no copy)
         out = {"G": loss_G.detach(), "D": loss_D.detach()}
         out.update({f"D_T{s}": l.detach() for s, l in enumerate(loss_D_T)})
         out.update({k: v.detach() for k, v in L.items()})
