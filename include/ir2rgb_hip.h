@@ -583,6 +583,30 @@ int ir2rgb_video_metrics_u8(const uint8_t *orig, const uint8_t *pred, const doub
                             long workspace_bytes, int N, int H, int W, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Temporal consistency (warp_error.hip): the warp error of consecutive frames, the trainer's G_Warp term
+ * (reference models/discriminator.py:137-138, MaskedL1Loss, Model.resample) as a score, in fp64 on the device.
+ * prev, cur: uint8 [N][H][W][3]; flow: fp32 [N][2][H][W], x then y, in pixels, from cur to prev; weight: fp32
+ * [N][1][H][W] or NULL (= 1).  N in [1, 65535], H, W >= 2, 3*H*W < 2^31.  For every pair n and pixel (y, x)
+ *   gx = (-1 + x * (2 / (W - 1))) + fx / ((W - 1) / 2),  ix = ((gx + 1) * W - 1) * 0.5 clamped to [0, W - 1]
+ *   x0 = floor(ix), x1 = min(x0 + 1, W - 1), ax = ix - x0; likewise y0, y1, ay       (get_grid + grid_sample(
+ *                                                    align_corners=False, padding_mode="border"), as warp_blend)
+ *   w_c = (1-ay)(1-ax) prev[y0][x0][c] + (1-ay) ax prev[y0][x1][c] + ay (1-ax) prev[y1][x0][c] + ay ax prev[y1][x1][c]
+ *   d_c = cur[y][x][c] - w_c;  S1 = sum m |d_c|,  S2 = sum m d_c^2,  SC = sum m
+ * and out[n] = {warp_l1 = S1 / (127.5 * 3 * H * W), warp_mse = S2 / (255^2 * 3 * SC), coverage = SC / (H * W)}.
+ * No special cases: SC = 0 gives NaN; a NaN flow vector or weight stays in its own pair's row; an infinite flow
+ * lands on the border.  No address leaves the frame whatever flow holds.  All sums have a fixed order: results
+ * are bit-reproducible and pairs never mix.
+ * The workspace is the caller's: ir2rgb_warp_error_workspace_bytes(N, H, W) bytes (negative for invalid sizes),
+ * fully written before it is read.  Two launches.  W % 4 == 0 with flow and weight on 16-byte and cur on 4-byte
+ * boundaries takes 16-byte loads, everything else the scalar form of the same code.
+ * IR2RGB_EINVAL: NULL prev / cur / flow / out / workspace, sizes out of range, workspace too small;
+ * IR2RGB_EALIGN: out or workspace off an 8-byte, flow or weight off a 4-byte boundary.  Both before any launch.
+ * ------------------------------------------------------------------------------------------ */
+long ir2rgb_warp_error_workspace_bytes(int N, int H, int W);
+int ir2rgb_warp_error_u8(const uint8_t *prev, const uint8_t *cur, const float *flow, const float *weight, double *out,
+                         void *workspace, long workspace_bytes, int N, int H, int W, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Frame scaling (frame_scale.hip): the loader's Image.resize(..., BICUBIC), crop and flip (reference
  * data/transform.py:64-113) on uint8 frames, equal to Pillow's 8-bit resampler byte for byte.
  *   src [N][Hs][Ws][C] uint8, C in {1, 3}  --scale-->  [new_h][new_w]  --crop-->  rows [crop_y, crop_y + Hc),

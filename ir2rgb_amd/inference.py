@@ -350,22 +350,42 @@ class VideoTranslator:
             if out is not None:
                 yield out
 
-    def evaluate(self, frames, targets, real_rgb=None, data_range="reference"):
+    def evaluate(self, frames, targets, real_rgb=None, data_range="reference", temporal=None):
         """``translate(frames, real_rgb)`` scored against a ground-truth RGB track (reference scripts/ssim_metric.py):
         output ``k`` is compared with ``targets[tG-1+k]`` -- ``targets`` is indexed like ``frames``, uint8 [H,W,3] each
         (camera-size ones are scaled like the frames), moved to the device if needed.
         -> ``ir2rgb_amd.metrics.VideoScore``; its ``result()`` is the only host
         synchronisation.  The scores are enqueued on the current stream after each step; the captured graph is the one
-        ``translate`` replays.  ``data_range``: see ``ir2rgb_amd.metrics.video_metrics``."""
+        ``translate`` replays.  ``data_range``: see ``ir2rgb_amd.metrics.video_metrics``.
+
+        ``temporal``: a callable ``(cur, prev) -> (flow, conf)`` on normalised fp32 [n,3,H,W] frames -- an
+        ``ir2rgb_amd.flownet.FlowNet`` or any stand-in.  With it every output ``k >= 1`` is also scored for flicker: the flow
+        of the scaled targets, ``temporal(norm(T_k), norm(T_k-1))`` (the trainer's ``flowNet(real_B[:, 1:], real_B[:, :-1])``),
+        gives ``warp_error(P_k-1, P_k, flow, conf)`` for the outputs and ``warp_error(T_k-1, T_k, flow, conf)`` for the
+        targets as the baseline (``VideoScore.add_pair``; ``result()`` then has ``warp_l1``, ``warp_mse``, ``truth_warp_l1``,
+        ``truth_warp_mse``, ``coverage``, ``pairs`` and ``per_pair``).  All of it is enqueued on the current stream after
+        the step; None (default) scores frame by frame only."""
         from .metrics import VideoScore
         if not hasattr(targets, "__getitem__"):
             targets = list(targets)
+        if temporal is not None and not callable(temporal):
+            raise TypeError(f"evaluate: temporal is a callable (cur, prev) -> (flow, conf), got {type(temporal)}")
         score = VideoScore(data_range)
+        prev = None                                                     # (output, target) of the step before
         for k, out in enumerate(self.translate(frames, real_rgb)):
             i = self.seq.output_frame(k)
             if i >= len(targets):
                 raise ValueError(f"evaluate: output {k} is scored against targets[{i}], {len(targets)} targets given")
-            score.add(self._rgb_frame(targets[i], "evaluate(targets)"), out)
+            target = self._rgb_frame(targets[i], "evaluate(targets)")
+            score.add(target, out)
+            if temporal is not None:
+                if prev is not None:
+                    with torch.no_grad():
+                        flow, conf = temporal(normalise_u8(target).unsqueeze(0).contiguous(),
+                                              normalise_u8(prev[1]).unsqueeze(0).contiguous())
+                    score.add_pair(prev[0].unsqueeze(0), out.unsqueeze(0), prev[1].unsqueeze(0), target.unsqueeze(0),
+                                   flow.float().contiguous(), conf.float().contiguous())
+                prev = (out, target)
         return score
 
     def inference(self, input_A, input_B=None):

@@ -26,6 +26,40 @@ The definition, per frame (H, W >= 7):
 scikit-image filters with reflected borders and crops 3 pixels afterwards: the cropped region never sees a border, so
 nothing is padded here.  There are no special cases: R <= 0, flat images and 0/0 behave as IEEE arithmetic does in NumPy,
 so an all-black pair scores NaN.
+
+Temporal consistency: the warp error of consecutive frames, the trainer's ``G_Warp`` term as a score
+(models/discriminator.py:137-138, ``MaskedL1Loss``, ``Model.resample`` in base_model.py:129-136; csrc/warp_error.hip):
+
+* ``warp_error(prev_u8, cur_u8, flow, weight=None)``   -> fp64 device tensor [N,3]: warp_l1, warp_mse, coverage per pair
+* ``warp_error_reference(...)``                          the same definition in plain torch fp64 on any device
+* ``warp_bound(H, W, flow, weight)``                     how far two fp64 evaluations of the definition may lie apart, [N,3]
+* ``VideoScore.add_pair``                                per-pair rows of a prediction and of the ground truth beside it
+
+A *pair* is two consecutive frames of one track, ``prev`` and ``cur``, uint8 [H,W,3] with H, W >= 2, with a flow ``f``
+(fp32 [2,H,W], x then y, in pixels, from ``cur`` to ``prev``) and an optional weight ``m`` (fp32 [1,H,W]; absent means 1).
+Everything is in fp64; bytes and fp32 inputs convert exactly.  For pixel (y, x):
+
+    gx = (-1 + x*(2/(W-1))) + fx/((W-1)/2)
+    ix = ((gx + 1)*W - 1)*0.5, then clamped to [0, W-1]            likewise iy from y, fy and H
+
+which is ``get_grid`` (an align_corners=True lattice) fed to ``grid_sample(align_corners=False, padding_mode="border")``:
+the reference's mismatch, which ``warp_blend`` (csrc/heads.hip) and ``vid2vid.resample`` reproduce too.  It is kept on
+purpose: the score is the trainer's G_Warp, not a cleaned-up cousin.  With x0 = floor(ix), x1 = min(x0+1, W-1),
+ax = ix - x0, and likewise in y:
+
+    w_c = (1-ay)(1-ax) prev[y0,x0,c] + (1-ay) ax prev[y0,x1,c] + ay (1-ax) prev[y1,x0,c] + ay ax prev[y1,x1,c]
+    d_c = cur[y,x,c] - w_c                                           (byte units)
+    S1 = sum m |d_c|     S2 = sum m d_c**2     SC = sum m             (S1, S2 over pixels and channels, SC over pixels)
+
+    warp_l1  = S1 / (127.5 * 3 * H * W)     masked_l1(fake_B, resample(fake_B_prev, flow_ref), conf_ref) on the normalised
+                                            frames = G_Warp / lambda_T
+    warp_mse = S2 / (255**2 * 3 * SC)       masked mean squared error in [0,1] image units (the usual "warping error")
+    coverage = SC / (H * W)
+
+There are no special cases: SC = 0 gives 0/0 = NaN as IEEE does; a NaN flow vector or weight stays in the sums of its own
+pair (the clamp keeps a NaN, so ax / ay carry it) and leaves every other pair of the batch bit-unchanged; an infinite flow
+vector lands on the border like any large one.  No address leaves the frame: indices are clamped as integers, a NaN
+coordinate maps to index 0.
 """
 import math
 
@@ -33,7 +67,8 @@ import torch
 
 from . import _lib
 
-__all__ = ["video_metrics", "ssim_reference", "VideoScore", "ssim_bound", "l2_bound", "RANGE_BOUND"]
+__all__ = ["video_metrics", "ssim_reference", "VideoScore", "ssim_bound", "l2_bound", "RANGE_BOUND",
+           "warp_error", "warp_error_reference", "warp_bound"]
 
 # ---------------------------------------------------------------------------------------------
 # The bound between two fp64 evaluations of the definition (written down before any kernel ran).
@@ -70,6 +105,62 @@ def ssim_bound(R):
 def l2_bound(H, W):
     """Largest difference between two fp64 evaluations of ``l2`` on an H x W frame."""
     return 64 * U * math.sqrt(H * W)
+
+
+# ---------------------------------------------------------------------------------------------
+# The bound between two fp64 evaluations of the warp error (written down before the kernel first ran).
+#
+# Coordinate, one evaluation, with F = |fx| * 2 / (W - 1) (the flow in lattice units; (W - 1) / 2 is exact):
+#   a = x * (2/(W-1))   the step and the product round once each, a <= 2                       -> <= 4u
+#   b = -1 + a          |b| <= 1                                                                -> <= 5u
+#   c = fx / ((W-1)/2)  one division                                                           -> <= u F
+#   gx = b + c          |gx| <= 1 + F                                                          -> <= 6u + 2u F
+#   e = gx + 1          |e| <= 2 + F                                                           -> <= 8u + 3u F
+#   g = e * W                                                                                  -> <= W (10u + 4u F)
+#   ix = (g - 1) * 0.5  the halving is exact                                                   -> <= W (6u + 2.5u F)
+#                                                                                               = 6u W + 5u |fx| W/(W-1)
+#   The clamp does not enlarge it.  A linspace lattice (torch's symmetric evaluation, <= 3u on b) stays inside the same
+#   figure.  Two evaluations therefore lie within  Ex = 16u (W + max|fx| W/(W-1))  of each other, Ey likewise with H, fy.
+# Warp: w_c is continuous in (ix, iy) -- across integer coordinates, where the neighbour that changes has weight 0, and
+#   across the clamp -- and piecewise bilinear between bytes, so its slope is at most 255 per pixel along either axis:
+#   |dw| <= 255 (Ex + Ey).  Its own arithmetic (four weights of two factors, four products, three additions on a convex
+#   combination of values <= 255; on normalised frames the conversions (v/255 - 0.5)/0.5 and the products a*m, b*m of
+#   masked_l1 instead) stays below 32u * 255 per evaluation.  Per channel:
+#       D = 255 (Ex + Ey) + 64u * 255                                                          bound on |d_c - d_c'|
+# Sums, with A = sum |m| over the pixels and n = 3 H W terms; a sum of n rounded terms taken in ANY order is within
+#   (n - 1) u sum|terms| of the exact one, each term m|d| <= 255 |m| (m d^2 <= 255^2 |m|) carries two more roundings:
+#       dS1 = 3 A D + (n + 2) u * 3 * 255 A
+#       dS2 = 3 A (2 * 255 D + D^2) + (n + 3) u * 3 * 255^2 A
+#       dSC = H W u A
+# Columns (one division each; r = A / |SC| is 1 for weights >= 0, so that S2 / (255^2 * 3 |SC|) <= r):
+#       warp_l1   (dS1 + u * 3 * 255 A) / (127.5 * 3 H W)
+#       warp_mse  dS2 / (255^2 * 3 |SC|) + r dSC / |SC| + 3u r
+#       coverage  (dSC + u A) / (H W)
+# At 512x1024 with a flow of a few pixels: Ex ~ 2e-12, D ~ 1e-9 bytes, and the sums' (n u ~ 1.7e-10 relative) term leads;
+# at 16x32 the coordinate term leads at ~1e-13 relative.  A wrong align_corners, padding, flow order or sign, a dropped
+# mask or the warp applied to the wrong frame moves the sums by more than 6e-5 relative (tests/test_warp_error_cpu.py).
+# A non-finite flow or weight makes the bound non-finite too: such rows are compared as NaN patterns, not by distance.
+# ---------------------------------------------------------------------------------------------
+def warp_bound(H, W, flow, weight=None):
+    """Largest difference between two fp64 evaluations of ``warp_error`` on these inputs: fp64 [N,3] for the columns
+    warp_l1, warp_mse, coverage.  ``flow`` [N,2,H,W] (or [2,H,W]), ``weight`` [N,1,H,W] (or [1,H,W]) or None."""
+    flow = flow.unsqueeze(0) if flow.dim() == 3 else flow
+    N = flow.shape[0]
+    f = flow.to(torch.float64).abs().reshape(N, 2, -1).amax(-1)
+    if weight is None:
+        A = SC = torch.full((N,), float(H * W), dtype=torch.float64, device=flow.device)
+    else:
+        m = weight.to(torch.float64).reshape(N, -1)
+        A, SC = m.abs().sum(-1), m.sum(-1).abs()
+    Ex, Ey = 16 * U * (W + f[:, 0] * W / (W - 1)), 16 * U * (H + f[:, 1] * H / (H - 1))
+    D = 255 * (Ex + Ey) + 64 * U * 255
+    n = 3 * H * W
+    dS1 = 3 * A * D + (n + 2) * U * 3 * 255 * A
+    dS2 = 3 * A * (2 * 255 * D + D * D) + (n + 3) * U * 3 * 255 ** 2 * A
+    dSC = H * W * U * A
+    r = A / SC
+    return torch.stack([(dS1 + U * 3 * 255 * A) / (127.5 * n), dS2 / (255 ** 2 * 3 * SC) + r * dSC / SC + 3 * U * r,
+                        (dSC + U * A) / (H * W)], 1)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -145,6 +236,73 @@ def ssim_reference(orig_u8, pred_u8, data_range="reference"):
     return torch.stack(rows)
 
 
+def _pairs(prev_u8, cur_u8, flow, weight, what):
+    """-> prev, cur uint8 [N,H,W,3], flow fp32 [N,2,H,W], weight fp32 [N,1,H,W] or None; anything else raises."""
+    for t in (prev_u8, cur_u8):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{what}: expected a tensor, got {type(t)}")
+        if t.dtype != torch.uint8:
+            raise TypeError(f"{what}: frames of dtype {torch.uint8} expected, got {t.dtype}")
+    for t, name in ((flow, "flow"), (weight, "weight")):
+        if t is None and name == "weight":
+            continue
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{what}: {name}: expected a tensor, got {type(t)}")
+        if t.dtype != torch.float32:
+            raise TypeError(f"{what}: {name} of dtype {torch.float32} expected, got {t.dtype}")
+    if prev_u8.shape != cur_u8.shape:
+        raise ValueError(f"{what}: {tuple(prev_u8.shape)} against {tuple(cur_u8.shape)}")
+    if prev_u8.dim() == 3:
+        if flow.dim() != 3 or (weight is not None and weight.dim() != 3):
+            raise ValueError(f"{what}: one pair takes flow [2,H,W] and weight [1,H,W]")
+        prev_u8, cur_u8, flow = prev_u8.unsqueeze(0), cur_u8.unsqueeze(0), flow.unsqueeze(0)
+        weight = weight.unsqueeze(0) if weight is not None else None
+    if prev_u8.dim() != 4 or prev_u8.shape[-1] != 3 or prev_u8.shape[0] < 1:
+        raise ValueError(f"{what}: uint8 [H,W,3] or [N,H,W,3] expected, got {tuple(cur_u8.shape)}")
+    N, H, W = prev_u8.shape[:3]
+    if H < 2 or W < 2:
+        raise ValueError(f"{what}: the lattice needs H, W >= 2, got {(H, W)}")
+    if tuple(flow.shape) != (N, 2, H, W):
+        raise ValueError(f"{what}: flow {tuple(flow.shape)} given, {(N, 2, H, W)} expected")
+    if weight is not None and tuple(weight.shape) != (N, 1, H, W):
+        raise ValueError(f"{what}: weight {tuple(weight.shape)} given, {(N, 1, H, W)} expected")
+    return prev_u8, cur_u8, flow, weight
+
+
+def _axis(idx, f, n):
+    """One axis of the warp: lattice positions ``idx``, flow component ``f`` in pixels, size ``n`` -> (weight of the second
+    neighbour, first index, second index).  A NaN coordinate keeps its NaN in the weight and reads index 0."""
+    g = (-1.0 + idx * (2.0 / (n - 1))) + f / ((n - 1) / 2.0)
+    p = ((g + 1.0) * n - 1.0) * 0.5
+    p = p.clamp(0.0, float(n - 1))                  # (torch's clamp keeps a NaN)
+    fl = p.floor()
+    i0 = torch.nan_to_num(fl, nan=0.0).long().clamp(0, n - 1)
+    return p - fl, i0, (i0 + 1).clamp(max=n - 1)
+
+
+def warp_error_reference(prev_u8, cur_u8, flow, weight=None):
+    """``warp_error`` in plain torch fp64 on whatever device the tensors are on -> fp64 [N,3] (warp_l1, warp_mse,
+    coverage).  Written from the formulas of this module's docstring in the operation order of csrc/warp_error.hip; the two
+    differ only in the order of the sums over a pair (``warp_bound``)."""
+    prev_u8, cur_u8, flow, weight = _pairs(prev_u8, cur_u8, flow, weight, "warp_error_reference")
+    N, H, W = prev_u8.shape[:3]
+    f64, dev = torch.float64, prev_u8.device
+    xs, ys = torch.arange(W, dtype=f64, device=dev).view(1, W), torch.arange(H, dtype=f64, device=dev).view(H, 1)
+    rows = []
+    for n in range(N):
+        P, C = prev_u8[n].to(f64), cur_u8[n].to(f64)
+        ax, x0, x1 = _axis(xs, flow[n, 0].to(f64), W)
+        ay, y0, y1 = _axis(ys, flow[n, 1].to(f64), H)
+        w00, w01, w10, w11 = (1.0 - ay) * (1.0 - ax), (1.0 - ay) * ax, ay * (1.0 - ax), ay * ax
+        wv = (w00.unsqueeze(-1) * P[y0, x0] + w01.unsqueeze(-1) * P[y0, x1] + w10.unsqueeze(-1) * P[y1, x0]
+              + w11.unsqueeze(-1) * P[y1, x1])
+        d = C - wv
+        m = weight[n, 0].to(f64).unsqueeze(-1) if weight is not None else torch.ones((H, W, 1), dtype=f64, device=dev)
+        S1, S2, SC = (m * d.abs()).sum(), (m * (d * d)).sum(), m.sum()
+        rows.append(torch.stack([S1 / (127.5 * 3 * H * W), S2 / (255.0 * 255.0 * 3.0 * SC), SC / (H * W)]))
+    return torch.stack(rows)
+
+
 # ---------------------------------------------------------------------------------------------
 # the kernels
 # ---------------------------------------------------------------------------------------------
@@ -194,14 +352,51 @@ def video_metrics(orig_u8, pred_u8, data_range="reference"):
     return out
 
 
+_WARP_WORKSPACES = {}
+
+
+def _warp_workspace(device, stream, N, H, W):
+    """As ``_workspace``: one fp64 buffer per (device, stream, N, H, W), written by the library before it is read."""
+    key = (device.index, stream, N, H, W)
+    ws = _WARP_WORKSPACES.get(key)
+    if ws is None:
+        nbytes = _lib.lib().ir2rgb_warp_error_workspace_bytes(N, H, W)
+        if nbytes < 0:
+            raise ValueError(f"warp_error: N={N}, H={H}, W={W} is outside what the kernels take "
+                             "(N <= 65535, H, W >= 2, 3*H*W < 2**31)")
+        ws = _WARP_WORKSPACES[key] = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=device)
+    return ws
+
+
+def warp_error(prev_u8, cur_u8, flow, weight=None):
+    """Warp error of ``cur_u8`` against ``prev_u8`` warped along ``flow``: uint8 [H,W,3] or [N,H,W,3] device frames, fp32
+    ``flow`` [2,H,W] / [N,2,H,W] (x then y, in pixels, from ``cur`` to ``prev``) and an optional fp32 ``weight`` [1,H,W] /
+    [N,1,H,W] (the confidence of the flow; None means 1) -> fp64 device tensor [N,3] with the columns warp_l1, warp_mse,
+    coverage (``ir2rgb_warp_error_u8``; the definition is in this module's docstring).  Enqueued on the current stream;
+    nothing synchronises the host.
+
+    CPU tensors, other dtypes, non-contiguous tensors and frames smaller than 2x2 raise."""
+    dev = _lib.require_device(prev_u8, cur_u8, dtype=torch.uint8)
+    if _lib.require_device(flow, weight, dtype=torch.float32) != dev:
+        raise ValueError("warp_error: frames and flow on different devices")
+    prev_u8, cur_u8, flow, weight = _pairs(prev_u8, cur_u8, flow, weight, "warp_error")
+    N, H, W = prev_u8.shape[:3]
+    out = torch.empty((N, 3), dtype=torch.float64, device=dev)
+    ws = _warp_workspace(dev, _lib.current_stream(out), N, H, W)
+    _lib.launch("ir2rgb_warp_error_u8", out, prev_u8, cur_u8, flow, weight, out, ws, ws.numel() * 8, N, H, W)
+    return out
+
+
 class VideoScore:
     """The movie scores of scripts/ssim_metric.py: ``add(orig_u8, pred_u8)`` appends the per-frame rows of
     ``video_metrics`` on the device, ``result()`` averages them (``ssim_movie`` / ``mse_movie``) and is the only call that
-    synchronises."""
+    synchronises.  ``add_pair`` collects the temporal rows (``warp_error`` of the prediction, and of the ground truth as the
+    baseline: how much of the error is the flow's own); ``result()`` reports them only when a pair was added."""
 
     def __init__(self, data_range="reference"):
         self.data_range = data_range
         self._rows = []
+        self._pair_rows = []
 
     def add(self, orig_u8, pred_u8):
         """One frame [H,W,3] or several [N,H,W,3]; -> their rows [N,3] (device)."""
@@ -219,7 +414,31 @@ class VideoScore:
             raise ValueError("VideoScore: no frame was added")
         return torch.cat(self._rows)
 
+    def add_pair(self, pred_prev_u8, pred_cur_u8, orig_prev_u8, orig_cur_u8, flow, weight=None):
+        """Two consecutive outputs and their ground-truth frames with the flow (and its confidence) between the latter;
+        -> rows [N,5] (device): warp_l1, warp_mse of the prediction, the same of the ground truth, coverage."""
+        pred = warp_error(pred_prev_u8, pred_cur_u8, flow, weight)
+        orig = warp_error(orig_prev_u8, orig_cur_u8, flow, weight)
+        rows = torch.cat([pred[:, :2], orig[:, :2], pred[:, 2:]], 1)
+        self._pair_rows.append(rows)
+        return rows
+
+    @property
+    def pairs(self):
+        return sum(r.shape[0] for r in self._pair_rows)
+
+    def per_pair(self):
+        """fp64 [pairs,5] device tensor (warp_l1, warp_mse, truth_warp_l1, truth_warp_mse, coverage), in the order added."""
+        if not self._pair_rows:
+            raise ValueError("VideoScore: no pair was added")
+        return torch.cat(self._pair_rows)
+
     def result(self):
         per = self.per_frame()
         ssim, l2 = per[:, :2].mean(0).tolist()
-        return {"ssim": ssim, "l2": l2, "frames": per.shape[0], "per_frame": per}
+        res = {"ssim": ssim, "l2": l2, "frames": per.shape[0], "per_frame": per}
+        if self._pair_rows:
+            pp = self.per_pair()
+            res.update(zip(("warp_l1", "warp_mse", "truth_warp_l1", "truth_warp_mse", "coverage"), pp.mean(0).tolist()))
+            res.update(pairs=pp.shape[0], per_pair=pp)
+        return res
