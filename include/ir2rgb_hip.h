@@ -474,6 +474,46 @@ int ir2rgb_loss_scale_update(void *scaler_state, const void *opt_states, int cou
                              int growth_interval, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Guarded optimizer steps for every compute dtype (grad_guard.hip): per optimizer and window a gradient that holds an
+ * inf or a NaN skips the step, a finite one is clipped to a global L2 norm -- decided on the device, like the
+ * loss-scaled step, whose check kernel, partial rows and ir2rgb_adam_state these entry points share.  With g the stored
+ * gradient (of the scaled loss when scaler_state is given) and inv = scaler_state's inv_scale, or exactly 1 when
+ * scaler_state is NULL, all in double:
+ *     norm = sqrt(sum g^2) * inv,  c = min(1, max_norm / (norm + 1e-6)),  factor = (float)(inv * c)
+ * and the step is ir2rgb_adam_step on fl(g * factor), one rounded product per element.  This is
+ * torch.nn.utils.clip_grad_norm_ applied after the unscaling, except that torch evaluates c in fp32.  max_norm +inf
+ * never clips: c is exactly 1 and factor is inv_scale, or 1.0 without a scaler.  c < 1 counts as clipped.
+ *   guard_state : ir2rgb_grad_guard_state, 4-byte aligned, zeroed by the caller, one per optimizer, written by the
+ *                 kernels only.  After a non-finite gradient grad_norm is that gradient's (inf or NaN), clip_coef and
+ *                 factor are 0, `skipped` is incremented and `steps` is not; p, m, v and opt_state's step stay bit for bit.
+ *   table, blocks, nblocks, partial, opt_state : as for ir2rgb_grad_check, which this call replaces (opt_state is
+ *                 left exactly as ir2rgb_grad_check leaves it, so ir2rgb_loss_scale_update, ir2rgb_ema_step and
+ *                 ir2rgb_loss_log_push read the skip decision where they always did)
+ * IR2RGB_EINVAL: a NULL pointer other than scaler_state, nblocks < 0, a beta outside [0, 1), max_norm <= 0 or NaN;
+ * IR2RGB_EALIGN: partial / opt_state off an 8-byte boundary, guard_state / scaler_state off a 4-byte one.  Both before
+ * any launch.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct ir2rgb_grad_guard_state {
+    float grad_norm;     /* unscaled global L2 norm of the last checked gradient */
+    float clip_coef;     /* c of the last check (1 when nothing was clipped, 0 after a skipped step) */
+    float factor;        /* what the step multiplied the stored gradient by: (float)(inv_scale * c) */
+    int steps;           /* steps taken under this guard */
+    int clipped;         /* of those, steps with c < 1 */
+    int skipped;         /* steps skipped because the gradient held an inf or a NaN */
+    int reserved[2];
+} ir2rgb_grad_guard_state;
+
+long ir2rgb_grad_guard_state_bytes(void);
+/* ir2rgb_grad_check's two launches with the rule above in the second one. */
+int ir2rgb_grad_guard_check(const void *table, const void *blocks, int nblocks, void *partial, void *opt_state,
+                            void *guard_state, const void *scaler_state, float max_norm, float lr, float beta1, float beta2,
+                            float eps, void *stream);
+/* ir2rgb_adam_step on g * guard_state's factor with the coefficients ir2rgb_grad_guard_check left in opt_state; touches
+ * nothing when opt_state's found_inf is set. */
+int ir2rgb_adam_step_guarded(const void *table, const void *blocks, int nblocks, const void *opt_state,
+                             const void *guard_state, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Exponential moving average of the generator's parameters (ema.hip): e <- e + alpha * (p - e) for every tensor
  * of a table, one streaming launch per window after the generator's optimizer step.  The three operations are
  * rounded one by one in fp32 (no fused multiply-add), so p == e leaves e unchanged bit for bit; inf and NaN

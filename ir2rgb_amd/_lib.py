@@ -55,6 +55,12 @@ class LossScaleState(ctypes.Structure):
     _fields_ = [("scale", c_float), ("inv_scale", c_float), ("growth_tracker", c_int), ("skipped", c_int)]
 
 
+class GradGuardState(ctypes.Structure):
+    """ir2rgb_grad_guard_state of include/ir2rgb_hip.h (device-resident; ir2rgb_grad_guard_state_bytes())."""
+    _fields_ = [("grad_norm", c_float), ("clip_coef", c_float), ("factor", c_float), ("steps", c_int), ("clipped", c_int),
+                ("skipped", c_int), ("reserved", c_int * 2)]
+
+
 class EmaState(ctypes.Structure):
     """ir2rgb_ema_state of include/ir2rgb_hip.h (device-resident; ir2rgb_ema_state_bytes())."""
     _fields_ = [("updates", c_int), ("skipped", c_int), ("alpha", c_float), ("reserved", c_int)]
@@ -137,6 +143,9 @@ PROTOTYPES = {
     "ir2rgb_grad_check": (c_int, [P, P, c_int, P, P, P, c_float, c_float, c_float, c_float, P]),
     "ir2rgb_adam_step_scaled": (c_int, [P, P, c_int, P, P, P]),
     "ir2rgb_loss_scale_update": (c_int, [P, P, c_int, c_float, c_float, c_int, P]),
+    "ir2rgb_grad_guard_state_bytes": (c_long, []),
+    "ir2rgb_grad_guard_check": (c_int, [P, P, c_int, P, P, P, P, c_float, c_float, c_float, c_float, c_float, P]),
+    "ir2rgb_adam_step_guarded": (c_int, [P, P, c_int, P, P, P]),
     "ir2rgb_ema_state_bytes": (c_long, []),
     "ir2rgb_ema_step": (c_int, [P, P, c_int, P, P, c_float, c_int, P]),
     "ir2rgb_loss_log_push": (c_int, [P, ctypes.c_uint, c_int, P, c_int, P, P, c_int, P]),

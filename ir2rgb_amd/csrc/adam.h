@@ -1,4 +1,5 @@
-// adam.h -- what adam.hip (the plain step) and loss_scale.hip (the loss-scaled step) share: the table row, the
+// adam.h -- what adam.hip (the plain step), loss_scale.hip (the loss-scaled step) and grad_guard.hip (the guarded step,
+// through grad_check.h) share: the table row, the
 // coefficients of one step, the update of one element and the three paths of one (tensor, chunk) workgroup.
 #pragma once
 #include "common.h"
@@ -51,8 +52,8 @@ __device__ __forceinline__ void adam_one(float &p, float g, float &m, float &v, 
     p = __builtin_fmaf(-step_size, m / denom, p);
 }
 
-// One workgroup of 256 lanes on its (tensor, chunk).  SCALED: the gradient enters as g * inv_scale; otherwise inv_scale
-// is not read.
+// One workgroup of 256 lanes on its (tensor, chunk).  SCALED: the gradient enters as g * inv_scale (the guarded step
+// passes its factor, inv_scale times the clip coefficient); otherwise inv_scale is not read.
 template <bool SCALED>
 __device__ __forceinline__ void adam_block(const AdamTensor *__restrict__ table, const int2 *__restrict__ blocks,
                                            const AdamCoef &k, const float inv_scale) {

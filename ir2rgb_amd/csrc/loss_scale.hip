@@ -3,101 +3,22 @@
 // An f16 activation gradient below 6e-5 loses bits and one below 6e-8 is gone, so the loss is multiplied by a scale
 // before backward() (the reference's --fp16, apex's dynamic loss scaling).  What follows the backward pass stays on
 // the device -- the host never reads the decision:
-//     grad_check_kernel         one read of g (4 B per parameter on top of the step's 28): finite? sum of squares
+//     grad_check_kernel         (grad_check.h, shared with grad_guard.hip) one read of g (4 B per parameter on top of
+//                               the step's 28): finite? sum of squares
 //     grad_check_finish_kernel  found_inf, the unscaled norm, and -- if finite -- the step count and its coefficients
 //     adam_scaled_kernel        adam_kernel on g * inv_scale, or nothing at all when found_inf is set
 //     loss_scale_update_kernel  torch._amp_update_scale_'s rule over the optimizers stepped this window
 // The check and the update are latency-shaped (DESIGN, "Small kernels are latency-shaped"): every load of a thread is
 // in flight before the first use, loads are unconditional from clamped indices and masked afterwards, sums are in
 // double in a fixed order (thread, wave, workgroup), and nothing is atomic.
-#include "adam.h"
+#include "grad_check.h"
 
 static_assert(sizeof(ir2rgb_adam_state) == 48 && offsetof(ir2rgb_adam_state, grad_sumsq) == 40, "ir2rgb_adam_state layout");
 static_assert(offsetof(ir2rgb_adam_state, step_size) == 4 && offsetof(ir2rgb_adam_state, found_inf) == 32 &&
               sizeof(AdamCoef) == 28, "the coefficients of ir2rgb_adam_state are an AdamCoef");
 static_assert(sizeof(ir2rgb_loss_scale_state) == 16, "ir2rgb_loss_scale_state layout");
 
-struct CheckRow {
-    double sumsq;
-    float nonfinite, reserved;
-};
-static_assert(sizeof(CheckRow) == 16, "one 16-byte load per partial row");
-
-#define CHECK_FINISH_THREADS 1024
 #define LOSS_SCALE_MAX_OPTIMIZERS 8
-
-// inf or NaN: decided from the value's exponent field (3e38 is finite although its square is not a float)
-__device__ __forceinline__ bool nonfinite(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
-
-// fixed-order sum over the 64 lanes of a wave (lane 0 holds the total)
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d, 64);
-    return v;
-}
-
-__global__ void __launch_bounds__(256)
-grad_check_kernel(const AdamTensor *__restrict__ table, const int2 *__restrict__ blocks, CheckRow *__restrict__ partial) {
-    const int2 tb = blocks[blockIdx.x];
-    const AdamTensor t = table[tb.x];
-    const long e0 = (long)tb.y * ADAM_CHUNK;
-    const long e1 = min(t.n, e0 + ADAM_CHUNK);
-    // the same three cases as adam_kernel, so that the 16-byte path is taken exactly where the step takes it
-    const bool vec = ((((uintptr_t)t.p | (uintptr_t)t.g | (uintptr_t)t.m | (uintptr_t)t.v) & 15) == 0);
-    double acc = 0.0;
-    bool bad = false;
-    auto take = [&](float g) { bad |= nonfinite(g); acc += (double)g * (double)g; };
-    if (vec && e1 - e0 == ADAM_CHUNK) {
-        typedef float vf4 __attribute__((ext_vector_type(4)));
-        typedef __attribute__((address_space(1))) vf4 gf4;
-        const gf4 *g4 = (const gf4 *)(uintptr_t)t.g;
-        const long q0 = (e0 >> 2) + threadIdx.x;
-        vf4 G[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) G[u] = g4[q0 + u * 256];      // (cached: the step reads g next)
-#pragma unroll
-        for (int u = 0; u < 8; ++u)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) take(G[u][c]);
-    } else if (vec) {
-        const long qb = e0 >> 2, q1 = e1 >> 2;   // whole float4s below e1 (e0 is a multiple of 4)
-        const float4 *g4 = (const float4 *)t.g;
-        if (q1 > qb) {                           // (uniform: a tensor of fewer than 4 elements has no float4 to clamp to)
-            float4 G[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) G[u] = g4[min(qb + u * 256 + threadIdx.x, q1 - 1)];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const float keep = qb + u * 256 + threadIdx.x < q1 ? 1.f : 0.f;    // masked after the load: 0 is finite
-                take(keep != 0.f ? G[u].x : 0.f); take(keep != 0.f ? G[u].y : 0.f);
-                take(keep != 0.f ? G[u].z : 0.f); take(keep != 0.f ? G[u].w : 0.f);
-            }
-        }
-        // tail of the tensor (n % 4 elements) belongs to the last chunk; e1 > e0, so e1 - 1 is an element of the tensor
-        const long e = (q1 << 2) + threadIdx.x;
-        const float g = t.g[min(e, e1 - 1)];
-        take(e < e1 ? g : 0.f);
-    } else {
-        float G[ADAM_CHUNK / 256];
-#pragma unroll
-        for (int u = 0; u < ADAM_CHUNK / 256; ++u) G[u] = t.g[min(e0 + u * 256 + threadIdx.x, e1 - 1)];
-#pragma unroll
-        for (int u = 0; u < ADAM_CHUNK / 256; ++u) take(e0 + u * 256 + threadIdx.x < e1 ? G[u] : 0.f);
-    }
-    __shared__ double s_sum[4];
-    __shared__ int s_bad[4];
-    acc = wave_sum(acc);
-    const bool wave_bad = __builtin_amdgcn_ballot_w64(bad) != 0;
-    if ((threadIdx.x & 63) == 0) { s_sum[threadIdx.x >> 6] = acc; s_bad[threadIdx.x >> 6] = wave_bad; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        CheckRow r;
-        r.sumsq = ((s_sum[0] + s_sum[1]) + s_sum[2]) + s_sum[3];
-        r.nonfinite = (s_bad[0] | s_bad[1] | s_bad[2] | s_bad[3]) ? 1.f : 0.f;
-        r.reserved = 0.f;
-        partial[blockIdx.x] = r;
-    }
-}
 
 __global__ void __launch_bounds__(CHECK_FINISH_THREADS)
 grad_check_finish_kernel(const CheckRow *__restrict__ partial, int nrows, ir2rgb_adam_state *__restrict__ st,
@@ -147,10 +68,7 @@ __global__ void __launch_bounds__(256)
 adam_scaled_kernel(const AdamTensor *__restrict__ table, const int2 *__restrict__ blocks,
                    const ir2rgb_adam_state *__restrict__ st, const ir2rgb_loss_scale_state *__restrict__ sc) {
     if (st->found_inf != 0.f) return;        // (uniform) the step is skipped: p, m, v stay as they are
-    AdamCoef k;
-    k.step_size = st->step_size; k.beta1 = st->beta1; k.beta2 = st->beta2; k.omb1 = st->omb1; k.omb2 = st->omb2;
-    k.bc2_sqrt = st->bc2_sqrt; k.eps = st->eps;
-    adam_block<true>(table, blocks, k, sc->inv_scale);
+    adam_block<true>(table, blocks, state_coef(st), sc->inv_scale);
 }
 
 __global__ void __launch_bounds__(64)
@@ -194,8 +112,6 @@ extern "C" long ir2rgb_grad_check_partial_bytes(int nblocks) {
     if (nblocks < 0) return IR2RGB_EINVAL;
     return (long)sizeof(CheckRow) * (nblocks > 0 ? nblocks : 1);
 }
-
-static inline bool misaligned(const void *p, unsigned a) { return ((uintptr_t)p & (a - 1)) != 0; }
 
 extern "C" int ir2rgb_grad_check(const void *table, const void *blocks, int nblocks, void *partial, void *opt_state,
                                  const void *scaler_state, float lr, float beta1, float beta2, float eps, void *stream) {

@@ -56,10 +56,12 @@ class LossLog:
         self.state = torch.zeros(ctypes.sizeof(_lib.LossLogState) // 8, dtype=torch.int64, device=device)
         self._srcs, self._opts = _HostPointers(MAX_NAMES), _HostPointers(8)
 
-    def push(self, out, scaler=None):
+    def push(self, out, scaler=None, optimizers=None):
         """One window: ``out`` maps names to zero-dimensional fp32 tensors on the device (what ``train_window`` returns;
         names this log does not record are ignored).  With the trainer's ``LossScaler`` a window whose optimizer steps
-        were skipped is counted as skipped and kept out of the sums.  Does not synchronise."""
+        were skipped is counted as skipped and kept out of the sums.  ``optimizers``: the optimizers stepped this window
+        whose steps were decided on the device (loss-scaled or guarded: ``Vid2VidTrainer.decided_optimizers``) --
+        given, they are asked instead of the scaler, so that a guarded window counts without one.  Does not synchronise."""
         present = 0
         srcs = self._srcs.array
         for name, i in self.slot.items():
@@ -71,8 +73,8 @@ class LossLog:
             srcs[i] = t.data_ptr()
             present |= 1 << i
         n_opts = 0
-        if scaler is not None:
-            opts = scaler.last_optimizers()
+        if optimizers is not None or scaler is not None:
+            opts = list(optimizers) if optimizers is not None else scaler.last_optimizers()
             if len(opts) > 8:
                 raise ValueError("LossLog.push: at most 8 optimizers")
             for o in opts:

@@ -10,6 +10,9 @@ f16 training scales its losses (``LossScaler``; libir2rgb_hip.so: loss_scale.hip
 the scaled gradient on the device, steps on ``g * inv_scale`` or skips, and ``LossScaler.update`` applies
 ``torch._amp_update_scale_``'s rule -- the decision, the step count and the scale never visit the host.
 
+``GradGuard`` (libir2rgb_hip.so: grad_guard.hip) guards the steps of every compute dtype: ``FusedAdam.step(scaler, guard)``
+skips the step on an inf or NaN and clips a finite gradient to a global L2 norm, with or without a scaler, on the device.
+
 ``ParamEMA`` (libir2rgb_hip.so: ema.hip) keeps an exponential moving average of a parameter list in one more launch per
 step; after a loss-scaled step it reads that step's skip decision from the optimizer's device state.
 """
@@ -61,10 +64,11 @@ class FusedAdam:
         self._ptrs = [p.data_ptr() for p in self.params]
         self.device = dev
         self._flip = 0
-        # loss-scaled steps only (scaled_state): ir2rgb_adam_state on the device and the check kernel's partial rows
+        # loss-scaled and guarded steps only (scaled_state): ir2rgb_adam_state on the device and the check kernel's partial rows
         self._state = self._partial = None
-        self._on_device = False          # the step count lives in _state[0] (loss-scaled steps) / in step_count
-        self.last_step_scaled = False    # the last step() took a scaler: its skip decision is in scaled_state() (ParamEMA.update)
+        self._on_device = False          # the step count lives in _state[0] (loss-scaled / guarded steps) / in step_count
+        # the last step() took a scaler or a guard: its skip decision is in scaled_state() (ParamEMA.update, LossLog.push)
+        self.last_step_scaled = False
 
     @property
     def lr(self):
@@ -175,14 +179,24 @@ class FusedAdam:
         self._copied[k].record()
 
     @torch.no_grad()
-    def step(self, scaler=None):
+    def step(self, scaler=None, guard=None):
         """One Adam step.  With a ``LossScaler`` the gradients are those of the scaled loss: they are checked on the
         device (ir2rgb_grad_check), and the step is taken on ``g * inv_scale`` or -- an inf or NaN anywhere -- not at all
-        (ir2rgb_adam_step_scaled); the host learns neither."""
+        (ir2rgb_adam_step_scaled); the host learns neither.  With a ``GradGuard`` -- with or without a scaler -- the check
+        also clips to the guard's global norm (ir2rgb_grad_guard_check) and the step is taken on ``g * factor``
+        (ir2rgb_adam_step_guarded): two launches that replace the scaler's two."""
+        if guard is not None and guard.optimizer is not self:
+            raise ValueError("FusedAdam.step: the guard was built for another optimizer")
         self._refresh_table()
         nblocks = self._blocks.shape[0]
-        self.last_step_scaled = scaler is not None
-        if scaler is None:
+        self.last_step_scaled = scaler is not None or guard is not None
+        if guard is not None:
+            state = self.scaled_state()
+            _lib.launch("ir2rgb_grad_guard_check", self.exp_avg, self._rows_dev, self._blocks, nblocks, self._partial, state,
+                        guard.state, None if scaler is None else scaler.state, guard.max_norm, self.lr, self.betas[0],
+                        self.betas[1], self.eps)
+            _lib.launch("ir2rgb_adam_step_guarded", self.exp_avg, self._rows_dev, self._blocks, nblocks, state, guard.state)
+        elif scaler is None:
             if self._on_device:              # loss-scaled steps came before: their count moves back to the host
                 self._read_step_count()
                 self._on_device = False
@@ -329,7 +343,62 @@ def make_loss_scaler(value, device):
     return LossScaler(device, init_scale=float(value), growth_interval=0)
 
 
-EMA_WARMUP_END = 1 << 20          # csrc/ema.hip: from this update on the decay is beta itself
+GUARD_FAMILIES = ("G", "D", "D_T")
+
+
+def check_max_norm(value, what="max_norm"):
+    """A clipping threshold: a number above 0, ``float("inf")`` (guard only, never clip) included -> as a float."""
+    if isinstance(value, bool) or not isinstance(value, (int, float)) or math.isnan(value) or value <= 0:
+        raise ValueError(f"{what}: a number above 0 (float(\"inf\"): never clip), got {value!r}")
+    if float(np.float32(value)) == 0.0:
+        raise ValueError(f"{what}: {value!r} is 0 as fp32")
+    with np.errstate(over="ignore"):
+        return float(np.float32(value))       # (the kernel receives a float)
+
+
+def check_grad_guard_option(value, fused_adam):
+    """Validates the trainer's ``max_grad_norm`` option -- None, a threshold for every optimizer, or a dict of thresholds
+    per optimizer family ("G", "D", "D_T"; a missing key means inf) -- without touching a device.
+    -> None | {"G": x, "D": y, "D_T": z}."""
+    if value is None:
+        return None
+    if isinstance(value, dict):
+        unknown = [k for k in value if k not in GUARD_FAMILIES]
+        if unknown:
+            raise ValueError(f"max_grad_norm: keys are among {GUARD_FAMILIES}, got {unknown!r}")
+        out = {k: check_max_norm(value[k], f"max_grad_norm[{k!r}]") if k in value else math.inf for k in GUARD_FAMILIES}
+    else:
+        out = dict.fromkeys(GUARD_FAMILIES, check_max_norm(value, "max_grad_norm"))
+    if not fused_adam:
+        raise ValueError("max_grad_norm needs fused_adam=True: the decision is taken on the device by ir2rgb_amd.optim.FusedAdam")
+    return out
+
+
+class GradGuard:
+    """The guard of one ``FusedAdam``: ``optimizer.step(scaler, guard)`` skips the step when the gradient holds an inf or a
+    NaN and otherwise clips it to the global L2 norm ``max_norm`` (``float("inf")``: never), decided on the device
+    (libir2rgb_hip.so: grad_guard.hip; ``grad_guard_reference`` restates the rule).  Owns the optimizer's
+    ir2rgb_grad_guard_state; ``norm_tensor`` is the unscaled gradient norm of the last step as a 0-dim fp32 view of it, a
+    device operand for ``LossLog``.  Nothing synchronises but ``stats``."""
+
+    def __init__(self, optimizer, max_norm):
+        if not isinstance(optimizer, FusedAdam):
+            raise ValueError("GradGuard: the optimizer is an ir2rgb_amd.optim.FusedAdam (the decision is taken by its kernels)")
+        self.max_norm = check_max_norm(max_norm, "GradGuard: max_norm")
+        self.optimizer = optimizer
+        nbytes = _lib.query("ir2rgb_grad_guard_state_bytes")
+        assert ctypes.sizeof(_lib.GradGuardState) == nbytes
+        self.state = torch.zeros(nbytes // 4, dtype=torch.int32, device=optimizer.device)
+        self.norm_tensor = self.state.view(torch.float32)[0]
+
+    def stats(self):
+        """{steps, clipped, skipped, grad_norm, clip_coef}: steps taken, steps clipped, steps skipped, and the norm and
+        coefficient of the last one checked (synchronises)."""
+        st = _lib.GradGuardState.from_buffer_copy(self.state.cpu().numpy().tobytes())
+        return {"steps": st.steps, "clipped": st.clipped, "skipped": st.skipped, "grad_norm": st.grad_norm, "clip_coef": st.clip_coef}
+
+
+EMA_WARMUP_END = 1 << 20         # csrc/ema.hip: from this update on the decay is beta itself
 
 
 def check_ema_option(value):
@@ -492,6 +561,33 @@ def loss_scale_update_reference(scale, growth_tracker, found_inf, growth_factor,
                     scale.copy_(grown)
                 growth_tracker.zero_()
     return (1.0 / scale.double()).float(), int(found)
+
+
+def grad_guard_reference(grads, max_norm, inv_scale=1.0):
+    """grad_check_kernel + grad_guard_finish_kernel's rule in torch fp64 on the CPU, over the stored gradients of ONE
+    optimizer (those of the scaled loss when ``inv_scale`` is a loss scaler's):
+    -> (found, sumsq, norm, c, factor).  ``found``: an element with an all-ones exponent (inf or NaN).  ``sumsq``: the
+    fp64 sum of squares of the stored gradients; ``norm = sqrt(sumsq) * inv_scale``; ``c = min(1, max_norm / (norm +
+    1e-6))`` (``torch.nn.utils.clip_grad_norm_``'s coefficient, in double); ``factor``: what the step multiplies every
+    stored element by, ``inv_scale * c`` rounded to fp32.  After ``found`` the step is skipped and ``c`` and ``factor``
+    are 0.  ``max_norm`` and ``inv_scale`` are taken as the fp32 numbers the device holds."""
+    flat = [torch.as_tensor(g).detach().cpu().reshape(-1) for g in grads]
+    found = any(not bool(torch.isfinite(g).all()) for g in flat)
+    sumsq = float(sum(float((g.double() * g.double()).sum()) for g in flat))
+    if found:
+        inv = float(np.float32(inv_scale))
+        return True, sumsq, math.sqrt(sumsq) * inv if sumsq >= 0 else float("nan"), 0.0, 0.0
+    return (False, sumsq) + grad_guard_rule(sumsq, max_norm, inv_scale)
+
+
+def grad_guard_rule(sumsq, max_norm, inv_scale=1.0):
+    """What grad_guard_finish_kernel derives from a finite gradient's sum of squares, the same expressions in double:
+    -> (norm, c, factor), ``factor`` rounded to fp32."""
+    inv = float(np.float32(inv_scale))
+    norm = math.sqrt(sumsq) * inv
+    q = float(np.float32(max_norm)) / (norm + 1e-6)
+    c = q if q < 1.0 else 1.0
+    return norm, c, float(np.float32(inv * c))
 
 
 def grad_check_reference(grads, inv_scale):

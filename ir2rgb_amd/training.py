@@ -14,12 +14,15 @@ from .frames import WindowSlicer
 from .losslog import LossLog
 
 # every term train_window can return with two temporal scales (the reference's loss_names / loss_names_T with the scale
-# appended, and the totals its losses_G / losses_D lists hold): 21 of the log's 32 slots
-def loss_names(t_scales):
+# appended, and the totals its losses_G / losses_D lists hold): 21 of the log's 32 slots.  ``grad_norms``: also the gradient
+# norms a guarded trainer (``max_grad_norm``) returns, one per optimizer: 25 slots
+def loss_names(t_scales, grad_norms=False):
     names = ["G", "D"] + [f"D_T{s}" for s in range(t_scales)]
     names += ["G_VGG", "G_GAN", "G_GAN_Feat", "D_real", "D_fake", "G_Warp", "F_Flow", "F_Warp", "W"]
     for s in range(t_scales):
         names += [f"G_T_GAN{s}", f"G_T_GAN_Feat{s}", f"D_T_real{s}", f"D_T_fake{s}"]
+    if grad_norms:
+        names += ["GN_G", "GN_D"] + [f"GN_D_T{s}" for s in range(t_scales)]
     return names
 
 
@@ -75,7 +78,7 @@ def fit(trainer, sequences, schedule, save_dir=None, log=print, loss_log=None, c
     n_frames_load = trainer.update_training_batch(st.ratio, resume=True)
     assert (n_frames_load, trainer.opt["n_frames_bp"]) == (st.n_frames_load, st.n_frames_bp)
     if loss_log is None:
-        loss_log = LossLog(trainer.device, loss_names(trainer.t_scales))
+        loss_log = LossLog(trainer.device, loss_names(trainer.t_scales, grad_norms=trainer.grad_guards is not None))
     tG = schedule.n_input_gen_frames
     totals = {"G", "D"} | {f"D_T{s}" for s in range(trainer.t_scales)}
     opt = trainer.opt
@@ -113,7 +116,11 @@ def fit(trainer, sequences, schedule, save_dir=None, log=print, loss_log=None, c
             save_fake = snapshots is not None and snapshots.due(st.total_steps + 1)      # (schedule.step: one per sequence)
             fake_B_first = None
             for i, (input_A, input_B) in enumerate(slicer):
-                loss_log.push(trainer.train_window(input_A, input_B), trainer.loss_scaler)
+                out = trainer.train_window(input_A, input_B)
+                if trainer.grad_guards is None:
+                    loss_log.push(out, trainer.loss_scaler)
+                else:           # guarded steps: a skipped window counts with or without a scaler
+                    loss_log.push(out, trainer.loss_scaler, trainer.decided_optimizers())
                 if save_fake and i == 0:       # the first generated image of this sequence (train_vid2vid.py:113-114)
                     fake_B_first = trainer.last_outputs[0][0, 0]
                     if _in_frame_history(trainer, fake_B_first):

@@ -29,7 +29,8 @@ from .flownet import FlowNet
 from .frames import FrameHistory
 from .losses import _SplitGroupsFn, drop_grad_dsts, fused_losses, split_groups  # noqa: F401  (re-exported)
 from .networks import SLOT_D_TEMPORAL, SLOT_FLOWNET, _Branch, side_stream
-from .optim import FusedAdam, LossScaler, ParamEMA, check_ema_option, check_loss_scale_option, make_loss_scaler  # noqa: F401
+from .optim import (FusedAdam, GradGuard, LossScaler, ParamEMA, check_ema_option, check_grad_guard_option,  # noqa: F401
+                    check_loss_scale_option, make_loss_scaler)
 
 DEFAULTS = dict(  # options/base_options.py, options/train_options.py
     input_nc=3, output_nc=3, n_input_gen_frames=3, first_layer_gen_filters=128, gen_network="composite", gen_ds_layers=3,
@@ -47,6 +48,10 @@ DEFAULTS = dict(  # options/base_options.py, options/train_options.py (SURVEY se
     fused_adam=True,     # one-launch HIP Adam (ir2rgb_amd.optim); False = torch.optim.Adam(foreach=True)
     loss_scale=None,     # f16 training: a number (static scale), "dynamic" (2^16, halved on overflow, doubled after 2000 clean
                          # windows) or an ir2rgb_amd.optim.LossScaler; overflowed windows are skipped on the device.  Needs fused_adam
+    max_grad_norm=None,  # guarded optimizer steps for every compute_dtype (ir2rgb_amd.optim.GradGuard): per optimizer a gradient with an inf
+                         # or NaN skips the step, a finite one is clipped to this global L2 norm -- decided on the device.  A number for
+                         # every optimizer, float("inf") (guard, never clip) or {"G": x, "D": y, "D_T": z} (a missing key: inf).  The
+                         # norms come back from train_window as GN_G, GN_D, GN_D_T{s}.  Needs fused_adam.  None: nothing changes
     ema_decay=None,      # a number in [0, 1): trainer.ema (ir2rgb_amd.optim.ParamEMA) averages every generator's parameters after each
                          # generator step, one launch per window; a loss-scaled window that was skipped skips the average too (decided
                          # on the device).  trainer.ema_generators() are the averaged networks for inference.  None: nothing is allocated
@@ -135,6 +140,7 @@ class Vid2VidTrainer:
         o.update(overrides)
         check_loss_scale_option(o["loss_scale"], o["fused_adam"])     # (a ValueError before anything is built)
         check_ema_option(o["ema_decay"])
+        self._max_norms = check_grad_guard_option(o["max_grad_norm"], o["fused_adam"])
         if o["lr_policy"] not in ("reference", "all"):
             raise ValueError(f"lr_policy: \"reference\" or \"all\", got {o['lr_policy']!r}")
         self.opt, self.device, self.world = o, device, world_size
@@ -199,6 +205,13 @@ class Vid2VidTrainer:
         self.optimizer_D_T = [self._make_optimizer(g.params, o["lr"], self._rule_DT[1]) for g in self.grads_DT]
         self.loss_scaler = make_loss_scaler(o["loss_scale"], device)
         self._register_scaler_tables()
+        # one guard per optimizer (max_grad_norm), in the order of its family; a replaced guard's counters are carried here
+        self.grad_guards = self._stepped = None
+        self._guard_carry = {"steps": 0, "clipped": 0, "skipped": 0}
+        if self._max_norms is not None:
+            self.grad_guards = {"G": GradGuard(self.optimizer_G, self._max_norms["G"]),
+                                "D": GradGuard(self.optimizer_D, self._max_norms["D"]),
+                                "D_T": [GradGuard(o_, self._max_norms["D_T"]) for o_ in self.optimizer_D_T]}
         # the average of ALL generators' parameters, whatever niter_fix_global says: a fixed scale's average equals its
         # parameters (p == e leaves e as it is) until update_fixed_params(), which leaves the average alone
         self.ema = self._ema_netG = None
@@ -248,6 +261,27 @@ class Vid2VidTrainer:
         if self.loss_scaler is not None:
             self.loss_scaler.forget_tables()
             self._register_scaler_tables()
+        if self.grad_guards is not None:        # (reads the old guard's counters: synchronises, between epochs)
+            old = self.grad_guards["G"].stats()
+            for k in self._guard_carry:
+                self._guard_carry[k] += old[k]
+            self.grad_guards["G"] = GradGuard(self.optimizer_G, self._max_norms["G"])
+            self._stepped = None
+
+    def grad_guard_stats(self):
+        """{"G": {...}, "D": {...}, "D_T": [{...}, ...]}: every guard's ``GradGuard.stats()`` (``max_grad_norm``), the
+        generator's counters including those of the guard ``update_fixed_params`` replaced.  Synchronises."""
+        if self.grad_guards is None:
+            raise ValueError("grad_guard_stats: the trainer was built without max_grad_norm")
+        g = self.grad_guards["G"].stats()
+        for k, v in self._guard_carry.items():
+            g[k] += v
+        return {"G": g, "D": self.grad_guards["D"].stats(), "D_T": [x.stats() for x in self.grad_guards["D_T"]]}
+
+    def decided_optimizers(self):
+        """The optimizers stepped in the last window when their steps were guarded (what ``LossLog.push`` asks whether
+        the window was skipped); None without ``max_grad_norm``: the log then asks the loss scaler, if there is one."""
+        return self._stepped
 
     def ema_generators(self):
         """The averaged generators (``ema_decay``): modules built once with the trainer's options whose parameters ARE the
@@ -734,8 +768,13 @@ class Vid2VidTrainer:
 
     def optimizer_steps(self, n_temporal):
         """The three ``optimizer.step()`` of train_vid2vid.py:104-111, then one launch refreshing every packed weight."""
-        scaler = self.loss_scaler
-        step = (lambda o: o.step()) if scaler is None else (lambda o: o.step(scaler))  # noqa: E731
+        scaler, guards = self.loss_scaler, self.grad_guards
+        if guards is not None:       # (with or without a scaler: check, clip and step, or skip, per optimizer)
+            by_opt = {id(g.optimizer): g for g in [guards["G"], guards["D"]] + guards["D_T"]}
+            step = lambda o: o.step(scaler, by_opt[id(o)])  # noqa: E731
+            self._stepped = [self.optimizer_G, self.optimizer_D] + self.optimizer_D_T[:n_temporal]
+        else:
+            step = (lambda o: o.step()) if scaler is None else (lambda o: o.step(scaler))  # noqa: E731
         # (world > 1: the averaged gradient is the same on every rank, so every rank takes the same skip decision)
         self.grads_G.wait()
         step(self.optimizer_G)
@@ -755,7 +794,8 @@ class Vid2VidTrainer:
     def train_window(self, input_A, input_B):
         """train_vid2vid.py:54-111 for one window.  Returns a dict of detached scalar losses: the totals ``G``, ``D``,
         ``D_T{s}`` and every term under the reference's names (``G_GAN`` ... ``W``; temporal ones with the scale
-        appended, ``G_T_GAN0`` ...).  ``self.last_outputs`` keeps (fake_B, fake_B_raw, flow, weight), detached,
+        appended, ``G_T_GAN0`` ...); with ``max_grad_norm`` also the gradient norm every stepped optimizer saw (``GN_G``,
+        ``GN_D``, ``GN_D_T{s}``: views of the guards' device state, valid until the next window).  ``self.last_outputs`` keeps (fake_B, fake_B_raw, flow, weight), detached,
         ``self.last_inputs`` (real_A, real_B, flow_ref, conf_ref): what ``ir2rgb_amd.visuals`` draws a snapshot from."""
         fake_prev_last = self.fake_B_prev
         drop_grad_dsts()                    # (gradient destinations of the previous window's discriminator outputs)
@@ -827,6 +867,9 @@ class Vid2VidTrainer:
         out.update({k: v.detach() for k, v in L.items()})
         for s, lt in zip(active, LT):
             out.update({f"{k}{s}": v.detach() for k, v in lt.items()})
+        if self.grad_guards is not None:    # the guards' device words: no launch, no copy
+            out["GN_G"], out["GN_D"] = self.grad_guards["G"].norm_tensor, self.grad_guards["D"].norm_tensor
+            out.update({f"GN_D_T{s}": self.grad_guards["D_T"][s].norm_tensor for s in range(len(loss_D_T))})
         return out
 
 
