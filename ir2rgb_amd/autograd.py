@@ -23,6 +23,7 @@ from . import _lib
 from . import conv as C
 from . import layers as L
 from . import stageplan
+from . import streamcheck as SC
 
 _DT = C._TORCH2DT
 _ADJ_DESCS = {}      # adjoint descriptors of strided convolutions (dgrad_geometry), one object per geometry
@@ -218,7 +219,11 @@ def conv_dgrad(gy, conv, spec, x_shape, weight_fn=None, tag="dgrad", out=None):
 # convolution whose weight is registered here writes its weight gradient straight into that slice and returns it, so
 # autograd adopts a tensor that already lives in the buffer and no gather copy precedes the all-reduce.  Only sound for
 # a parameter that receives ONE contribution per backward pass (the caller's promise: flatgrads.FlatGrads(direct=True)).
+# SINK_STREAMS: weight parameter -> the stream its sink was last written on.  A backward node runs on the stream of its
+# forward (the finer generators' branches: two streams), and whoever reads a range of the buffer from inside the pass --
+# the hook that puts a chunk on the wire -- has to wait for each of them (flatgrads.FlatGrads._join_writers).
 GRAD_SINKS = {}
+SINK_STREAMS = {}
 
 
 def wgrad_destination(weight, shape):
@@ -237,6 +242,7 @@ def wgrad_destination(weight, shape):
         raise ValueError("conv2d_wgrad: out must be a contiguous fp32 tensor of the weight's shape on the inputs' device")
     # (a NEW tensor object over the sink's memory: autograd adopts a gradient without cloning it only when nobody else
     # holds the object it is handed)
+    SINK_STREAMS[weight] = torch.cuda.current_stream(sink.device)     # (the caller launches on the current stream)
     return sink, False, sink.view(shape)
 
 
@@ -301,8 +307,9 @@ def wgrad_overlapped(conv, fn, *inputs):
     if not WGRAD_SIDE_STREAM or dev.type != "cuda" or not getattr(conv, "_ir2rgb_side_wgrad", False):
         return fn()
     if GRAD_SINKS and param in GRAD_SINKS:
-        # the gradient goes straight into the all-reduce buffer, and the hook that puts its chunk on the wire runs on the
-        # main stream: it must not overtake a kernel on the side stream
+        # the gradient goes straight into the all-reduce buffer, and the hook that puts its chunk on the wire waits for the
+        # streams wgrad_destination saw (SINK_STREAMS: the node's own stream, main or the generators' branch stream), not
+        # for SLOT_WGRAD: a sink is never written from there
         return fn()
     from .networks import SLOT_WGRAD, side_stream      # (networks imports this module)
     main, side = torch.cuda.current_stream(dev), side_stream(dev, SLOT_WGRAD)
@@ -536,7 +543,10 @@ def _weight_grad(ctx, xin, gy):
             return dw
 
         def wgrad():            # (conv2d_wgrad hands back the fresh tensor, or its own new view of the sink)
-            return conv_wgrad(xin, gy, wsh, spec, out=out)
+            g = conv_wgrad(xin, gy, wsh, spec, out=out)
+            if SC.ENABLED and out is not None:
+                SC.produced(out, f"grad sink {wsh}")
+            return g
     return wgrad_overlapped(conv, wgrad, xin, gy)
 
 

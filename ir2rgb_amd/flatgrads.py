@@ -4,6 +4,7 @@ import torch
 import torch.distributed as dist
 
 from . import autograd
+from . import streamcheck as SC
 
 
 class FlatGrads:
@@ -22,7 +23,13 @@ class FlatGrads:
     weights sit at the front of the buffer in parameter order, cut into chunks; a chunk goes onto the wire from the
     autograd hook of the parameter that completes it, i.e. WHILE the backward pass is still running (the generators'
     1.4 GB of residual-block gradients are produced over the last ~5 ms of their pass: the all-reduce then ends about
-    when the pass does instead of starting there); ``all_reduce_async`` sends what is left."""
+    when the pass does instead of starting there); ``all_reduce_async`` sends what is left.
+
+    Streams: a collective is ordered after the stream that is current where it is issued, and nothing else.  After the
+    pass that is every gradient (the engine joins the pass's streams before backward() returns).  Inside the pass a hook's
+    stream is ordered after ITS parameter's gradient only, while the sinks of one chunk are written on the streams of their
+    nodes -- two for a generator whose branches run on two streams (branch_streams_training): the hook first makes its
+    stream wait for every other stream that wrote into the chunk (``_join_writers``)."""
 
     def __init__(self, params, chunk_elems=32 * 1024 * 1024, world=1, direct=False):
         self.params = [p for p in params if p.requires_grad]
@@ -82,6 +89,7 @@ class FlatGrads:
                 autograd.GRAD_SINKS[self.params[i]] = self.views[i]
             else:
                 autograd.GRAD_SINKS.pop(self.params[i], None)
+                autograd.SINK_STREAMS.pop(self.params[i], None)
         self._pending, self._issued = [], []
 
     def close(self):
@@ -108,11 +116,30 @@ class FlatGrads:
                 self._pending[c] -= 1
                 if self._pending[c] == 0:
                     lo, hi, _ = self.chunks[c]
+                    self._join_writers(c)
                     self._reduce(lo, hi)
                     self._issued[c] = True
         return hook
 
+    def _join_writers(self, c):
+        """Chunk ``c`` is complete on the HOST: every weight-gradient kernel that writes into it has been queued, on the
+        stream of its node (autograd.SINK_STREAMS).  The current stream -- the one the collective will be ordered after --
+        waits for each of those that is not itself: at most the generators' branch stream in the trainer.  -> the streams
+        it waited for (none where one stream wrote the whole chunk and runs the hook)."""
+        writers = [autograd.SINK_STREAMS.get(self.params[i]) for i in self.chunks[c][2]]
+        writers = [s for s in writers if s is not None]
+        waited = []
+        if writers:
+            cur = torch.cuda.current_stream(writers[0].device)
+            for s in writers:
+                if s != cur and s not in waited:
+                    waited.append(s)
+                    cur.wait_stream(s)
+        return waited
+
     def _reduce(self, lo, hi):
+        if SC.ENABLED:      # the collective reads flat[lo:hi] after the current stream, and after nothing else
+            SC.consumed_range(self.flat, lo, hi, "all-reduce range")
         avg = dist.get_backend() == "nccl"     # RCCL averages in the collective; gloo (CPU tests) has no AVG
         self.scale_after = None if avg else 1.0 / self._world
         for i in range(lo, hi, self.chunk):
@@ -152,6 +179,9 @@ class FlatGrads:
         if world <= 1:
             return
         if src:
+            if SC.ENABLED:
+                for t in src:
+                    SC.consumed(t, "gathered gradient")
             torch._foreach_copy_(dst, src)
         # what the hooks have not sent: unfinished chunks of the sink region (merged into runs), then the gathered tail
         run = None

@@ -436,9 +436,9 @@ def bn_apply_add(a, b):
                       torch.zeros(ch, dtype=torch.float32, device=a.device))
         # shared by every later call on ANY stream (the generators run independent branches on two): the fills above
         # were queued on the current stream only, so make them visible to all streams once
-        torch.cuda.synchronize(a.device)
-        if SC.ENABLED:
+        if SC.ENABLED:      # (tagged BEFORE the host wait: a tag made after it would count as newer than what the host has seen)
             SC.produced(_UNIT[key][0], "unit scale"), SC.produced(_UNIT[key][1], "zero shift")
+        torch.cuda.synchronize(a.device)
     one, zero = _UNIT[key]
     if SC.ENABLED:
         SC.consumed(one, "unit scale"), SC.consumed(zero, "zero shift")

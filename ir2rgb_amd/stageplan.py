@@ -11,7 +11,9 @@ BatchNorm launches.  A ``StagePlan`` computes those once and then issues the SAM
 the general path, in a handful of statements (``IR2RGB_LEAN_STAGE=0`` switches it off; tests/test_stage_backward_gpu.py
 holds the two paths against each other bit for bit, forward and backward).
 
-Anything else -- and any call while the stream check or a side-stream weight gradient is on -- takes the general path.
+Anything else -- and any call while a side-stream weight gradient is on -- takes the general path.  The stream check
+(ir2rgb_amd.streamcheck) runs the plans: they tag and check the same cached buffers as the general path -- packed weights and
+the split-K workspace through the helpers both paths share, the BatchNorm running statistics and a gradient sink here.
 """
 import os
 
@@ -92,6 +94,9 @@ class StagePlan:
         for g in self.order:          # (the order the running statistics advance in)
             r = reps[g] if isinstance(reps, tuple) else reps
             sc = pv + g * c4
+            if SC.ENABLED and track:      # the launch reads and advances them (as layers.bn_finalize / bn_finalize_apply)
+                SC.consumed(bn.running_mean, "BatchNorm running statistics")
+                SC.produced(bn.running_mean, "BatchNorm running statistics")
             if self.fused:
                 rc = lib.ir2rgb_bn_finalize_apply(ps + g * per_s, rg, cout, npix, pw, pb, bias, prm if track else None,
                                                   prv if track else None, momentum, eps, sc, sc + gc4, sc + 2 * gc4, sc + 3 * gc4,
@@ -191,6 +196,7 @@ class StagePlan:
                 self._build_wgrad(conv)
             wd = self.wdesc
             out, acc, dw = A.wgrad_destination(conv.weight, self.wshape)
+            sink = out if dw is not None else None          # (the parameter's slice of a flat all-reduce buffer)
             if out is None:
                 out = dw = torch.empty(self.wshape, dtype=_F32, device=dev)
             wsn = torch.empty(self.wgrad_ws[1 if acc else 0], dtype=_F32, device=dev)
@@ -198,6 +204,8 @@ class StagePlan:
             rc = (lib.ir2rgb_conv2d_wgrad_acc if acc else lib.ir2rgb_conv2d_wgrad)(wd, x, gy, out, wsn, stream)
             if rc:
                 _lib.check(rc, "conv2d_wgrad")
+            if SC.ENABLED and sink is not None:
+                SC.produced(sink, f"grad sink {self.wshape}")
             if tok is not None:
                 C._prof_end(tok, wd, "conv_wgrad")
         # (training-mode BatchNorm removes the per-channel mean: the bias gradient is exactly zero = None)
@@ -211,7 +219,7 @@ def _autograd():
 
 def lookup(x, spec, conv, bn, fused_bn):
     """The plan of this stage call, or None when the general path has to run it."""
-    if not ENABLED or SC.ENABLED or bn is None or spec["first"] or not spec["training"]:
+    if not ENABLED or bn is None or spec["first"] or not spec["training"]:
         return None
     A = _autograd()
     if A.WGRAD_SIDE_STREAM:

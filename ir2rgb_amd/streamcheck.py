@@ -11,8 +11,20 @@ Happens-before by vector clocks, on the host, from the calls this process makes 
   * ``produced(t, what)``: the kernel just queued on the current stream writes cached buffer ``t`` -> tag (stream, count);
   * ``consumed(t)``: the kernel about to be queued on the current stream reads ``t``; if its tag belongs to another stream
     and the current stream's clock has not reached it, raise StreamOrderError;
-  * Stream.wait_stream / Stream.wait_event / Event.record / synchronize calls (patched while the check is on) move the clocks.
+  * Stream.wait_stream / Stream.wait_event / Event.record / synchronize calls (patched while the check is on) move the clocks;
+  * so does the return of ``torch.autograd.backward`` (patched too): the engine ends a pass by making the caller's stream wait
+    for every stream a leaf's gradient was accumulated on, and each of those was ordered after the node that produced the
+    gradient -- the caller's stream is then ordered after every stream that tagged a buffer DURING the pass.  Inside the
+    pass (the post-accumulate hooks) nothing of the kind holds: a hook's stream is ordered after its own parameter's
+    gradient only.
 A HIP graph replay is one node on the stream it is launched on; tags made during its capture carry the capture stream.
+
+Gradient sinks (data-parallel runs, autograd.GRAD_SINKS): a weight-gradient kernel that writes straight into its slice of a
+flat all-reduce buffer tags the slice ("grad sink <shape>") on the stream it was queued on; ``consumed_range(flat, lo, hi)``
+checks every tag inside ``flat[lo:hi]`` against the current stream -- what a collective over that range, ordered after the
+current stream only, is about to read (flatgrads.FlatGrads._reduce, from the autograd hooks and after the pass).  The cached
+plans of the common convolution stage (stageplan.StagePlan) emit the same tags as the general path: the check runs what
+production runs.
 
 Off (the default) every entry point is a constant-false test.  ``enable()`` / ``disable()`` switch it at run time
 (tests/test_streams_gpu.py runs sixteen training windows under it, and plants a violation to see it caught).
@@ -26,6 +38,7 @@ _seq = {}        # stream id -> productions so far
 _clock = {}      # stream id -> {stream id: count seen}
 _tags = {}       # (device index, data_ptr) -> (stream id, count, what)
 _patched = []
+_pass = None     # stream ids that tagged a buffer during the running backward pass (None: no pass is running)
 STATS = {"produced": 0, "consumed": 0, "cross_stream": 0}
 
 
@@ -61,6 +74,8 @@ def produced(t, what=""):
     sid = _cur(t.device)
     _seq[sid] = _seq.get(sid, 0) + 1
     _tags[(t.device.index, t.data_ptr())] = (sid, _seq[sid], what)
+    if _pass is not None:
+        _pass.add(sid)
     STATS["produced"] += 1
 
 
@@ -70,8 +85,11 @@ def consumed(t, what=""):
     tag = _tags.get((t.device.index, t.data_ptr()))
     if tag is None:
         return
+    _check(tag, _cur(t.device), what)
+
+
+def _check(tag, sid, what):
     STATS["consumed"] += 1
-    sid = _cur(t.device)
     if tag[0] == sid:
         return
     STATS["cross_stream"] += 1
@@ -83,6 +101,25 @@ def consumed(t, what=""):
             f"{seen} of that stream (no wait_stream / wait_event in between)")
 
 
+def consumed_range(flat, lo, hi, what=""):
+    """``consumed`` for every tagged buffer that starts inside ``flat[lo:hi]`` (a flat fp32 buffer; elements): the kernel
+    or collective about to be queued on the current stream reads that whole range.  -> the tags it checked."""
+    if not ENABLED or flat is None or not flat.is_cuda:
+        return ()
+    dev, base = flat.device.index, flat.data_ptr()
+    a, b = base + flat.element_size() * lo, base + flat.element_size() * hi
+    hit = [tag for (d, ptr), tag in _tags.items() if d == dev and a <= ptr < b]
+    sid = _cur(flat.device)
+    for tag in hit:
+        _check(tag, sid, what)
+    return hit
+
+
+def tag_of(t):
+    """-> (stream id, production, what) of the tracked buffer ``t``, or None: who wrote it last (for tests and reports)."""
+    return _tags.get((t.device.index, t.data_ptr())) if t is not None and t.is_cuda else None
+
+
 def forget(t):
     if ENABLED and t is not None and t.is_cuda:
         _tags.pop((t.device.index, t.data_ptr()), None)
@@ -92,6 +129,24 @@ def _patch():
     S, E = torch.cuda.Stream, torch.cuda.Event
     o_wait_stream, o_wait_event, o_record, o_ssync, o_esync, o_sync = (S.wait_stream, S.wait_event, E.record, S.synchronize,
                                                                        E.synchronize, torch.cuda.synchronize)
+    o_backward = torch.autograd.backward
+
+    def backward(*args, **kwargs):
+        # (Tensor.backward arrives here too.)  The engine's closing join, see the module docstring; a pass started from
+        # inside a pass hands its streams on to the outer one
+        global _pass
+        outer, _pass = _pass, set()
+        try:
+            r = o_backward(*args, **kwargs)
+        finally:
+            mine, _pass = _pass, outer
+        if mine:        # (a pass that raised has joined nothing)
+            clock = _clock.setdefault(_cur(), {})
+            for sid in mine:
+                _merge(clock, _view_of(sid))
+            if outer is not None:
+                outer |= mine
+        return r
 
     def wait_stream(self, other):
         _merge(_clock.setdefault(_sid(self), {}), _view_of(_sid(other)))
@@ -132,8 +187,10 @@ def _patch():
 
     S.wait_stream, S.wait_event, E.record, S.synchronize, E.synchronize, torch.cuda.synchronize = (
         wait_stream, wait_event, record, ssync, esync, sync)
+    torch.autograd.backward = backward
     _patched[:] = [(S, "wait_stream", o_wait_stream), (S, "wait_event", o_wait_event), (E, "record", o_record),
-                   (S, "synchronize", o_ssync), (E, "synchronize", o_esync), (torch.cuda, "synchronize", o_sync)]
+                   (S, "synchronize", o_ssync), (E, "synchronize", o_esync), (torch.cuda, "synchronize", o_sync),
+                   (torch.autograd, "backward", o_backward)]
 
 
 _HOST = {}       # what the host has waited for: a stream created later starts from here

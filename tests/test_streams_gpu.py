@@ -140,6 +140,12 @@ def test_sixteen_training_windows_under_the_stream_check(dev):
         torch.cuda.synchronize()
         assert tr._early_on and all(torch.isfinite(v).all() for v in out.values())
         assert SC.STATS["cross_stream"] > 0 and SC.STATS["produced"] > 1000, SC.STATS
+        # the check ran what production runs: the stages' cached plans (ir2rgb_amd.stageplan), not the general path alone
+        convs = [m for net in tr.netG + [tr.netD] + tr.netD_T for m in net.modules()
+                 if isinstance(m, (torch.nn.Conv2d, torch.nn.ConvTranspose2d))]
+        planned = [m for m in convs if any(m.__dict__.get("_ir2rgb_plans", {}).values())]
+        print(f"convolutions with a cached stage plan: {len(planned)} of {len(convs)}")
+        assert planned, "no convolution stage ran from its cached plan under the stream check"
         # ... and an inference forward on two streams right after the training step that rewrote the weights
         with torch.no_grad():
             b, t, c, h, w_ = A[:, :3].shape
