@@ -422,26 +422,39 @@ int ir2rgb_adam_step(const void *table, const void *blocks, int nblocks, float l
                      int step, void *stream);
 
 /* ------------------------------------------------------------------------------------------
- * Dynamic loss scaling for f16 training, decided on the device (loss_scale.hip).  The loss is multiplied by
- * `scale` before backward(); the step then (1) checks the scaled gradient for inf / NaN, (2) takes the Adam step
- * on g * inv_scale or leaves p, m, v and the step count alone, (3) updates the scale by torch._amp_update_scale_'s
- * rule.  The host never reads the decision: the step count, the coefficients of the step being taken and the
- * scale live in two device blocks, laid out as the structs below (plain C layout; ir2rgb_loss_scale_state_bytes
- * answers their sizes, so that a caller need not repeat them).
+ * Checked optimizer steps, decided on the device (adam.hip; the scale's update: loss_scale.hip).  f16 training
+ * multiplies its losses by `scale` before backward() (dynamic loss scaling); any compute dtype may guard its steps.  Per
+ * optimizer and window the step (1) reads the stored gradient once: finite? sum of squares, (2) applies the rule below,
+ * (3) takes the Adam step on g * factor or -- after an inf or a NaN -- leaves p, m, v and the step count alone bit for
+ * bit; once per window (4) the scale moves by torch._amp_update_scale_'s rule.  The host never reads the decision: the
+ * step count, the coefficients of the step being taken, the factor and the scale live in device blocks, laid out as the
+ * structs below (plain C layout; the *_state_bytes queries answer their sizes, so that a caller need not repeat them).
+ * With g the stored gradient (of the scaled loss when scaler_state is given) and inv = scaler_state's inv_scale, or
+ * exactly 1 when scaler_state is NULL, all in double:
+ *     norm = sqrt(sum g^2) * inv,  c = min(1, max_norm / (norm + 1e-6)),  factor = (float)(inv * c)
+ * and the step is ir2rgb_adam_step on fl(g * factor), one rounded product per element.  This is
+ * torch.nn.utils.clip_grad_norm_ applied after the unscaling, except that torch evaluates c in fp32.  max_norm +inf
+ * never clips: c is exactly 1 and factor is inv_scale, or 1.0 without a scaler.  c < 1 counts as clipped.
  *   table, blocks, nblocks : as for ir2rgb_adam_step
- *   partial   : device scratch of ir2rgb_grad_check_partial_bytes(nblocks) bytes, 8-byte aligned: one
- *               { double sumsq; float nonfinite; float reserved; } row per workgroup, summed in row order
- *   opt_state : ir2rgb_adam_state, 8-byte aligned, one per optimizer;  scaler_state : ir2rgb_loss_scale_state,
- *               4-byte aligned, one per trainer.  Both are written by the kernels only.
- * IR2RGB_EINVAL: a NULL pointer, nblocks < 0, a beta outside [0, 1), count outside [0, 8], growth_interval < 0,
- * growth < 1, backoff outside (0, 1]; IR2RGB_EALIGN: partial / opt_state / opt_states off an 8-byte boundary,
+ *   partial     : device scratch of ir2rgb_grad_check_partial_bytes(nblocks) bytes, 8-byte aligned: one
+ *                 { double sumsq; float nonfinite; float reserved; } row per workgroup, summed in row order
+ *   opt_state   : ir2rgb_adam_state, 8-byte aligned, one per optimizer.  ir2rgb_loss_scale_update, ir2rgb_ema_step and
+ *                 ir2rgb_loss_log_push read the skip decision (found_inf) from it
+ *   guard_state : ir2rgb_grad_guard_state, 4-byte aligned, zeroed by the caller, one per optimizer, or NULL (no figures
+ *                 and counters are kept).  After a non-finite gradient grad_norm is that gradient's (inf or NaN),
+ *                 clip_coef and factor are 0, `skipped` is incremented and `steps` is not
+ *   scaler_state : ir2rgb_loss_scale_state, 4-byte aligned, one per trainer, or NULL (inv is 1)
+ * All three blocks are written by the kernels only.
+ * IR2RGB_EINVAL: NULL table / blocks / partial / opt_state, NULL scaler_state / opt_states of the update,
+ * nblocks < 0, a beta outside [0, 1), max_norm <= 0 or NaN, count outside [0, 8], growth_interval < 0, growth < 1,
+ * backoff outside (0, 1]; IR2RGB_EALIGN: partial / opt_state / opt_states off an 8-byte boundary, guard_state /
  * scaler_state off a 4-byte one.  Both before any launch.
  * ------------------------------------------------------------------------------------------ */
 typedef struct ir2rgb_adam_state {
     int step;            /* successful (not skipped) steps so far */
     float step_size, beta1, beta2, omb1, omb2, bc2_sqrt, eps;   /* coefficients of the step being taken (AdamCoef) */
     float found_inf;     /* 1 when the last checked gradient held an inf or a NaN, else 0 */
-    int reserved;
+    float factor;        /* what the step multiplies every stored gradient element by: (float)(inv * c); 0 after found_inf */
     double grad_sumsq;   /* sum of squares of the last checked gradient, unscaled (x inv_scale^2) */
 } ir2rgb_adam_state;
 
@@ -451,67 +464,38 @@ typedef struct ir2rgb_loss_scale_state {
     int skipped;              /* windows skipped so far (for logging) */
 } ir2rgb_loss_scale_state;
 
-/* Size in bytes of ir2rgb_adam_state (which 0) or ir2rgb_loss_scale_state (which 1); IR2RGB_EINVAL otherwise. */
-long ir2rgb_loss_scale_state_bytes(int which);
-long ir2rgb_grad_check_partial_bytes(int nblocks);
-/* Two launches.  Every workgroup of the first reads its chunk of g only (16-byte loads where adam_kernel takes them) and
- * writes its partial row: finiteness decided per element from the value, squares accumulated in double in a fixed
- * order, no atomics.  The second (one workgroup) sums the rows and writes found_inf and
- * grad_sumsq = sumsq * inv_scale^2; if the gradient is finite it advances `step` and evaluates that step's
- * coefficients in double from lr, beta1, beta2, eps -- the expressions of ir2rgb_adam_step's host code.
- * nblocks 0: the second launch alone (a finite, empty gradient). */
-int ir2rgb_grad_check(const void *table, const void *blocks, int nblocks, void *partial, void *opt_state,
-                      const void *scaler_state, float lr, float beta1, float beta2, float eps, void *stream);
-/* ir2rgb_adam_step on g * inv_scale with the coefficients ir2rgb_grad_check left in opt_state; touches nothing when
- * opt_state's found_inf is set. */
-int ir2rgb_adam_step_scaled(const void *table, const void *blocks, int nblocks, const void *opt_state,
-                            const void *scaler_state, void *stream);
-/* opt_states: device array of `count` (<= 8) addresses of the ir2rgb_adam_state blocks stepped this window.  Any
- * found_inf: scale *= backoff, tracker 0, skipped += 1.  Otherwise the tracker is incremented and, when it reaches
- * growth_interval, reset, with scale *= growth unless that product is not finite.  growth_interval 0: a static
- * scale -- the scale and the tracker never change, skipped still counts. */
-int ir2rgb_loss_scale_update(void *scaler_state, const void *opt_states, int count, float growth, float backoff,
-                             int growth_interval, void *stream);
-
-/* ------------------------------------------------------------------------------------------
- * Guarded optimizer steps for every compute dtype (grad_guard.hip): per optimizer and window a gradient that holds an
- * inf or a NaN skips the step, a finite one is clipped to a global L2 norm -- decided on the device, like the
- * loss-scaled step, whose check kernel, partial rows and ir2rgb_adam_state these entry points share.  With g the stored
- * gradient (of the scaled loss when scaler_state is given) and inv = scaler_state's inv_scale, or exactly 1 when
- * scaler_state is NULL, all in double:
- *     norm = sqrt(sum g^2) * inv,  c = min(1, max_norm / (norm + 1e-6)),  factor = (float)(inv * c)
- * and the step is ir2rgb_adam_step on fl(g * factor), one rounded product per element.  This is
- * torch.nn.utils.clip_grad_norm_ applied after the unscaling, except that torch evaluates c in fp32.  max_norm +inf
- * never clips: c is exactly 1 and factor is inv_scale, or 1.0 without a scaler.  c < 1 counts as clipped.
- *   guard_state : ir2rgb_grad_guard_state, 4-byte aligned, zeroed by the caller, one per optimizer, written by the
- *                 kernels only.  After a non-finite gradient grad_norm is that gradient's (inf or NaN), clip_coef and
- *                 factor are 0, `skipped` is incremented and `steps` is not; p, m, v and opt_state's step stay bit for bit.
- *   table, blocks, nblocks, partial, opt_state : as for ir2rgb_grad_check, which this call replaces (opt_state is
- *                 left exactly as ir2rgb_grad_check leaves it, so ir2rgb_loss_scale_update, ir2rgb_ema_step and
- *                 ir2rgb_loss_log_push read the skip decision where they always did)
- * IR2RGB_EINVAL: a NULL pointer other than scaler_state, nblocks < 0, a beta outside [0, 1), max_norm <= 0 or NaN;
- * IR2RGB_EALIGN: partial / opt_state off an 8-byte boundary, guard_state / scaler_state off a 4-byte one.  Both before
- * any launch.
- * ------------------------------------------------------------------------------------------ */
 typedef struct ir2rgb_grad_guard_state {
     float grad_norm;     /* unscaled global L2 norm of the last checked gradient */
     float clip_coef;     /* c of the last check (1 when nothing was clipped, 0 after a skipped step) */
-    float factor;        /* what the step multiplied the stored gradient by: (float)(inv_scale * c) */
+    float factor;        /* opt_state's factor of the last check */
     int steps;           /* steps taken under this guard */
     int clipped;         /* of those, steps with c < 1 */
     int skipped;         /* steps skipped because the gradient held an inf or a NaN */
     int reserved[2];
 } ir2rgb_grad_guard_state;
 
+/* Size in bytes of ir2rgb_adam_state (which 0) or ir2rgb_loss_scale_state (which 1); IR2RGB_EINVAL otherwise. */
+long ir2rgb_loss_scale_state_bytes(int which);
 long ir2rgb_grad_guard_state_bytes(void);
-/* ir2rgb_grad_check's two launches with the rule above in the second one. */
-int ir2rgb_grad_guard_check(const void *table, const void *blocks, int nblocks, void *partial, void *opt_state,
-                            void *guard_state, const void *scaler_state, float max_norm, float lr, float beta1, float beta2,
-                            float eps, void *stream);
-/* ir2rgb_adam_step on g * guard_state's factor with the coefficients ir2rgb_grad_guard_check left in opt_state; touches
- * nothing when opt_state's found_inf is set. */
-int ir2rgb_adam_step_guarded(const void *table, const void *blocks, int nblocks, const void *opt_state,
-                             const void *guard_state, void *stream);
+long ir2rgb_grad_check_partial_bytes(int nblocks);
+/* Two launches.  Every workgroup of the first reads its chunk of g only (16-byte loads where adam_kernel takes them) and
+ * writes its partial row: finiteness decided per element from the value, squares accumulated in double in a fixed
+ * order, no atomics.  The second (one workgroup) sums the rows and writes found_inf, grad_sumsq = sumsq * inv^2 and
+ * factor, and guard_state when it is given; if the gradient is finite it advances `step` and evaluates that step's
+ * coefficients in double from lr, beta1, beta2, eps -- the expressions of ir2rgb_adam_step's host code.
+ * nblocks 0: the second launch alone (a finite, empty gradient). */
+int ir2rgb_grad_check(const void *table, const void *blocks, int nblocks, void *partial, void *opt_state,
+                      void *guard_state, const void *scaler_state, float max_norm, float lr, float beta1, float beta2,
+                      float eps, void *stream);
+/* ir2rgb_adam_step on g * factor with the coefficients ir2rgb_grad_check left in opt_state; touches nothing when
+ * opt_state's found_inf is set.  nblocks 0: IR2RGB_OK, nothing is launched. */
+int ir2rgb_adam_step_checked(const void *table, const void *blocks, int nblocks, const void *opt_state, void *stream);
+/* opt_states: device array of `count` (<= 8) addresses of the ir2rgb_adam_state blocks stepped this window.  Any
+ * found_inf: scale *= backoff, tracker 0, skipped += 1.  Otherwise the tracker is incremented and, when it reaches
+ * growth_interval, reset, with scale *= growth unless that product is not finite.  growth_interval 0: a static
+ * scale -- the scale and the tracker never change, skipped still counts. */
+int ir2rgb_loss_scale_update(void *scaler_state, const void *opt_states, int count, float growth, float backoff,
+                             int growth_interval, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Exponential moving average of the generator's parameters (ema.hip): e <- e + alpha * (p - e) for every tensor

@@ -47,7 +47,7 @@ _pjob = ctypes.POINTER(PackJob)
 class AdamState(ctypes.Structure):
     """ir2rgb_adam_state of include/ir2rgb_hip.h (device-resident; the size comes from ir2rgb_loss_scale_state_bytes(0))."""
     _fields_ = [("step", c_int)] + [(n, c_float) for n in ("step_size", "beta1", "beta2", "omb1", "omb2", "bc2_sqrt", "eps",
-                                                           "found_inf")] + [("reserved", c_int), ("grad_sumsq", ctypes.c_double)]
+                                                           "found_inf", "factor")] + [("grad_sumsq", ctypes.c_double)]
 
 
 class LossScaleState(ctypes.Structure):
@@ -140,12 +140,10 @@ PROTOTYPES = {
     "ir2rgb_adam_step": (c_int, [P, P, c_int, c_float, c_float, c_float, c_float, c_int, P]),
     "ir2rgb_loss_scale_state_bytes": (c_long, [c_int]),
     "ir2rgb_grad_check_partial_bytes": (c_long, [c_int]),
-    "ir2rgb_grad_check": (c_int, [P, P, c_int, P, P, P, c_float, c_float, c_float, c_float, P]),
-    "ir2rgb_adam_step_scaled": (c_int, [P, P, c_int, P, P, P]),
-    "ir2rgb_loss_scale_update": (c_int, [P, P, c_int, c_float, c_float, c_int, P]),
     "ir2rgb_grad_guard_state_bytes": (c_long, []),
-    "ir2rgb_grad_guard_check": (c_int, [P, P, c_int, P, P, P, P, c_float, c_float, c_float, c_float, c_float, P]),
-    "ir2rgb_adam_step_guarded": (c_int, [P, P, c_int, P, P, P]),
+    "ir2rgb_grad_check": (c_int, [P, P, c_int, P, P, P, P, c_float, c_float, c_float, c_float, c_float, P]),
+    "ir2rgb_adam_step_checked": (c_int, [P, P, c_int, P, P]),
+    "ir2rgb_loss_scale_update": (c_int, [P, P, c_int, c_float, c_float, c_int, P]),
     "ir2rgb_ema_state_bytes": (c_long, []),
     "ir2rgb_ema_step": (c_int, [P, P, c_int, P, P, c_float, c_int, P]),
     "ir2rgb_loss_log_push": (c_int, [P, ctypes.c_uint, c_int, P, c_int, P, P, c_int, P]),
@@ -275,6 +273,17 @@ def query(name, *args):
     if n < 0:
         check(int(n), name[7:])
     return n
+
+
+def struct_to_device(st, tensor):
+    """The bytes of a ctypes struct (``AdamState`` ...) into the device tensor that holds it (a blocking copy)."""
+    import torch
+    tensor.copy_(torch.frombuffer(bytearray(bytes(st)), dtype=tensor.dtype))
+
+
+def struct_from_device(cls, tensor):
+    """The ctypes struct ``cls`` a device tensor holds (synchronises)."""
+    return cls.from_buffer_copy(tensor.cpu().numpy().tobytes())
 
 
 def require_device(*tensors, dtype=None):

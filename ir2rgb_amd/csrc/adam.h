@@ -1,6 +1,5 @@
-// adam.h -- what adam.hip (the plain step), loss_scale.hip (the loss-scaled step) and grad_guard.hip (the guarded step,
-// through grad_check.h) share: the table row, the
-// coefficients of one step, the update of one element and the three paths of one (tensor, chunk) workgroup.
+// adam.h -- what the two step kernels of adam.hip (plain and checked) share, and the chunk size ema.hip walks by: the
+// table row, the coefficients of one step, the update of one element and the three paths of one (tensor, chunk) workgroup.
 #pragma once
 #include "common.h"
 
@@ -35,8 +34,8 @@ static __host__ __device__ inline AdamCoef adam_coef(float lr, float beta1, floa
 
 #ifdef __HIPCC__
 // One element.  Every product-sum is spelled out and contraction is off inside, so that the rounding does not hang on
-// what the compiler happens to fuse around it: adam_kernel and adam_scaled_kernel then run the same arithmetic by
-// construction (with equal coefficients the scaled step on g is the plain step on g * inv_scale bit for bit).  The
+// what the compiler happens to fuse around it: adam_kernel and adam_checked_kernel then run the same arithmetic by
+// construction (with equal coefficients the checked step on g is the plain step on g * factor bit for bit).  The
 // forms are the ones the compiler had chosen for adam_kernel before they were pinned: v = fma(g, omb2 g, beta2 v) and
 // p = fma(-step_size, m / denom, p) everywhere; m = fma(omb1, g, beta1 m) on the two float4 paths (FUSED_M) and
 // beta1 m + omb1 g with both products rounded on the element-wise ones.
@@ -52,7 +51,7 @@ __device__ __forceinline__ void adam_one(float &p, float g, float &m, float &v, 
     p = __builtin_fmaf(-step_size, m / denom, p);
 }
 
-// One workgroup of 256 lanes on its (tensor, chunk).  SCALED: the gradient enters as g * inv_scale (the guarded step
+// One workgroup of 256 lanes on its (tensor, chunk).  SCALED: the gradient enters as g * inv_scale (the checked step
 // passes its factor, inv_scale times the clip coefficient); otherwise inv_scale is not read.
 template <bool SCALED>
 __device__ __forceinline__ void adam_block(const AdamTensor *__restrict__ table, const int2 *__restrict__ blocks,

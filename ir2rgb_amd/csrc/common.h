@@ -54,6 +54,9 @@ static inline ConvView conv_view(const ir2rgb_conv_desc *d) {
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
+// p is off an a-byte boundary (a a power of two); NULL is aligned
+static inline bool misaligned(const void *p, unsigned a) { return ((uintptr_t)p & (a - 1)) != 0; }
+
 // grid size for HBM-bound grid-stride kernels: enough blocks to fill 256 CUs x 8 blocks.
 static inline int stream_grid(long work_items, int block) {
     long g = (work_items + block - 1) / block;
@@ -117,6 +120,17 @@ __device__ __forceinline__ unsigned fdiv(unsigned n, FastDiv f) {
     const unsigned t = __umulhi(f.m, n);
     return (t + ((n - t) >> 1)) >> f.sh;
 }
+
+// inf or NaN: decided from the value's exponent field (3e38 is finite although its square is not a float)
+__device__ __forceinline__ bool nonfinite(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
+
+// fixed-order sum over the 64 lanes of a wave (lane 0 holds the total)
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d, 64);
+    return v;
+}
+
 // sum over the 16 lanes of a DPP row (all lanes end with the row total): two quad permutes, a
 // half-row mirror and a row mirror, each folded into the v_add as a DPP operand.
 __device__ __forceinline__ float row16_sum(float v) {

@@ -122,7 +122,7 @@ extern "C" long ir2rgb_ema_state_bytes(void) { return (long)sizeof(ir2rgb_ema_st
 extern "C" int ir2rgb_ema_step(const void *table, const void *blocks, int nblocks, void *ema_state, const void *opt_state,
                                float beta, int warmup, void *stream) {
     if (!table || !blocks || !ema_state || nblocks < 0 || !(beta >= 0.f && beta < 1.f)) return IR2RGB_EINVAL;
-    if (((uintptr_t)ema_state & 3) != 0 || ((uintptr_t)opt_state & 7) != 0) return IR2RGB_EALIGN;
+    if (misaligned(ema_state, 4) || misaligned(opt_state, 8)) return IR2RGB_EALIGN;
     if (nblocks == 0) return IR2RGB_OK;
     ema_prepare_kernel<<<1, 64, 0, as_stream(stream)>>>((ir2rgb_ema_state *)ema_state, (const ir2rgb_adam_state *)opt_state,
                                                         beta, warmup != 0);

@@ -84,7 +84,7 @@ class LossLog:
                     self.state, self._opts if n_opts else None, n_opts)
 
     def _fetch_state(self):
-        return _lib.LossLogState.from_buffer_copy(self.state.cpu().numpy().tobytes())
+        return _lib.struct_from_device(_lib.LossLogState, self.state)
 
     def read(self):
         """-> {"count": windows pushed so far, "skipped": windows skipped since the previous read, "last": {name: value},

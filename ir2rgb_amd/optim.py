@@ -6,12 +6,11 @@ betas=(opt.beta1, 0.999))``).  Moments live in two flat fp32 buffers; a device t
 {param, grad, exp_avg, exp_avg_sq, numel} rows is refreshed with the current gradient pointers before
 every step (one small asynchronous copy from pinned memory).
 
-f16 training scales its losses (``LossScaler``; libir2rgb_hip.so: loss_scale.hip): ``FusedAdam.step(scaler)`` then checks
-the scaled gradient on the device, steps on ``g * inv_scale`` or skips, and ``LossScaler.update`` applies
-``torch._amp_update_scale_``'s rule -- the decision, the step count and the scale never visit the host.
-
-``GradGuard`` (libir2rgb_hip.so: grad_guard.hip) guards the steps of every compute dtype: ``FusedAdam.step(scaler, guard)``
-skips the step on an inf or NaN and clips a finite gradient to a global L2 norm, with or without a scaler, on the device.
+``FusedAdam.step(scaler, guard)`` is the checked step (adam.hip), decided on the device.  f16 training scales its losses
+(``LossScaler``): the step checks the scaled gradient, steps on ``g * inv_scale`` or skips, and ``LossScaler.update``
+(loss_scale.hip) applies ``torch._amp_update_scale_``'s rule.  ``GradGuard`` guards the steps of every compute dtype: the
+step is skipped on an inf or NaN and a finite gradient is clipped to a global L2 norm, with or without a scaler.  The
+decision, the step count and the scale never visit the host.
 
 ``ParamEMA`` (libir2rgb_hip.so: ema.hip) keeps an exponential moving average of a parameter list in one more launch per
 step; after a loss-scaled step it reads that step's skip decision from the optimizer's device state.
@@ -24,6 +23,13 @@ import torch
 
 from . import _lib
 from . import streamcheck as SC
+
+
+def _chunk_blocks(params, device):
+    """The (tensor, chunk) pairs of a parameter list, one per workgroup of a table kernel -> int32 [nblocks, 2]."""
+    chunk = _lib.lib().ir2rgb_adam_chunk_elems()
+    blocks = [(i, c) for i, p in enumerate(params) for c in range((p.numel() + chunk - 1) // chunk)]
+    return torch.tensor(blocks, dtype=torch.int32, device=device).reshape(-1, 2)
 
 
 class FusedAdam:
@@ -45,14 +51,11 @@ class FusedAdam:
         n = sum(p.numel() for p in self.params)
         self.exp_avg = torch.zeros(n, dtype=torch.float32, device=dev)
         self.exp_avg_sq = torch.zeros(n, dtype=torch.float32, device=dev)
-        lib = _lib.lib()
-        chunk = lib.ir2rgb_adam_chunk_elems()
         rows = np.zeros((len(self.params), 5), dtype=np.int64)
-        blocks, off = [], 0
+        off = 0
         for i, p in enumerate(self.params):
             k = p.numel()
             rows[i] = (p.data_ptr(), 0, self.exp_avg.data_ptr() + 4 * off, self.exp_avg_sq.data_ptr() + 4 * off, k)
-            blocks += [(i, c) for c in range((k + chunk - 1) // chunk)]
             off += k
         # two pinned staging copies used alternately: the host may run a step ahead of the GPU, and a
         # staging buffer is rewritten only after the asynchronous copy that last read it has completed
@@ -60,13 +63,13 @@ class FusedAdam:
         self._rows_np = [t.numpy() for t in self._rows_host]
         self._copied = [None, None]
         self._rows_dev = torch.empty_like(self._rows_host[0], device=dev)
-        self._blocks = torch.tensor(blocks, dtype=torch.int32, device=dev)
+        self._blocks = _chunk_blocks(self.params, dev)
         self._ptrs = [p.data_ptr() for p in self.params]
         self.device = dev
         self._flip = 0
-        # loss-scaled and guarded steps only (scaled_state): ir2rgb_adam_state on the device and the check kernel's partial rows
+        # checked steps only (scaled_state): ir2rgb_adam_state on the device and the check kernel's partial rows
         self._state = self._partial = None
-        self._on_device = False          # the step count lives in _state[0] (loss-scaled / guarded steps) / in step_count
+        self._on_device = False          # the step count lives in _state[0] (checked steps) / in step_count
         # the last step() took a scaler or a guard: its skip decision is in scaled_state() (ParamEMA.update, LossLog.push)
         self.last_step_scaled = False
 
@@ -142,8 +145,7 @@ class FusedAdam:
             nbytes = _lib.query("ir2rgb_grad_check_partial_bytes", self._blocks.shape[0])
             self._partial = torch.zeros(nbytes // 8, dtype=torch.float64, device=self.device)
         if not self._on_device:
-            st = _lib.AdamState(step=self.step_count)
-            self._state.copy_(torch.frombuffer(bytearray(bytes(st)), dtype=torch.int32))
+            _lib.struct_to_device(_lib.AdamState(step=self.step_count), self._state)
             self._on_device = True
         return self._state
 
@@ -154,7 +156,7 @@ class FusedAdam:
 
     def grad_stats(self):
         """(found_inf, unscaled gradient norm) of the last loss-scaled step (synchronises)."""
-        st = _lib.AdamState.from_buffer_copy(self.scaled_state().cpu().numpy().tobytes())
+        st = _lib.struct_from_device(_lib.AdamState, self.scaled_state())
         return bool(st.found_inf), math.sqrt(st.grad_sumsq) if st.grad_sumsq >= 0 else float("nan")
 
     def _refresh_table(self):
@@ -180,34 +182,28 @@ class FusedAdam:
 
     @torch.no_grad()
     def step(self, scaler=None, guard=None):
-        """One Adam step.  With a ``LossScaler`` the gradients are those of the scaled loss: they are checked on the
-        device (ir2rgb_grad_check), and the step is taken on ``g * inv_scale`` or -- an inf or NaN anywhere -- not at all
-        (ir2rgb_adam_step_scaled); the host learns neither.  With a ``GradGuard`` -- with or without a scaler -- the check
-        also clips to the guard's global norm (ir2rgb_grad_guard_check) and the step is taken on ``g * factor``
-        (ir2rgb_adam_step_guarded): two launches that replace the scaler's two."""
+        """One Adam step.  Plain (neither argument): the host evaluates the coefficients, one launch.  Checked: with a
+        ``LossScaler`` the gradients are those of the scaled loss; with a ``GradGuard`` a finite gradient is clipped to the
+        guard's global norm.  Either way the gradient is checked on the device (ir2rgb_grad_check) and the step is taken on
+        ``g * factor`` or -- an inf or NaN anywhere -- not at all (ir2rgb_adam_step_checked); the host learns neither."""
         if guard is not None and guard.optimizer is not self:
             raise ValueError("FusedAdam.step: the guard was built for another optimizer")
         self._refresh_table()
         nblocks = self._blocks.shape[0]
         self.last_step_scaled = scaler is not None or guard is not None
-        if guard is not None:
+        if self.last_step_scaled:
             state = self.scaled_state()
-            _lib.launch("ir2rgb_grad_guard_check", self.exp_avg, self._rows_dev, self._blocks, nblocks, self._partial, state,
-                        guard.state, None if scaler is None else scaler.state, guard.max_norm, self.lr, self.betas[0],
-                        self.betas[1], self.eps)
-            _lib.launch("ir2rgb_adam_step_guarded", self.exp_avg, self._rows_dev, self._blocks, nblocks, state, guard.state)
-        elif scaler is None:
-            if self._on_device:              # loss-scaled steps came before: their count moves back to the host
+            _lib.launch("ir2rgb_grad_check", self.exp_avg, self._rows_dev, self._blocks, nblocks, self._partial, state,
+                        None if guard is None else guard.state, None if scaler is None else scaler.state,
+                        math.inf if guard is None else guard.max_norm, self.lr, self.betas[0], self.betas[1], self.eps)
+            _lib.launch("ir2rgb_adam_step_checked", self.exp_avg, self._rows_dev, self._blocks, nblocks, state)
+        else:
+            if self._on_device:              # checked steps came before: their count moves back to the host
                 self._read_step_count()
                 self._on_device = False
             self.step_count += 1
             _lib.launch("ir2rgb_adam_step", self.exp_avg, self._rows_dev.data_ptr(), self._blocks.data_ptr(),
                         nblocks, self.lr, self.betas[0], self.betas[1], self.eps, self.step_count)
-        else:
-            state = self.scaled_state()
-            _lib.launch("ir2rgb_grad_check", self.exp_avg, self._rows_dev, self._blocks, nblocks, self._partial, state,
-                        scaler.state, self.lr, self.betas[0], self.betas[1], self.eps)
-            _lib.launch("ir2rgb_adam_step_scaled", self.exp_avg, self._rows_dev, self._blocks, nblocks, state, scaler.state)
         # the kernel wrote the parameters behind autograd's back: bump their version counters so that
         # caches keyed on them (the packed MFMA weights of ir2rgb_amd.layers) are refreshed
         torch.autograd.graph.increment_version(self.params)
@@ -246,10 +242,10 @@ class LossScaler:
     def _write(self, scale, tracker, skipped):
         scale = float(np.float32(scale))
         st = _lib.LossScaleState(scale=scale, inv_scale=float(np.float32(1.0 / scale)), growth_tracker=tracker, skipped=skipped)
-        self.state.copy_(torch.frombuffer(bytearray(bytes(st)), dtype=torch.float32))
+        _lib.struct_to_device(st, self.state)
 
     def _read(self):
-        return _lib.LossScaleState.from_buffer_copy(self.state.cpu().numpy().tobytes())
+        return _lib.struct_from_device(_lib.LossScaleState, self.state)
 
     def register(self, optimizers):
         """The device table of the optimizers' state addresses ``update`` hands the kernel; built once per set of
@@ -377,7 +373,7 @@ def check_grad_guard_option(value, fused_adam):
 class GradGuard:
     """The guard of one ``FusedAdam``: ``optimizer.step(scaler, guard)`` skips the step when the gradient holds an inf or a
     NaN and otherwise clips it to the global L2 norm ``max_norm`` (``float("inf")``: never), decided on the device
-    (libir2rgb_hip.so: grad_guard.hip; ``grad_guard_reference`` restates the rule).  Owns the optimizer's
+    (libir2rgb_hip.so: adam.hip; ``grad_guard_reference`` restates the rule).  Owns the optimizer's
     ir2rgb_grad_guard_state; ``norm_tensor`` is the unscaled gradient norm of the last step as a 0-dim fp32 view of it, a
     device operand for ``LossLog``.  Nothing synchronises but ``stats``."""
 
@@ -394,7 +390,7 @@ class GradGuard:
     def stats(self):
         """{steps, clipped, skipped, grad_norm, clip_coef}: steps taken, steps clipped, steps skipped, and the norm and
         coefficient of the last one checked (synchronises)."""
-        st = _lib.GradGuardState.from_buffer_copy(self.state.cpu().numpy().tobytes())
+        st = _lib.struct_from_device(_lib.GradGuardState, self.state)
         return {"steps": st.steps, "clipped": st.clipped, "skipped": st.skipped, "grad_norm": st.grad_norm, "clip_coef": st.clip_coef}
 
 
@@ -435,21 +431,16 @@ class ParamEMA:
             if p.dtype != torch.float32 or not p.is_contiguous() or p.device != dev:
                 raise ValueError("ParamEMA: contiguous fp32 parameters on one device")
         self.device = dev
-        lib = _lib.lib()
-        chunk = lib.ir2rgb_adam_chunk_elems()
         self._offsets, off = [], 0
         for p in self.params:
             self._offsets.append(off)
             off += (p.numel() + 3) // 4 * 4
         self.buf = torch.zeros(max(off, 4), dtype=torch.float32, device=dev)
         rows = np.zeros((len(self.params), 3), dtype=np.int64)
-        blocks = []
         for i, (p, o) in enumerate(zip(self.params, self._offsets)):
-            k = p.numel()
-            rows[i] = (p.data_ptr(), self.buf.data_ptr() + 4 * o, k)
-            blocks += [(i, c) for c in range((k + chunk - 1) // chunk)]
+            rows[i] = (p.data_ptr(), self.buf.data_ptr() + 4 * o, p.numel())
         self._rows_dev = torch.from_numpy(rows).to(dev)
-        self._blocks = torch.tensor(blocks, dtype=torch.int32, device=dev).reshape(-1, 2)
+        self._blocks = _chunk_blocks(self.params, dev)
         self._ptrs = [p.data_ptr() for p in self.params]
         self._views = [self.buf[o:o + p.numel()].view_as(p) for p, o in zip(self.params, self._offsets)]
         nbytes = _lib.query("ir2rgb_ema_state_bytes")
@@ -463,10 +454,10 @@ class ParamEMA:
 
     def _write(self, updates, skipped, alpha=0.0):
         st = _lib.EmaState(updates=int(updates), skipped=int(skipped), alpha=float(alpha))
-        self.state.copy_(torch.frombuffer(bytearray(bytes(st)), dtype=torch.int32))
+        _lib.struct_to_device(st, self.state)
 
     def _read(self):
-        return _lib.EmaState.from_buffer_copy(self.state.cpu().numpy().tobytes())
+        return _lib.struct_from_device(_lib.EmaState, self.state)
 
     def _touched(self):
         # the shadow changed behind autograd's back: caches keyed on the version counter (the packed MFMA weights of
@@ -564,7 +555,7 @@ def loss_scale_update_reference(scale, growth_tracker, found_inf, growth_factor,
 
 
 def grad_guard_reference(grads, max_norm, inv_scale=1.0):
-    """grad_check_kernel + grad_guard_finish_kernel's rule in torch fp64 on the CPU, over the stored gradients of ONE
+    """grad_check_kernel + grad_check_finish_kernel's rule in torch fp64 on the CPU, over the stored gradients of ONE
     optimizer (those of the scaled loss when ``inv_scale`` is a loss scaler's):
     -> (found, sumsq, norm, c, factor).  ``found``: an element with an all-ones exponent (inf or NaN).  ``sumsq``: the
     fp64 sum of squares of the stored gradients; ``norm = sqrt(sumsq) * inv_scale``; ``c = min(1, max_norm / (norm +
@@ -581,7 +572,7 @@ def grad_guard_reference(grads, max_norm, inv_scale=1.0):
 
 
 def grad_guard_rule(sumsq, max_norm, inv_scale=1.0):
-    """What grad_guard_finish_kernel derives from a finite gradient's sum of squares, the same expressions in double:
+    """What grad_check_finish_kernel derives from a finite gradient's sum of squares, the same expressions in double:
     -> (norm, c, factor), ``factor`` rounded to fp32."""
     inv = float(np.float32(inv_scale))
     norm = math.sqrt(sumsq) * inv

@@ -1,10 +1,10 @@
-"""Guarded optimizer steps on the device (csrc/grad_guard.hip, ir2rgb_amd.optim.GradGuard, the trainer's ``max_grad_norm``).
+"""Guarded optimizer steps on the device (csrc/adam.hip, ir2rgb_amd.optim.GradGuard, the trainer's ``max_grad_norm``).
 
 Kernel level: ``FusedAdam`` over hand-made parameter lists.  The list below puts every size at which the check and the
 step take another path on the 16-byte path (its moments start at a multiple of four elements) and fills the gaps with
 1- and 3-element tensors, which -- their moments off 16 bytes -- take the element-wise path, as does the tensor whose
-parameter storage is offset by 4 bytes.  Everything is compared bit for bit: with max_norm = inf against the entry points
-the guarded step replaces, with a threshold against ir2rgb_adam_step on the gradient pre-multiplied by the device's
+parameter storage is offset by 4 bytes.  Everything is compared bit for bit: with max_norm = inf against ir2rgb_adam_step
+on the unscaled gradient, with a threshold against ir2rgb_adam_step on the gradient pre-multiplied by the device's
 factor, the decision itself with ``decision_errors`` of tests/test_grad_guard_cpu.py (which shows there that it rejects
 five faulty rules).  Trainer level: training is bit-reproducible, so the guarded trainer is compared bit for bit too.
 """
@@ -122,27 +122,38 @@ def _guarded_step(ps, guard, scaler, inv):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# T1: max_norm = inf is the step it replaces, bit for bit
+# T1: max_norm = inf is the unguarded step, bit for bit
 @pytest.mark.parametrize("scale", [None, 2.0 ** 12])
 @pytest.mark.parametrize("table", list(TABLES))
 def test_infinite_threshold_is_the_unguarded_step(dev, table, scale):
+    """The reference is the plain step (ir2rgb_adam_step, the host's coefficients) on the gradient times 1 / scale, a
+    product that is exact for the power of two here.  With a scale, a third optimizer takes the step with the scaler alone
+    (no guard block): its ir2rgb_adam_state must be the guarded one's byte for byte."""
     specs = TABLES[table]
+    inv = 1.0 / (scale or 1.0)
     a, b = _Params(dev, specs, 1), _Params(dev, specs, 1)
     guard = OP.GradGuard(a.opt, INF)
-    sa = sb = None
+    sa = c = sc = None
     if scale is not None:
-        sa, sb = OP.LossScaler(dev, init_scale=scale, growth_interval=0), OP.LossScaler(dev, init_scale=scale, growth_interval=0)
+        sa, sc = OP.LossScaler(dev, init_scale=scale, growth_interval=0), OP.LossScaler(dev, init_scale=scale, growth_interval=0)
+        c = _Params(dev, specs, 1)
     for step in range(3):
         host = _host_grads(specs, 10 + step, scale or 1.0)
-        a.set_grads(host), b.set_grads(host)
-        got = _guarded_step(a, guard, sa, 1.0 / (scale or 1.0))
-        b.opt.step(sb)             # ir2rgb_adam_step, or ir2rgb_grad_check + ir2rgb_adam_step_scaled
-        assert decision_errors(got, host, INF, 1.0 / (scale or 1.0)) == []
-        assert float(got["c"]) == 1.0 and float(got["factor"]) == 1.0 / (scale or 1.0)
+        unscaled = [torch.from_numpy(g.numpy() * F(inv)) for g in host]
+        assert all(torch.equal(u.double(), g.double() * inv) for u, g in zip(unscaled, host))      # exact
+        a.set_grads(host), b.set_grads(unscaled)
+        got = _guarded_step(a, guard, sa, inv)
+        b.opt.step()               # ir2rgb_adam_step
+        assert not b.opt.last_step_scaled
+        assert decision_errors(got, host, INF, inv) == []
+        assert float(got["c"]) == 1.0 and float(got["factor"]) == inv
+        assert f32_bits(_adam_state(a.opt).factor) == f32_bits(inv)
         _assert_same_bits(a.state(), b.state(), f"{table} scale {scale} step {step + 1}")
+        if c is not None:          # scaler only (guard_state NULL) against scaler + guard at inf
+            c.set_grads(host)
+            c.opt.step(sc)
+            assert bytes(_adam_state(a.opt)) == bytes(_adam_state(c.opt))
     assert _guard_state(guard).steps == 3 and _guard_state(guard).clipped == 0 and _adam_state(a.opt).step == 3
-    if scale is not None:          # the optimizer's device state is the loss-scaled step's, byte for byte
-        assert bytes(_adam_state(a.opt)) == bytes(_adam_state(b.opt))
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -251,22 +262,21 @@ def test_entry_points_refuse_bad_arguments(dev):
     def check(**kw):
         names = ("table", "blocks", "nblocks", "partial", "opt_state", "guard_state", "scaler_state", "max_norm", "lr", "beta1",
                  "beta2", "eps")
-        return lib.ir2rgb_grad_guard_check(*[kw.get(n, v) for n, v in zip(names, good)], stream)
+        return lib.ir2rgb_grad_check(*[kw.get(n, v) for n, v in zip(names, good)], stream)
 
-    for kw in (dict(table=None), dict(blocks=None), dict(partial=None), dict(opt_state=None), dict(guard_state=None), dict(nblocks=-1),
+    for kw in (dict(table=None), dict(blocks=None), dict(partial=None), dict(opt_state=None), dict(nblocks=-1),
                dict(max_norm=0.0), dict(max_norm=-1.0), dict(max_norm=math.nan), dict(max_norm=-INF), dict(beta1=1.0), dict(beta2=-0.1)):
         assert check(**kw) == -1, kw
     for kw in (dict(partial=part.ptr + 4), dict(opt_state=st.ptr + 4), dict(guard_state=gs.ptr + 2), dict(scaler_state=sc.ptr + 2)):
         assert check(**kw) == -3, kw
-    step_good = (tab, blk, 1, st.ptr, gs.ptr)
-    for i in (0, 1, 3, 4):
-        assert lib.ir2rgb_adam_step_guarded(*[None if j == i else v for j, v in enumerate(step_good)], stream) == -1
-    assert lib.ir2rgb_adam_step_guarded(tab, blk, -1, st.ptr, gs.ptr, stream) == -1
-    assert lib.ir2rgb_adam_step_guarded(tab, blk, 1, st.ptr + 4, gs.ptr, stream) == -3
-    assert lib.ir2rgb_adam_step_guarded(tab, blk, 1, st.ptr, gs.ptr + 2, stream) == -3
-    assert lib.ir2rgb_adam_step_guarded(tab, blk, 0, st.ptr, gs.ptr, stream) == 0
-    with pytest.raises(ValueError, match="grad_guard_check"):
-        _lib.launch("ir2rgb_grad_guard_check", ps.opt.exp_avg, *good[:7], 0.0, *good[8:])
+    step_good = (tab, blk, 1, st.ptr)
+    for i in (0, 1, 3):
+        assert lib.ir2rgb_adam_step_checked(*[None if j == i else v for j, v in enumerate(step_good)], stream) == -1
+    assert lib.ir2rgb_adam_step_checked(tab, blk, -1, st.ptr, stream) == -1
+    assert lib.ir2rgb_adam_step_checked(tab, blk, 1, st.ptr + 4, stream) == -3
+    assert lib.ir2rgb_adam_step_checked(tab, blk, 0, st.ptr, stream) == 0
+    with pytest.raises(ValueError, match="grad_check"):
+        _lib.launch("ir2rgb_grad_check", ps.opt.exp_avg, *good[:7], 0.0, *good[8:])
     torch.cuda.synchronize()
     # refused before any launch: nothing was written
     assert st.bytes() == bytes(_lib.AdamState(step=4)) and gs.bytes() == bytes(_lib.GradGuardState(steps=4, clipped=1, skipped=2))
@@ -279,6 +289,14 @@ def test_entry_points_refuse_bad_arguments(dev):
     got = _lib.GradGuardState.from_buffer_copy(gs.bytes())
     assert (got.steps, got.clipped, got.skipped, got.clip_coef, got.factor) == (6, 1, 2, 1.0, 0.25)
     assert f32_bits(got.grad_norm) == f32_bits(abs(g) * 0.25)
+    # a NULL guard block is accepted, and the banded guard block that was not passed keeps its bytes
+    kept = gs.bytes()
+    assert check(guard_state=None) == 0 and check(guard_state=None, max_norm=INF, scaler_state=None) == 0
+    torch.cuda.synchronize()
+    assert gs.bytes() == kept
+    after = _lib.AdamState.from_buffer_copy(st.bytes())
+    assert (after.step, after.found_inf, after.factor) == (8, 0.0, 1.0)
+    part.bytes(), sc.bytes()
     with pytest.raises(ValueError, match="another optimizer"):
         ps.opt.step(None, OP.GradGuard(_Params(dev, TABLES["single"], 6).opt, 1.0))
 
@@ -334,7 +352,7 @@ def _windows(dev, n):
     return [(A[:, w:w + 3], Bs[:, w:w + 3]) for w in range(n)]
 
 
-STEP_ENTRIES = {"ir2rgb_adam_step", "ir2rgb_grad_check", "ir2rgb_adam_step_scaled", "ir2rgb_grad_guard_check", "ir2rgb_adam_step_guarded"}
+STEP_ENTRIES = {"ir2rgb_adam_step", "ir2rgb_grad_check", "ir2rgb_adam_step_checked"}
 
 
 def _launch_names(monkeypatch):
@@ -401,7 +419,7 @@ def test_trainer_bf16_guard_at_inf_changes_no_bit(dev, monkeypatch, bf16_runs):
     a, b = _windows(dev, 4)[3]
     tr.train_window(a, b)
     steps = {n for n in names if n in STEP_ENTRIES}
-    assert steps == {"ir2rgb_grad_guard_check", "ir2rgb_adam_step_guarded"}, steps
+    assert steps == {"ir2rgb_grad_check", "ir2rgb_adam_step_checked"}, steps
     assert tr.decided_optimizers() == _optimizers(tr)[:len(tr.decided_optimizers())]
 
 

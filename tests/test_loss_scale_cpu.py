@@ -125,13 +125,14 @@ def test_state_block_sizes_match_the_ctypes_structs():
     buf = torch.zeros(64, dtype=torch.float64)
     p = buf.data_ptr()
     assert p % 8 == 0
-    assert lib.ir2rgb_grad_check(None, p, 1, p, p, p, 2e-4, 0.5, 0.999, 1e-8, None) == -1
-    assert lib.ir2rgb_grad_check(p, p, 1, p, p, p, 2e-4, 1.0, 0.999, 1e-8, None) == -1
-    assert lib.ir2rgb_grad_check(p, p, 1, p, p + 4, p, 2e-4, 0.5, 0.999, 1e-8, None) == -3
-    assert lib.ir2rgb_grad_check(p, p, 1, p + 4, p, p, 2e-4, 0.5, 0.999, 1e-8, None) == -3
-    assert lib.ir2rgb_adam_step_scaled(p, p, -1, p, p, None) == -1
-    assert lib.ir2rgb_adam_step_scaled(p, p, 1, p + 4, p, None) == -3
-    assert lib.ir2rgb_adam_step_scaled(p, p, 0, p, p, None) == 0
+    inf = float("inf")
+    assert lib.ir2rgb_grad_check(None, p, 1, p, p, None, p, inf, 2e-4, 0.5, 0.999, 1e-8, None) == -1
+    assert lib.ir2rgb_grad_check(p, p, 1, p, p, None, p, inf, 2e-4, 1.0, 0.999, 1e-8, None) == -1
+    assert lib.ir2rgb_grad_check(p, p, 1, p, p + 4, None, p, inf, 2e-4, 0.5, 0.999, 1e-8, None) == -3
+    assert lib.ir2rgb_grad_check(p, p, 1, p + 4, p, None, p, inf, 2e-4, 0.5, 0.999, 1e-8, None) == -3
+    assert lib.ir2rgb_adam_step_checked(p, p, -1, p, None) == -1
+    assert lib.ir2rgb_adam_step_checked(p, p, 1, p + 4, None) == -3
+    assert lib.ir2rgb_adam_step_checked(p, p, 0, p, None) == 0
     assert lib.ir2rgb_loss_scale_update(p, p, 9, 2.0, 0.5, 2000, None) == -1
     assert lib.ir2rgb_loss_scale_update(p, p, 1, 0.5, 0.5, 2000, None) == -1
     assert lib.ir2rgb_loss_scale_update(p, p, 1, 2.0, 0.5, -1, None) == -1

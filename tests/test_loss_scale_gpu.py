@@ -1,4 +1,4 @@
-"""Dynamic loss scaling on the device (csrc/loss_scale.hip, ir2rgb_amd.optim.LossScaler, the trainer's ``loss_scale``).
+"""Dynamic loss scaling on the device (csrc/adam.hip, csrc/loss_scale.hip, ir2rgb_amd.optim.LossScaler, the trainer's ``loss_scale``).
 
 Kernel level: the gradient check at every path of its three-way split with inf / NaN planted where each path could miss
 them; the skipped step; the scaled step against the fp64 Adam reference under the bounds oracle/replay_ops.replay_adam
@@ -114,12 +114,21 @@ def _scaler_block(dev, scale):
                    _lib.LossScaleState(scale=scale, inv_scale=float(np.float32(1.0 / scale)), growth_tracker=0, skipped=0))
 
 
+def _factor_bits(st):
+    return int(np.float32(st.factor).view(np.int32))
+
+
+def _inv_scale_bits(scale):
+    """The bits of the inv_scale a scaler block of ``scale`` holds (_scaler_block)."""
+    return int(np.float32(1.0 / float(np.float32(scale))).view(np.int32))
+
+
 def _check(dev, tab, scale, step0):
-    """ir2rgb_grad_check on a fresh state -> (AdamState, raw state bytes, raw partial bytes, scaler block, state block)."""
+    """ir2rgb_grad_check (no guard block, max_norm inf) on a fresh state -> (AdamState, raw state bytes, raw partial bytes, scaler block, state block)."""
     st = _Banded(dev, _lib.query("ir2rgb_loss_scale_state_bytes", 0), _lib.AdamState(step=step0))
     sc = _scaler_block(dev, scale)
     part = _Banded(dev, _lib.query("ir2rgb_grad_check_partial_bytes", tab.nblocks))
-    _lib.launch("ir2rgb_grad_check", tab.table, tab.table, tab.blocks, tab.nblocks, part.ptr, st.ptr, sc.ptr, LR, B1, B2, EPS)
+    _lib.launch("ir2rgb_grad_check", tab.table, tab.table, tab.blocks, tab.nblocks, part.ptr, st.ptr, None, sc.ptr, math.inf, LR, B1, B2, EPS)
     torch.cuda.synchronize()
     raw = st.bytes()
     assert sc.bytes() == bytes(_lib.LossScaleState(scale=scale, inv_scale=float(np.float32(1.0 / scale)))), "the check wrote the scaler state"
@@ -155,6 +164,8 @@ def test_grad_check_flag_norm_repeatability_and_canaries(dev, plant):
     want_found = plant not in ("nothing", "finite_3e38")
     assert st.found_inf == (1.0 if want_found else 0.0)
     assert st.step == (6 if want_found else 7)                # the step count advances only for a finite gradient
+    # the factor the step multiplies by: the scaler block's inv_scale bit for bit, +0.0 after a non-finite gradient
+    assert _factor_bits(st) == (0 if want_found else _inv_scale_bits(scale))
     ref = float(sum((arrs[1].double() ** 2).sum() for arrs in host)) * (1.0 / scale) ** 2
     bound = (N_TOTAL + 2) * 2.0 ** -53
     if math.isfinite(ref):
@@ -199,8 +210,8 @@ def _scaled_step(dev, host_scaled, scale, step):
     st = _Banded(dev, _lib.query("ir2rgb_loss_scale_state_bytes", 0), _lib.AdamState(step=step - 1))
     sc = _scaler_block(dev, scale)
     part = _Banded(dev, _lib.query("ir2rgb_grad_check_partial_bytes", tab.nblocks))
-    _lib.launch("ir2rgb_grad_check", tab.table, tab.table, tab.blocks, tab.nblocks, part.ptr, st.ptr, sc.ptr, LR, B1, B2, EPS)
-    _lib.launch("ir2rgb_adam_step_scaled", tab.table, tab.table, tab.blocks, tab.nblocks, st.ptr, sc.ptr)
+    _lib.launch("ir2rgb_grad_check", tab.table, tab.table, tab.blocks, tab.nblocks, part.ptr, st.ptr, None, sc.ptr, math.inf, LR, B1, B2, EPS)
+    _lib.launch("ir2rgb_adam_step_checked", tab.table, tab.table, tab.blocks, tab.nblocks, st.ptr)
     torch.cuda.synchronize()
     part.bytes(), sc.bytes()
     return tab.read(), _lib.AdamState.from_buffer_copy(st.bytes())
@@ -239,7 +250,7 @@ def test_scaled_step_power_of_two(dev, k, step):
     scaled = [[p, g * scale, m, v] for p, g, m, v in host]
     assert all(torch.equal(s[1] / scale, h[1]) for s, h in zip(scaled, host))          # g * 2^k and back: exact
     got, st = _scaled_step(dev, scaled, scale, step)
-    assert st.found_inf == 0.0 and st.step == step
+    assert st.found_inf == 0.0 and st.step == step and _factor_bits(st) == _inv_scale_bits(scale)
     worst = _assert_fp64_bounds(f"scale 2^{k} step {step}", got, scaled, [h[1].double().numpy() for h in host], step)
     ulps = _ulps(_device_coef(st), _host_coef(step))
     equal = int(ulps.max()) == 0
@@ -266,7 +277,7 @@ def test_scaled_step_scale_1000(dev, step):
     host = _host_arrays(200 + step, step)
     scaled = [[p, g * scale, m, v] for p, g, m, v in host]
     got, st = _scaled_step(dev, scaled, scale, step)
-    assert st.found_inf == 0.0 and st.step == step
+    assert st.found_inf == 0.0 and st.step == step and _factor_bits(st) == _inv_scale_bits(scale)
     worst = _assert_fp64_bounds(f"scale 1000 step {step}", got, scaled, [s[1].double().numpy() / scale for s in scaled], step,
                                 dg_rel=2 * 2.0 ** -24)
     print(f"scale 1000 step {step}: worst err/bound {worst:.3g}")

@@ -1,16 +1,17 @@
-"""The guarded optimizer step beside the plain and the loss-scaled one over the full-size generators' parameter table, in
-one process:
+"""The checked optimizer step, with a guard and with a loss scaler, beside the plain one over the full-size generators'
+parameter table, in one process:
 
     python tools/microbench/grad_guard_bench.py [--scales 2] [--calls 100] [--samples 5]
 
-    guarded   ir2rgb_grad_guard_check + ir2rgb_adam_step_guarded   (check, finish, step: 32 bytes per parameter)
-    plain     ir2rgb_adam_step                                     (28 bytes per parameter)
-    scaled    ir2rgb_grad_check + ir2rgb_adam_step_scaled          (the same kernels as guarded but for the finish rule)
+    guard     ir2rgb_grad_check + ir2rgb_adam_step_checked   (check, finish, step: 32 bytes per parameter; every step clipped)
+    plain     ir2rgb_adam_step                               (28 bytes per parameter)
+    scaler    ir2rgb_grad_check + ir2rgb_adam_step_checked   (the same kernels: no guard block, max_norm inf)
 
 A sample is ``--calls`` back-to-back steps between two device events; the variants' samples alternate.  The plain step's
 bytes per second in this run is the yardstick, and the spread of its samples (max - min) the margin within which the
-guarded and the loss-scaled medians are expected to agree."""
+two checked medians are expected to agree."""
 import argparse
+import math
 import os
 import statistics
 import sys
@@ -49,15 +50,16 @@ def main():
         step[0] += 1
         _lib.launch("ir2rgb_adam_step", adam.exp_avg, adam._rows_dev, adam._blocks, nb, 2e-4, 0.5, 0.999, 1e-8, step[0])
 
-    def scaled_call():
-        _lib.launch("ir2rgb_grad_check", adam.exp_avg, adam._rows_dev, adam._blocks, nb, adam._partial, state, scaler.state,
-                    2e-4, 0.5, 0.999, 1e-8)
-        _lib.launch("ir2rgb_adam_step_scaled", adam.exp_avg, adam._rows_dev, adam._blocks, nb, state, scaler.state)
+    def checked_call(guard_state, scaler_state, max_norm):
+        _lib.launch("ir2rgb_grad_check", adam.exp_avg, adam._rows_dev, adam._blocks, nb, adam._partial, state, guard_state,
+                    scaler_state, max_norm, 2e-4, 0.5, 0.999, 1e-8)
+        _lib.launch("ir2rgb_adam_step_checked", adam.exp_avg, adam._rows_dev, adam._blocks, nb, state)
 
-    def guarded_call():
-        _lib.launch("ir2rgb_grad_guard_check", adam.exp_avg, adam._rows_dev, adam._blocks, nb, adam._partial, state, guard.state,
-                    None, guard.max_norm, 2e-4, 0.5, 0.999, 1e-8)
-        _lib.launch("ir2rgb_adam_step_guarded", adam.exp_avg, adam._rows_dev, adam._blocks, nb, state, guard.state)
+    def scaler_call():
+        checked_call(None, scaler.state, math.inf)
+
+    def guard_call():
+        checked_call(guard.state, None, guard.max_norm)
 
     def sample(fn):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -68,7 +70,7 @@ def main():
         torch.cuda.synchronize()
         return e0.elapsed_time(e1) / a.calls * 1e3      # us per call
 
-    variants = (("guarded", guarded_call, 32), ("plain", plain_call, 28), ("scaled", scaled_call, 32))
+    variants = (("guard", guard_call, 32), ("plain", plain_call, 28), ("scaler", scaler_call, 32))
     for _, fn, _ in variants:
         for _ in range(10):
             fn()
@@ -86,9 +88,9 @@ def main():
         print(f"{name:8s} TB/s: " + " ".join(f"{x:.2f}" for x in tbs) +
               f"  median {statistics.median(tbs):.2f} (min {min(tbs):.2f} max {max(tbs):.2f})")
     spread = max(us["plain"]) - min(us["plain"])
-    diff = statistics.median(us["guarded"]) - statistics.median(us["scaled"])
-    print(f"guarded / plain medians: {statistics.median(us['guarded']) / statistics.median(us['plain']):.3f} (32 / 28 = 1.143 by bytes)")
-    print(f"guarded - scaled medians: {diff:+.1f} us; the plain step's max - min spread: {spread:.1f} us")
+    diff = statistics.median(us["guard"]) - statistics.median(us["scaler"])
+    print(f"guard / plain medians: {statistics.median(us['guard']) / statistics.median(us['plain']):.3f} (32 / 28 = 1.143 by bytes)")
+    print(f"guard - scaler medians: {diff:+.1f} us; the plain step's max - min spread: {spread:.1f} us")
     st = guard.stats()
     assert st["steps"] == 10 + a.calls * a.samples and st["skipped"] == 0 and st["clipped"] == st["steps"], st
     assert all(bool(torch.isfinite(p).all()) for p in params[:4])

@@ -1,5 +1,5 @@
 """Cost of the loss-scaled optimizer step at the generator's size: ir2rgb_grad_check +
-ir2rgb_adam_step_scaled (+ ir2rgb_loss_scale_update) against ir2rgb_adam_step on the same tensors.  The bytes predict
+ir2rgb_adam_step_checked (+ ir2rgb_loss_scale_update) against ir2rgb_adam_step on the same tensors.  The bytes predict
 32 / 28 = 1.14 (one more read of the gradient); the check's two launches and the update are latency on top."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
