@@ -24,6 +24,17 @@ template <class F> static inline void with_dtype(int dtype, F &&f) {
     else f(std::integral_constant<int, IR2RGB_F16>{});
 }
 
+// The same for run-time flags that select a kernel form:  with_bool(vec, [&](auto v) { K<v.value><<<...>>>(...); });
+// f is instantiated for every value (all four pairs in the two-flag form).  A launch site whose kernel has fewer forms maps
+// the pairs it never takes onto one it has, in the template arguments, so that no further kernel is compiled.
+template <class F> static inline void with_bool(bool flag, F &&f) {
+    if (flag) f(std::true_type{});
+    else f(std::false_type{});
+}
+template <class F> static inline void with_bool(bool a, bool b, F &&f) {
+    with_bool(a, [&](auto ca) { with_bool(b, [&](auto cb) { f(ca, cb); }); });
+}
+
 // An integer environment switch (IR2RGB_CONV3X3P, IR2RGB_CONV3X3P_SPLIT, IR2RGB_CONV_DOT, IR2RGB_CONV_HALF_TILE): unset = dflt.  Callers keep
 // the value in a function-local static: the environment is read once per process.
 static inline int env_switch(const char *name, int dflt) {

@@ -17,13 +17,9 @@
 //   to 8 bit    trunc(clip((x + 1) / 2 * 255, 0, 255))       numpy: ((x + 1) / 2.0 * 255.0).clip(0, 255).astype(uint8)
 //   pooling     the statement order of avgpool3s2_fwd_kernel (pointwise.hip): rows outer, columns inner, one division
 #include "common.h"
-#include "u8.h"         // to_u8
+#include "u8.h"         // to_u8, normalise_u8, the bytes of a pixel group
 
 namespace {
-
-__device__ __forceinline__ float normalise_u8(unsigned v) {
-    return __fdiv_rn(__fsub_rn(__fdiv_rn((float)v, 255.f), 0.5f), 0.5f);
-}
 
 // history [T][plane] -> slots 1..T-1 move to 0..T-2 at element(s) e, the newest slot receives v
 template <typename V>
@@ -66,10 +62,8 @@ frame_push_kernel(const void *__restrict__ frame, float *__restrict__ hist0, flo
                 float v[C][4];
                 if (F32) {
 #pragma unroll
-                    for (int c = 0; c < C; ++c) {
-                        const float4 t = *reinterpret_cast<const float4 *>(static_cast<const float *>(frame) + ((long)c * H + y) * W + x);
-                        v[c][0] = t.x, v[c][1] = t.y, v[c][2] = t.z, v[c][3] = t.w;
-                    }
+                    for (int c = 0; c < C; ++c)
+                        unpack4(*reinterpret_cast<const float4 *>(static_cast<const float *>(frame) + ((long)c * H + y) * W + x), v[c]);
                 } else {
                     unsigned b[C];      // 4 pixels x C channels = C dwords of interleaved bytes
                     const unsigned *src = reinterpret_cast<const unsigned *>(static_cast<const uint8_t *>(frame) + ((long)y * W + x) * C);
@@ -78,10 +72,7 @@ frame_push_kernel(const void *__restrict__ frame, float *__restrict__ hist0, flo
 #pragma unroll
                     for (int p = 0; p < 4; ++p)
 #pragma unroll
-                        for (int c = 0; c < C; ++c) {
-                            const int byte = p * C + c;
-                            v[c][p] = normalise_u8((b[byte >> 2] >> (8 * (byte & 3))) & 0xffu);
-                        }
+                        for (int c = 0; c < C; ++c) v[c][p] = normalise_u8(get_byte(b, p * C + c));
                 }
 #pragma unroll
                 for (int c = 0; c < C; ++c)
@@ -121,7 +112,7 @@ frame_finish_kernel(const float *__restrict__ x, float *__restrict__ hist, uint8
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
                 const float4 t = *reinterpret_cast<const float4 *>(x + c * hw + e);
-                v[c][0] = t.x, v[c][1] = t.y, v[c][2] = t.z, v[c][3] = t.w;
+                unpack4(t, v[c]);
                 shift_in(hist, T, plane, c * hw + e, t);
             }
             if (img) {
@@ -129,10 +120,7 @@ frame_finish_kernel(const float *__restrict__ x, float *__restrict__ hist, uint8
 #pragma unroll
                 for (int p = 0; p < 4; ++p)
 #pragma unroll
-                    for (int c = 0; c < 3; ++c) {
-                        const int byte = p * 3 + c;
-                        b[byte >> 2] |= to_u8(v[c][p]) << (8 * (byte & 3));
-                    }
+                    for (int c = 0; c < 3; ++c) or_byte(b, p * 3 + c, to_u8(v[c][p]));
                 unsigned *dst = reinterpret_cast<unsigned *>(img + e * 3);
 #pragma unroll
                 for (int k = 0; k < 3; ++k) dst[k] = b[k];
@@ -148,16 +136,16 @@ frame_finish_kernel(const float *__restrict__ x, float *__restrict__ hist, uint8
     }
 }
 
-inline bool aligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 template <int C, bool F32>
 void launch_push(const void *frame, float *hist0, float *hist1, int T, int H, int W, int Ho, int Wo, bool vf, bool vp, hipStream_t s) {
     const long n_full = vf ? (long)H * (W >> 2) : (long)H * W;
     const long n_pool = hist1 ? (long)C * Ho * (vp ? (Wo >> 2) : Wo) : 0;
     const int grid = stream_grid(n_full + n_pool, 256);
-    if (vf && vp) frame_push_kernel<C, F32, true, true><<<grid, 256, 0, s>>>(frame, hist0, hist1, T, H, W, Ho, Wo, n_full, n_pool);
-    else if (vf) frame_push_kernel<C, F32, true, false><<<grid, 256, 0, s>>>(frame, hist0, hist1, T, H, W, Ho, Wo, n_full, n_pool);
-    else frame_push_kernel<C, F32, false, false><<<grid, 256, 0, s>>>(frame, hist0, hist1, T, H, W, Ho, Wo, n_full, n_pool);
+    // vp implies vf, so the pair (false, true) never arrives: it is mapped onto <false, false> and no such kernel is built
+    with_bool(vf, vp, [&](auto VF, auto VP) {
+        frame_push_kernel<C, F32, VF.value, VF.value && VP.value>
+            <<<grid, 256, 0, s>>>(frame, hist0, hist1, T, H, W, Ho, Wo, n_full, n_pool);
+    });
 }
 
 }  // namespace
@@ -166,29 +154,24 @@ extern "C" int ir2rgb_frame_push_u8(const void *frame, float *hist0, float *hist
                                     void *stream) {
     if (!frame || !hist0 || T < 1 || (C != 1 && C != 3) || H < 1 || W < 1 || (src_f32 != 0 && src_f32 != 1)) return IR2RGB_EINVAL;
     if ((long)C * H * W > 0x7fffffffL) return IR2RGB_EINVAL;
-    if (!aligned(hist0, 4) || !aligned(hist1, 4) || (src_f32 && !aligned(frame, 4))) return IR2RGB_EALIGN;
+    if (misaligned(hist0, 4) || misaligned(hist1, 4) || (src_f32 && misaligned(frame, 4))) return IR2RGB_EALIGN;
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
     // 16-byte accesses need rows that are multiples of 4 floats and 16-byte bases (the byte frame: 4*C bytes per group -> dword)
-    const bool vf = W % 4 == 0 && aligned(hist0, 16) && aligned(frame, src_f32 ? 16 : 4);
-    const bool vp = vf && hist1 && Wo % 4 == 0 && aligned(hist1, 16);
+    const bool vf = W % 4 == 0 && !misaligned(hist0, 16) && !misaligned(frame, src_f32 ? 16 : 4);
+    const bool vp = vf && hist1 && Wo % 4 == 0 && !misaligned(hist1, 16);
     hipStream_t s = as_stream(stream);
-    if (C == 1) {
-        if (src_f32) launch_push<1, true>(frame, hist0, hist1, T, H, W, Ho, Wo, vf, vp, s);
-        else launch_push<1, false>(frame, hist0, hist1, T, H, W, Ho, Wo, vf, vp, s);
-    } else {
-        if (src_f32) launch_push<3, true>(frame, hist0, hist1, T, H, W, Ho, Wo, vf, vp, s);
-        else launch_push<3, false>(frame, hist0, hist1, T, H, W, Ho, Wo, vf, vp, s);
-    }
+    with_bool(src_f32 != 0, [&](auto f32) {
+        (C == 1 ? launch_push<1, f32.value> : launch_push<3, f32.value>)(frame, hist0, hist1, T, H, W, Ho, Wo, vf, vp, s);
+    });
     return ir2rgb_launch_status();
 }
 
 extern "C" int ir2rgb_frame_finish_u8(const float *x, float *hist, uint8_t *img_u8, int T, int H, int W, void *stream) {
     if (!x || !hist || T < 1 || H < 1 || W < 1 || (long)H * W * 3 > 0x7fffffffL) return IR2RGB_EINVAL;
-    if (!aligned(x, 4) || !aligned(hist, 4)) return IR2RGB_EALIGN;
-    const long hw = (long)H * W;
-    const bool vec = W % 4 == 0 && aligned(x, 16) && aligned(hist, 16) && aligned(img_u8, 4);
+    if (misaligned(x, 4) || misaligned(hist, 4)) return IR2RGB_EALIGN;
+    const bool vec = W % 4 == 0 && !misaligned(x, 16) && !misaligned(hist, 16) && !misaligned(img_u8, 4);
+    const long n = vec ? ((long)H * W) >> 2 : (long)H * W;
     hipStream_t s = as_stream(stream);
-    if (vec) frame_finish_kernel<true><<<stream_grid(hw >> 2, 256), 256, 0, s>>>(x, hist, img_u8, T, H, W, hw >> 2);
-    else frame_finish_kernel<false><<<stream_grid(hw, 256), 256, 0, s>>>(x, hist, img_u8, T, H, W, hw);
+    with_bool(vec, [&](auto V) { frame_finish_kernel<V.value><<<stream_grid(n, 256), 256, 0, s>>>(x, hist, img_u8, T, H, W, n); });
     return ir2rgb_launch_status();
 }

@@ -15,19 +15,17 @@
 //   scale_v_kernel   workspace -> dst.  One weight row serves every byte of an output row, so a thread takes 4 consecutive
 //                    bytes of the Wc*C-byte row: one dword load per tap, four int32 accumulators, one dword store (rows whose
 //                    byte count is a multiple of 4 with 4-byte aligned bases; the scalar form of the same code otherwise).
-//                    dst is uint8 [N][Hc][Wc][C] or, through normalise_u8 of frame_io.hip, fp32 [N][C][Hc][Wc].
+//                    dst is uint8 [N][Hc][Wc][C] or, through normalise_u8 of u8.h (the one frame_io.hip applies), fp32
+//                    [N][C][Hc][Wc].
 // A pass whose size does not change gets no tables (bounds == nullptr) and copies; the copy still crops and mirrors.
 // Table indices and window positions are clamped to the table / the buffer they read, so a table that does not belong to
 // the sizes given cannot make a kernel read outside its operands; writes depend on the sizes alone.
 #include "common.h"
+#include "u8.h"         // normalise_u8, the bytes of a dword
 
 namespace {
 
 constexpr int PRECISION_BITS = 22;
-
-__device__ __forceinline__ float normalise_u8(unsigned v) {        // frame_io.hip's expression
-    return __fdiv_rn(__fsub_rn(__fdiv_rn((float)v, 255.f), 0.5f), 0.5f);
-}
 
 __device__ __forceinline__ unsigned clip8(int acc) { return (unsigned)min(max(acc >> PRECISION_BITS, 0), 255); }
 
@@ -86,7 +84,7 @@ scale_v_kernel(const uint8_t *__restrict__ ws, void *__restrict__ dst, const int
             if (VEC) {
                 const unsigned w = *reinterpret_cast<const unsigned *>(p);
 #pragma unroll
-                for (int b = 0; b < B; ++b) v[b] = (w >> (8 * b)) & 0xffu;
+                for (int b = 0; b < B; ++b) v[b] = get_byte(w, b);
             } else {
                 v[0] = p[0];
             }
@@ -103,7 +101,7 @@ scale_v_kernel(const uint8_t *__restrict__ ws, void *__restrict__ dst, const int
                 if (VEC) {
                     const unsigned w = *reinterpret_cast<const unsigned *>(p);
 #pragma unroll
-                    for (int b = 0; b < B; ++b) acc[b] += (int)((w >> (8 * b)) & 0xffu) * kk;
+                    for (int b = 0; b < B; ++b) acc[b] += (int)get_byte(w, b) * kk;
                 } else {
                     acc[0] += (int)p[0] * kk;
                 }
@@ -123,7 +121,7 @@ scale_v_kernel(const uint8_t *__restrict__ ws, void *__restrict__ dst, const int
             if (VEC) {
                 unsigned w = 0;
 #pragma unroll
-                for (int b = 0; b < B; ++b) w |= v[b] << (8 * b);
+                for (int b = 0; b < B; ++b) w = or_byte(w, b, v[b]);
                 *reinterpret_cast<unsigned *>(out) = w;
             } else {
                 out[0] = (uint8_t)v[0];
@@ -131,8 +129,6 @@ scale_v_kernel(const uint8_t *__restrict__ ws, void *__restrict__ dst, const int
         }
     }
 }
-
-inline bool aligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 // Pillow's precompute_coeffs window of output xx (double, its statement order; no contraction) -> xmin, *xmax
 inline int window(int in, int out, int xx, int *xmax) {
@@ -186,14 +182,10 @@ void launch(const uint8_t *src, void *dst, uint8_t *ws, const int *xb, const int
     const long n_h = (long)N * g.rows * Wc;
     scale_h_kernel<C><<<stream_grid(n_h, 256), 256, 0, s>>>(src, ws, xb, xc, xk, Hs, Ws, g.r0, g.rows, crop_x, Wc, flip, n_h);
     const long n_v = (long)N * Hc * (Wc * C / (vec ? 4 : 1));
-    const int grid = stream_grid(n_v, 256);
-#define IR2RGB_SCALE_V(VEC, F32) \
-    scale_v_kernel<C, VEC, F32><<<grid, 256, 0, s>>>(ws, dst, yb, yc, yk, g.r0, g.rows, crop_y, Hc, Wc, n_v)
-    if (vec && f32) IR2RGB_SCALE_V(true, true);
-    else if (vec) IR2RGB_SCALE_V(true, false);
-    else if (f32) IR2RGB_SCALE_V(false, true);
-    else IR2RGB_SCALE_V(false, false);
-#undef IR2RGB_SCALE_V
+    with_bool(vec, f32, [&](auto V, auto F32) {
+        scale_v_kernel<C, V.value, F32.value>
+            <<<stream_grid(n_v, 256), 256, 0, s>>>(ws, dst, yb, yc, yk, g.r0, g.rows, crop_y, Hc, Wc, n_v);
+    });
 }
 
 }  // namespace
@@ -219,9 +211,9 @@ extern "C" int ir2rgb_frame_scale_u8(const uint8_t *src, void *dst, uint8_t *wor
     const bool need_h = new_w != Ws, need_v = new_h != Hs;
     if (need_h ? (!xbounds || !xcoef || xksize != axis_ksize(Ws, new_w)) : (xbounds || xcoef)) return IR2RGB_EINVAL;
     if (need_v ? (!ybounds || !ycoef || yksize != axis_ksize(Hs, new_h)) : (ybounds || ycoef)) return IR2RGB_EINVAL;
-    if (!aligned(xbounds, 4) || !aligned(xcoef, 4) || !aligned(ybounds, 4) || !aligned(ycoef, 4)) return IR2RGB_EALIGN;
-    if (dst_f32 && !aligned(dst, 4)) return IR2RGB_EALIGN;
-    const bool vec = (Wc * C) % 4 == 0 && aligned(workspace, 4) && (dst_f32 || aligned(dst, 4));
+    if (misaligned(xbounds, 4) || misaligned(xcoef, 4) || misaligned(ybounds, 4) || misaligned(ycoef, 4)) return IR2RGB_EALIGN;
+    if (dst_f32 && misaligned(dst, 4)) return IR2RGB_EALIGN;
+    const bool vec = (Wc * C) % 4 == 0 && !misaligned(workspace, 4) && (dst_f32 || !misaligned(dst, 4));
     hipStream_t s = as_stream(stream);
     auto run = C == 1 ? launch<1> : launch<3>;
     run(src, dst, workspace, xbounds, xcoef, xksize, ybounds, ycoef, yksize, N, Hs, Ws, crop_y, crop_x, Hc, Wc, flip, dst_f32 != 0,

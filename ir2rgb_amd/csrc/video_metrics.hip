@@ -30,6 +30,8 @@
 // 2 partial loads per thread in flight, a reduce thread 4 x 6 dwords (rows of 4 pixels as 3 dwords when H*W is a multiple
 // of 4 and the bases are dword aligned) or 4 x 6 bytes per trip.  46 to 74 VGPRs, no scratch.
 #include "common.h"
+#include "reduce.h"     // block_reduce, partial_rows, frame_sizes_ok
+#include "u8.h"         // get_byte
 
 #pragma clang fp contract(off)
 
@@ -42,30 +44,11 @@ constexpr int NP = (HR * HC + BLOCK - 1) / BLOCK;   // haloed pixels per thread
 constexpr int P1_UNROLL = 4;                // groups per thread and trip of the reduce pass
 constexpr int P1_PIXELS = BLOCK * 16;       // pixels per partial row before a workgroup takes a second trip
 constexpr int P1_MAX_ROWS = BLOCK;          // one partial row per thread of the passes that read them
+constexpr int MIN_SIDE = 7;                 // one window
 
 __device__ __forceinline__ double gray(unsigned r, unsigned g, unsigned b) {
     // skimage.color.rgb2gray of a uint8 image: img_as_float (v / 255), then the dot product with the weights
     return ((double)r / 255.0) * 0.2125 + ((double)g / 255.0) * 0.7154 + ((double)b / 255.0) * 0.0721;
-}
-
-enum { SUM = 0, MAX = 1, MIN = 2 };
-
-// fixed-order binary tree over the workgroup; every thread returns the total
-template <int OP>
-__device__ __forceinline__ double block_reduce(double v, double *sh) {
-    const int t = threadIdx.x;
-    sh[t] = v;
-    __syncthreads();
-    for (int s = BLOCK / 2; s > 0; s >>= 1) {
-        if (t < s) {
-            const double a = sh[t], b = sh[t + s];
-            sh[t] = OP == SUM ? a + b : (OP == MAX ? fmax(a, b) : fmin(a, b));
-        }
-        __syncthreads();
-    }
-    const double r = sh[0];
-    __syncthreads();
-    return r;
 }
 
 // PPG pixels per group: 4 (their 12 bytes as 3 dwords; hw % 4 == 0, dword-aligned bases) or 1 (3 bytes)
@@ -102,9 +85,8 @@ metrics_reduce_kernel(const uint8_t *__restrict__ orig, const uint8_t *__restric
                 unsigned co[3], cp[3];
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {
-                    const int byte = p * 3 + c;
-                    co[c] = PPG == 4 ? (bo[u][byte >> 2] >> (8 * (byte & 3))) & 0xffu : bo[u][c];
-                    cp[c] = PPG == 4 ? (bp[u][byte >> 2] >> (8 * (byte & 3))) & 0xffu : bp[u][c];
+                    co[c] = PPG == 4 ? get_byte(bo[u], p * 3 + c) : bo[u][c];
+                    cp[c] = PPG == 4 ? get_byte(bp[u], p * 3 + c) : bp[u][c];
                 }
                 const double go = gray(co[0], co[1], co[2]), gp = gray(cp[0], cp[1], cp[2]);
                 const double d = go - gp;
@@ -114,9 +96,9 @@ metrics_reduce_kernel(const uint8_t *__restrict__ orig, const uint8_t *__restric
             }
         }
     }
-    mx = block_reduce<MAX>(mx, red);
-    mn = block_reduce<MIN>(mn, red);
-    ss = block_reduce<SUM>(ss, red);
+    mx = block_reduce<REDUCE_MAX, BLOCK>(mx, red);
+    mn = block_reduce<REDUCE_MIN, BLOCK>(mn, red);
+    ss = block_reduce<REDUCE_SUM, BLOCK>(ss, red);
     if (tid == 0) {
         double *row = part1 + ((long)n * rows + blockIdx.x) * 3;
         row[0] = mx, row[1] = mn, row[2] = ss;
@@ -152,8 +134,8 @@ metrics_ssim_kernel(const uint8_t *__restrict__ orig, const uint8_t *__restrict_
             gy[p] = gray(bp[k][0], bp[k][1], bp[k][2]);
         }
     }
-    const double mx = block_reduce<MAX>(tid < rows ? pmx : -INFINITY, red);     // (its barriers also publish gx / gy)
-    const double mn = block_reduce<MIN>(tid < rows ? pmn : INFINITY, red);
+    const double mx = block_reduce<REDUCE_MAX, BLOCK>(tid < rows ? pmx : -INFINITY, red);     // (its barriers also publish gx / gy)
+    const double mn = block_reduce<REDUCE_MIN, BLOCK>(tid < rows ? pmn : INFINITY, red);
     const double R = range ? given : mx - mn;
     const double C1 = (0.01 * R) * (0.01 * R), C2 = (0.03 * R) * (0.03 * R);
 
@@ -188,7 +170,7 @@ metrics_ssim_kernel(const uint8_t *__restrict__ orig, const uint8_t *__restrict_
         const double S = (A1 * A2) / (B1 * B2);
         acc += (y0 + r < H - 6 && x0 + c < W - 6) ? S : 0.0;
     }
-    acc = block_reduce<SUM>(acc, red);
+    acc = block_reduce<REDUCE_SUM, BLOCK>(acc, red);
     if (tid == 0) part2[(long)n * tiles + tile] = acc;
 }
 
@@ -209,27 +191,15 @@ metrics_finish_kernel(const double *__restrict__ range, const double *__restrict
 #pragma unroll
         for (int u = 0; u < 8; ++u) acc += base + u * BLOCK + tid < tiles ? v[u] : 0.0;
     }
-    acc = block_reduce<SUM>(acc, red);
-    const double mx = block_reduce<MAX>(tid < rows ? pmx : -INFINITY, red);
-    const double mn = block_reduce<MIN>(tid < rows ? pmn : INFINITY, red);
-    const double ss = block_reduce<SUM>(tid < rows ? pss : 0.0, red);
+    acc = block_reduce<REDUCE_SUM, BLOCK>(acc, red);
+    const double mx = block_reduce<REDUCE_MAX, BLOCK>(tid < rows ? pmx : -INFINITY, red);
+    const double mn = block_reduce<REDUCE_MIN, BLOCK>(tid < rows ? pmn : INFINITY, red);
+    const double ss = block_reduce<REDUCE_SUM, BLOCK>(tid < rows ? pss : 0.0, red);
     if (tid == 0) {
         out[(long)n * 3 + 0] = acc / (double)windows;
         out[(long)n * 3 + 1] = sqrt(ss);
         out[(long)n * 3 + 2] = range ? given : mx - mn;
     }
-}
-
-inline bool aligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
-// N rides in gridDim.y; offsets inside a frame stay below 2^31
-inline bool sizes_ok(int N, int H, int W) {
-    return N >= 1 && N <= 65535 && H >= 7 && W >= 7 && (long)H * W * 3 <= 0x7fffffffL;
-}
-
-inline int reduce_rows(long hw) {
-    const long r = (hw + P1_PIXELS - 1) / P1_PIXELS;
-    return (int)(r > P1_MAX_ROWS ? P1_MAX_ROWS : r);
 }
 
 inline int tiles_x(int W) { return (W - 6 + TC - 1) / TC; }
@@ -238,8 +208,8 @@ inline int tiles_y(int H) { return (H - 6 + TR - 1) / TR; }
 }  // namespace
 
 extern "C" long ir2rgb_video_metrics_workspace_bytes(int N, int H, int W) {
-    if (!sizes_ok(N, H, W)) return IR2RGB_EINVAL;
-    return (long)sizeof(double) * N * (3L * reduce_rows((long)H * W) + (long)tiles_x(W) * tiles_y(H));
+    if (!frame_sizes_ok(N, H, W, MIN_SIDE)) return IR2RGB_EINVAL;
+    return (long)sizeof(double) * N * (3L * partial_rows((long)H * W, P1_PIXELS, P1_MAX_ROWS) + (long)tiles_x(W) * tiles_y(H));
 }
 
 extern "C" int ir2rgb_video_metrics_tile(int which) {
@@ -248,17 +218,16 @@ extern "C" int ir2rgb_video_metrics_tile(int which) {
 
 extern "C" int ir2rgb_video_metrics_u8(const uint8_t *orig, const uint8_t *pred, const double *range, double *out,
                                        void *workspace, long workspace_bytes, int N, int H, int W, void *stream) {
-    if (!orig || !pred || !out || !workspace || !sizes_ok(N, H, W)) return IR2RGB_EINVAL;
+    if (!orig || !pred || !out || !workspace || !frame_sizes_ok(N, H, W, MIN_SIDE)) return IR2RGB_EINVAL;
     if (workspace_bytes < ir2rgb_video_metrics_workspace_bytes(N, H, W)) return IR2RGB_EINVAL;
-    if (!aligned(out, 8) || !aligned(range, 8) || !aligned(workspace, 8)) return IR2RGB_EALIGN;
+    if (misaligned(out, 8) || misaligned(range, 8) || misaligned(workspace, 8)) return IR2RGB_EALIGN;
     const long hw = (long)H * W;
-    const int rows = reduce_rows(hw), tx = tiles_x(W), tiles = tx * tiles_y(H);
+    const int rows = partial_rows(hw, P1_PIXELS, P1_MAX_ROWS), tx = tiles_x(W), tiles = tx * tiles_y(H);
     double *part1 = static_cast<double *>(workspace), *part2 = part1 + (long)N * rows * 3;
     hipStream_t s = as_stream(stream);
-    if (hw % 4 == 0 && aligned(orig, 4) && aligned(pred, 4))
-        metrics_reduce_kernel<4><<<dim3(rows, N), BLOCK, 0, s>>>(orig, pred, part1, hw);
-    else
-        metrics_reduce_kernel<1><<<dim3(rows, N), BLOCK, 0, s>>>(orig, pred, part1, hw);
+    with_bool(hw % 4 == 0 && !misaligned(orig, 4) && !misaligned(pred, 4), [&](auto wide) {
+        metrics_reduce_kernel<wide.value ? 4 : 1><<<dim3(rows, N), BLOCK, 0, s>>>(orig, pred, part1, hw);
+    });
     metrics_ssim_kernel<<<dim3(tiles, N), BLOCK, 0, s>>>(orig, pred, range, part1, part2, H, W, rows, tx);
     metrics_finish_kernel<<<N, BLOCK, 0, s>>>(range, part1, part2, out, rows, tiles, (long)(H - 6) * (W - 6));
     return ir2rgb_launch_status();

@@ -29,7 +29,8 @@
 #include <math.h>
 
 #include "common.h"
-#include "u8.h"
+#include "reduce.h"     // partial_rows
+#include "u8.h"         // to_u8, unit_to_u8, the bytes of a pixel group
 
 namespace {
 
@@ -134,10 +135,7 @@ __device__ __forceinline__ void run_panel(const float *__restrict__ src, uint8_t
             for (int p = 0; p < 4; ++p) {
                 const unsigned rgb = pixel_rgb<KIND, C>(x[p], mn, range);
 #pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const int byte = p * 3 + c;
-                    w[byte >> 2] |= ((rgb >> (8 * c)) & 0xffu) << (8 * (byte & 3));
-                }
+                for (int c = 0; c < 3; ++c) or_byte(w, p * 3 + c, get_byte(rgb, c));
             }
             unsigned *out = reinterpret_cast<unsigned *>(dst + e * 3);
 #pragma unroll
@@ -177,13 +175,8 @@ visuals_panel_kernel(PanelTable tab, const float *__restrict__ ws, int rows, uin
     }
 }
 
-inline bool aligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 // (min, max) rows per flow panel: one per workgroup of visuals_minmax_kernel, a workgroup per 1024 pixels, at most 256
-inline int minmax_rows(long hw) {
-    const long r = (hw + 1023) / 1024;
-    return (int)(r > 256 ? 256 : r);
-}
+inline int minmax_rows(long hw) { return partial_rows(hw, 1024, 256); }
 
 }  // namespace
 
@@ -198,7 +191,7 @@ extern "C" int ir2rgb_visuals_u8(const ir2rgb_panel *panels, int n, int H, int W
         return IR2RGB_EINVAL;
     PanelTable tab{};
     int n_flow = 0;
-    bool vec = W % 4 == 0 && aligned(out, 4);
+    bool vec = W % 4 == 0 && !misaligned(out, 4);
     for (int p = 0; p < n; ++p) {
         const ir2rgb_panel &q = panels[p];
         const bool image = q.kind == IR2RGB_PANEL_IMAGE_NORM || q.kind == IR2RGB_PANEL_IMAGE_UNIT;
@@ -206,23 +199,21 @@ extern "C" int ir2rgb_visuals_u8(const ir2rgb_panel *panels, int n, int H, int W
             return IR2RGB_EINVAL;
         tab.src[p] = q.src, tab.kind[p] = q.kind, tab.channels[p] = q.channels;
         if (q.kind == IR2RGB_PANEL_FLOW) tab.flow_slot[p] = n_flow, tab.flow_panel[n_flow++] = p;
-        vec = vec && aligned(q.src, 16);
+        vec = vec && !misaligned(q.src, 16);
     }
     if (n_flow && !workspace) return IR2RGB_EINVAL;
     for (int p = 0; p < n; ++p)
-        if (!aligned(panels[p].src, 4)) return IR2RGB_EALIGN;
-    if (!aligned(workspace, 4)) return IR2RGB_EALIGN;
+        if (misaligned(panels[p].src, 4)) return IR2RGB_EALIGN;
+    if (misaligned(workspace, 4)) return IR2RGB_EALIGN;
     const long hw = (long)H * W;
     const int rows = minmax_rows(hw);
     hipStream_t s = as_stream(stream);
-    if (n_flow) {
-        if (vec) visuals_minmax_kernel<true><<<n_flow * rows, 256, 0, s>>>(tab, workspace, rows, hw);
-        else visuals_minmax_kernel<false><<<n_flow * rows, 256, 0, s>>>(tab, workspace, rows, hw);
-    }
     // workgroups per panel: one per 256 work items, the whole grid within what stream_grid hands a streaming kernel
     int bpp = stream_grid(vec ? hw >> 2 : hw, 256);
     if (bpp > 2048 / n) bpp = 2048 / n;
-    if (vec) visuals_panel_kernel<true><<<n * bpp, 256, 0, s>>>(tab, workspace, rows, out, hw, bpp);
-    else visuals_panel_kernel<false><<<n * bpp, 256, 0, s>>>(tab, workspace, rows, out, hw, bpp);
+    with_bool(vec, [&](auto V) {
+        if (n_flow) visuals_minmax_kernel<V.value><<<n_flow * rows, 256, 0, s>>>(tab, workspace, rows, hw);
+        visuals_panel_kernel<V.value><<<n * bpp, 256, 0, s>>>(tab, workspace, rows, out, hw, bpp);
+    });
     return ir2rgb_launch_status();
 }

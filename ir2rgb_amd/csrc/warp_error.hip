@@ -36,6 +36,8 @@
 // and weight as 16-byte loads, the 12 bytes of cur as three dwords (a group never crosses a row); otherwise the same code
 // runs on 4 groups of one pixel.
 #include "common.h"
+#include "reduce.h"     // block_reduce, partial_rows, frame_sizes_ok
+#include "u8.h"         // get_byte, unpack4
 
 #pragma clang fp contract(off)
 
@@ -45,20 +47,7 @@ constexpr int BLOCK = 256;
 constexpr int PPT = 4;                          // pixels per thread and trip
 constexpr int ROW_PIXELS = BLOCK * PPT;         // pixels per partial row: one trip each until MAX_ROWS workgroups per pair
 constexpr int MAX_ROWS = BLOCK;                 // one partial row per thread of the finish pass
-
-// fixed-order binary tree over the workgroup; every thread returns the total
-__device__ __forceinline__ double block_sum(double v, double *sh) {
-    const int t = threadIdx.x;
-    sh[t] = v;
-    __syncthreads();
-    for (int s = BLOCK / 2; s > 0; s >>= 1) {
-        if (t < s) sh[t] = sh[t] + sh[t + s];
-        __syncthreads();
-    }
-    const double r = sh[0];
-    __syncthreads();
-    return r;
-}
+constexpr int MIN_SIDE = 2;                     // the lattice divides by W - 1 and H - 1
 
 struct Coord {
     double a;       // weight of the second neighbour (NaN when the coordinate is)
@@ -105,12 +94,8 @@ warp_reduce_kernel(const uint8_t *__restrict__ prev, const uint8_t *__restrict__
             const int gc = valid[u] ? g : groups - 1;
             if (PPG == 4) {
                 const float4 a = reinterpret_cast<const float4 *>(fx)[gc], b = reinterpret_cast<const float4 *>(fy)[gc];
-                vx[0] = a.x, vx[1] = a.y, vx[2] = a.z, vx[3] = a.w;
-                vy[0] = b.x, vy[1] = b.y, vy[2] = b.z, vy[3] = b.w;
-                if (HAS_W) {
-                    const float4 m = reinterpret_cast<const float4 *>(fw)[gc];
-                    vw[0] = m.x, vw[1] = m.y, vw[2] = m.z, vw[3] = m.w;
-                }
+                unpack4(a, vx), unpack4(b, vy);
+                if (HAS_W) unpack4(reinterpret_cast<const float4 *>(fw)[gc], vw);
 #pragma unroll
                 for (int k = 0; k < 3; ++k) cb[u][k] = reinterpret_cast<const unsigned *>(fc)[gc * 3 + k];
             } else {
@@ -146,8 +131,7 @@ warp_reduce_kernel(const uint8_t *__restrict__ prev, const uint8_t *__restrict__
             const double m = HAS_W ? (double)vw[q] : 1.0;
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
-                const int byte = p * 3 + c;
-                const unsigned cc = PPG == 4 ? (cb[u][byte >> 2] >> (8 * (byte & 3))) & 0xffu : cb[u][c];
+                const unsigned cc = PPG == 4 ? get_byte(cb[u], p * 3 + c) : cb[u][c];
                 const double wv = w00 * (double)pb[q][0][c] + w01 * (double)pb[q][1][c] + w10 * (double)pb[q][2][c] +
                                   w11 * (double)pb[q][3][c];
                 const double d = (double)cc - wv;
@@ -157,9 +141,9 @@ warp_reduce_kernel(const uint8_t *__restrict__ prev, const uint8_t *__restrict__
             sc += valid[u] ? m : 0.0;
         }
     }
-    s1 = block_sum(s1, red);
-    s2 = block_sum(s2, red);
-    sc = block_sum(sc, red);
+    s1 = block_reduce<REDUCE_SUM, BLOCK>(s1, red);
+    s2 = block_reduce<REDUCE_SUM, BLOCK>(s2, red);
+    sc = block_reduce<REDUCE_SUM, BLOCK>(sc, red);
     if (tid == 0) {
         double *row = part + ((long)n * rows + blockIdx.x) * 3;
         row[0] = s1, row[1] = s2, row[2] = sc;
@@ -172,9 +156,9 @@ warp_finish_kernel(const double *__restrict__ part, double *__restrict__ out, in
     const int n = blockIdx.x, tid = threadIdx.x;
     const double *row = part + ((long)n * rows + min(tid, rows - 1)) * 3;
     const double p1 = row[0], p2 = row[1], pc = row[2];
-    const double s1 = block_sum(tid < rows ? p1 : 0.0, red);
-    const double s2 = block_sum(tid < rows ? p2 : 0.0, red);
-    const double sc = block_sum(tid < rows ? pc : 0.0, red);
+    const double s1 = block_reduce<REDUCE_SUM, BLOCK>(tid < rows ? p1 : 0.0, red);
+    const double s2 = block_reduce<REDUCE_SUM, BLOCK>(tid < rows ? p2 : 0.0, red);
+    const double sc = block_reduce<REDUCE_SUM, BLOCK>(tid < rows ? pc : 0.0, red);
     if (tid == 0) {
         out[(long)n * 3 + 0] = s1 / (127.5 * 3.0 * (double)H * (double)W);
         out[(long)n * 3 + 1] = s2 / (255.0 * 255.0 * 3.0 * sc);
@@ -182,42 +166,25 @@ warp_finish_kernel(const double *__restrict__ part, double *__restrict__ out, in
     }
 }
 
-inline bool aligned(const void *p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
-// N rides in gridDim.y; offsets inside a pair stay below 2^31
-inline bool sizes_ok(int N, int H, int W) {
-    return N >= 1 && N <= 65535 && H >= 2 && W >= 2 && (long)H * W * 3 <= 0x7fffffffL;
-}
-
-inline int reduce_rows(long hw) {
-    const long r = (hw + ROW_PIXELS - 1) / ROW_PIXELS;
-    return (int)(r > MAX_ROWS ? MAX_ROWS : r);
-}
-
 }  // namespace
 
 extern "C" long ir2rgb_warp_error_workspace_bytes(int N, int H, int W) {
-    if (!sizes_ok(N, H, W)) return IR2RGB_EINVAL;
-    return (long)sizeof(double) * N * 3L * reduce_rows((long)H * W);
+    if (!frame_sizes_ok(N, H, W, MIN_SIDE)) return IR2RGB_EINVAL;
+    return (long)sizeof(double) * N * 3L * partial_rows((long)H * W, ROW_PIXELS, MAX_ROWS);
 }
 
 extern "C" int ir2rgb_warp_error_u8(const uint8_t *prev, const uint8_t *cur, const float *flow, const float *weight,
                                     double *out, void *workspace, long workspace_bytes, int N, int H, int W, void *stream) {
-    if (!prev || !cur || !flow || !out || !workspace || !sizes_ok(N, H, W)) return IR2RGB_EINVAL;
+    if (!prev || !cur || !flow || !out || !workspace || !frame_sizes_ok(N, H, W, MIN_SIDE)) return IR2RGB_EINVAL;
     if (workspace_bytes < ir2rgb_warp_error_workspace_bytes(N, H, W)) return IR2RGB_EINVAL;
-    if (!aligned(out, 8) || !aligned(workspace, 8) || !aligned(flow, 4) || !aligned(weight, 4)) return IR2RGB_EALIGN;
-    const int rows = reduce_rows((long)H * W);
+    if (misaligned(out, 8) || misaligned(workspace, 8) || misaligned(flow, 4) || misaligned(weight, 4)) return IR2RGB_EALIGN;
+    const int rows = partial_rows((long)H * W, ROW_PIXELS, MAX_ROWS);
     double *part = static_cast<double *>(workspace);
     hipStream_t s = as_stream(stream);
-    const bool wide = W % 4 == 0 && aligned(flow, 16) && aligned(weight, 16) && aligned(cur, 4);
-    auto reduce = [&](auto ppg, auto has_w) {
-        warp_reduce_kernel<ppg.value, has_w.value><<<dim3(rows, N), BLOCK, 0, s>>>(prev, cur, flow, weight, part, H, W);
-    };
-    using std::integral_constant;
-    if (wide && weight) reduce(integral_constant<int, 4>{}, integral_constant<bool, true>{});
-    else if (wide) reduce(integral_constant<int, 4>{}, integral_constant<bool, false>{});
-    else if (weight) reduce(integral_constant<int, 1>{}, integral_constant<bool, true>{});
-    else reduce(integral_constant<int, 1>{}, integral_constant<bool, false>{});
+    const bool wide = W % 4 == 0 && !misaligned(flow, 16) && !misaligned(weight, 16) && !misaligned(cur, 4);
+    with_bool(wide, weight != nullptr, [&](auto wd, auto has_w) {
+        warp_reduce_kernel<wd.value ? 4 : 1, has_w.value><<<dim3(rows, N), BLOCK, 0, s>>>(prev, cur, flow, weight, part, H, W);
+    });
     warp_finish_kernel<<<N, BLOCK, 0, s>>>(part, out, rows, H, W);
     return ir2rgb_launch_status();
 }

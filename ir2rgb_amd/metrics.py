@@ -166,21 +166,28 @@ def warp_bound(H, W, flow, weight=None):
 # ---------------------------------------------------------------------------------------------
 # plain torch
 # ---------------------------------------------------------------------------------------------
-def _batched(orig_u8, pred_u8, what):
-    for t in (orig_u8, pred_u8):
+def _frames(a, b, what, dtype_text, needs, min_side):
+    """The opening check of two uint8 frame batches -> both as [N,H,W,3] and whether they came as one frame [H,W,3];
+    anything else raises.  ``dtype_text`` and ``needs`` are the caller's words for the dtype and the smallest side."""
+    for t in (a, b):
         if not isinstance(t, torch.Tensor):
             raise TypeError(f"{what}: expected a tensor, got {type(t)}")
         if t.dtype != torch.uint8:
-            raise TypeError(f"{what}: expected dtype {torch.uint8}, got {t.dtype}")
-    if orig_u8.shape != pred_u8.shape:
-        raise ValueError(f"{what}: {tuple(orig_u8.shape)} against {tuple(pred_u8.shape)}")
-    if orig_u8.dim() == 3:
-        orig_u8, pred_u8 = orig_u8.unsqueeze(0), pred_u8.unsqueeze(0)
-    if orig_u8.dim() != 4 or orig_u8.shape[-1] != 3 or orig_u8.shape[0] < 1:
-        raise ValueError(f"{what}: uint8 [H,W,3] or [N,H,W,3] expected, got {tuple(pred_u8.shape)}")
-    if orig_u8.shape[1] < 7 or orig_u8.shape[2] < 7:
-        raise ValueError(f"{what}: the 7x7 window needs H, W >= 7, got {tuple(orig_u8.shape[1:3])}")
-    return orig_u8, pred_u8
+            raise TypeError(f"{what}: {dtype_text.format(torch.uint8)}, got {t.dtype}")
+    if a.shape != b.shape:
+        raise ValueError(f"{what}: {tuple(a.shape)} against {tuple(b.shape)}")
+    single = a.dim() == 3
+    if single:
+        a, b = a.unsqueeze(0), b.unsqueeze(0)
+    if a.dim() != 4 or a.shape[-1] != 3 or a.shape[0] < 1:
+        raise ValueError(f"{what}: uint8 [H,W,3] or [N,H,W,3] expected, got {tuple(b.shape)}")
+    if a.shape[1] < min_side or a.shape[2] < min_side:
+        raise ValueError(f"{what}: {needs} needs H, W >= {min_side}, got {tuple(a.shape[1:3])}")
+    return a, b, single
+
+
+def _batched(orig_u8, pred_u8, what):
+    return _frames(orig_u8, pred_u8, what, "expected dtype {}", "the 7x7 window", 7)[:2]
 
 
 def _range(data_range, N, device):
@@ -238,11 +245,6 @@ def ssim_reference(orig_u8, pred_u8, data_range="reference"):
 
 def _pairs(prev_u8, cur_u8, flow, weight, what):
     """-> prev, cur uint8 [N,H,W,3], flow fp32 [N,2,H,W], weight fp32 [N,1,H,W] or None; anything else raises."""
-    for t in (prev_u8, cur_u8):
-        if not isinstance(t, torch.Tensor):
-            raise TypeError(f"{what}: expected a tensor, got {type(t)}")
-        if t.dtype != torch.uint8:
-            raise TypeError(f"{what}: frames of dtype {torch.uint8} expected, got {t.dtype}")
     for t, name in ((flow, "flow"), (weight, "weight")):
         if t is None and name == "weight":
             continue
@@ -250,18 +252,12 @@ def _pairs(prev_u8, cur_u8, flow, weight, what):
             raise TypeError(f"{what}: {name}: expected a tensor, got {type(t)}")
         if t.dtype != torch.float32:
             raise TypeError(f"{what}: {name} of dtype {torch.float32} expected, got {t.dtype}")
-    if prev_u8.shape != cur_u8.shape:
-        raise ValueError(f"{what}: {tuple(prev_u8.shape)} against {tuple(cur_u8.shape)}")
-    if prev_u8.dim() == 3:
+    prev_u8, cur_u8, single = _frames(prev_u8, cur_u8, what, "frames of dtype {} expected", "the lattice", 2)
+    if single:
         if flow.dim() != 3 or (weight is not None and weight.dim() != 3):
             raise ValueError(f"{what}: one pair takes flow [2,H,W] and weight [1,H,W]")
-        prev_u8, cur_u8, flow = prev_u8.unsqueeze(0), cur_u8.unsqueeze(0), flow.unsqueeze(0)
-        weight = weight.unsqueeze(0) if weight is not None else None
-    if prev_u8.dim() != 4 or prev_u8.shape[-1] != 3 or prev_u8.shape[0] < 1:
-        raise ValueError(f"{what}: uint8 [H,W,3] or [N,H,W,3] expected, got {tuple(cur_u8.shape)}")
+        flow, weight = flow.unsqueeze(0), weight.unsqueeze(0) if weight is not None else None
     N, H, W = prev_u8.shape[:3]
-    if H < 2 or W < 2:
-        raise ValueError(f"{what}: the lattice needs H, W >= 2, got {(H, W)}")
     if tuple(flow.shape) != (N, 2, H, W):
         raise ValueError(f"{what}: flow {tuple(flow.shape)} given, {(N, 2, H, W)} expected")
     if weight is not None and tuple(weight.shape) != (N, 1, H, W):
@@ -309,16 +305,15 @@ def warp_error_reference(prev_u8, cur_u8, flow, weight=None):
 _WORKSPACES = {}
 
 
-def _workspace(device, stream, N, H, W):
-    """One fp64 buffer per (device, stream, N, H, W): the library writes all of it before reading, so it is neither
-    zeroed nor shared between streams whose launches could overlap."""
-    key = (device.index, stream, N, H, W)
+def _workspace(entry, limits, device, stream, N, H, W):
+    """One fp64 buffer per (entry, device, stream, N, H, W), sized by ``ir2rgb_<entry>_workspace_bytes``: the library
+    writes all of it before reading, so it is neither zeroed nor shared between streams whose launches could overlap."""
+    key = (entry, device.index, stream, N, H, W)
     ws = _WORKSPACES.get(key)
     if ws is None:
-        nbytes = _lib.lib().ir2rgb_video_metrics_workspace_bytes(N, H, W)
+        nbytes = getattr(_lib.lib(), f"ir2rgb_{entry}_workspace_bytes")(N, H, W)
         if nbytes < 0:
-            raise ValueError(f"video_metrics: N={N}, H={H}, W={W} is outside what the kernels take "
-                             "(N <= 65535, H, W >= 7, 3*H*W < 2**31)")
+            raise ValueError(f"{entry}: N={N}, H={H}, W={W} is outside what the kernels take ({limits})")
         ws = _WORKSPACES[key] = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=device)
     return ws
 
@@ -347,25 +342,9 @@ def video_metrics(orig_u8, pred_u8, data_range="reference"):
     N, H, W = orig_u8.shape[:3]
     given = _range(data_range, N, dev)
     out = torch.empty((N, 3), dtype=torch.float64, device=dev)
-    ws = _workspace(dev, _lib.current_stream(out), N, H, W)
+    ws = _workspace("video_metrics", "N <= 65535, H, W >= 7, 3*H*W < 2**31", dev, _lib.current_stream(out), N, H, W)
     _lib.launch("ir2rgb_video_metrics_u8", out, orig_u8, pred_u8, given, out, ws, ws.numel() * 8, N, H, W)
     return out
-
-
-_WARP_WORKSPACES = {}
-
-
-def _warp_workspace(device, stream, N, H, W):
-    """As ``_workspace``: one fp64 buffer per (device, stream, N, H, W), written by the library before it is read."""
-    key = (device.index, stream, N, H, W)
-    ws = _WARP_WORKSPACES.get(key)
-    if ws is None:
-        nbytes = _lib.lib().ir2rgb_warp_error_workspace_bytes(N, H, W)
-        if nbytes < 0:
-            raise ValueError(f"warp_error: N={N}, H={H}, W={W} is outside what the kernels take "
-                             "(N <= 65535, H, W >= 2, 3*H*W < 2**31)")
-        ws = _WARP_WORKSPACES[key] = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=device)
-    return ws
 
 
 def warp_error(prev_u8, cur_u8, flow, weight=None):
@@ -382,7 +361,7 @@ def warp_error(prev_u8, cur_u8, flow, weight=None):
     prev_u8, cur_u8, flow, weight = _pairs(prev_u8, cur_u8, flow, weight, "warp_error")
     N, H, W = prev_u8.shape[:3]
     out = torch.empty((N, 3), dtype=torch.float64, device=dev)
-    ws = _warp_workspace(dev, _lib.current_stream(out), N, H, W)
+    ws = _workspace("warp_error", "N <= 65535, H, W >= 2, 3*H*W < 2**31", dev, _lib.current_stream(out), N, H, W)
     _lib.launch("ir2rgb_warp_error_u8", out, prev_u8, cur_u8, flow, weight, out, ws, ws.numel() * 8, N, H, W)
     return out
 

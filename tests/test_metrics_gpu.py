@@ -98,6 +98,56 @@ def test_repeatable_on_any_stream_with_a_reused_workspace(dev):
     assert torch.equal(other, first)
 
 
+@pytest.mark.parametrize("H,W", [(9, 13), (8, 16)])
+def test_both_scores_alternate_on_one_workspace_cache(dev, H, W):
+    """``video_metrics`` and ``warp_error`` share one workspace cache.  Called in turn at the same N, H, W on the same
+    stream, and once more on a second stream, each repeats its first result bit for bit and stays within the bounds of its
+    CPU reference.  On the first stream ``warp_error`` goes first: a cache keyed without the entry would then hand the
+    SSIM call the smaller warp-error buffer, which the library refuses.  The cache holds, per stream, two distinct buffers
+    of the sizes the two entries ask for.  9x13 has an odd byte count (the scalar form of both reduce kernels), 8x16 takes
+    the 4-pixel form."""
+    import test_warp_error_cpu as warp
+    from ir2rgb_amd import _lib, metrics
+    frames = [make_pair(k, H, W, 31 + i) for i, k in enumerate(("random", "smooth"))]
+    O, P = torch.stack([f[0] for f in frames]), torch.stack([f[1] for f in frames])
+    pairs = [warp.reference("random", "fractional", H, W), warp.reference("consistent", "binary", H, W)]
+    prev, cur, flow, weight = (torch.stack([p[j] for p in pairs]) for j in range(4))
+    ssim_want = metrics.ssim_reference(O, P)
+    ssim_in, warp_in = [O.to(dev), P.to(dev)], [t.to(dev) for t in (prev, cur, flow, weight)]
+
+    def check(ssim_got, warp_got, what):
+        for n in range(2):
+            assert_rows_close(ssim_got[n].cpu(), ssim_want[n], H, W, f"{what} ssim row {n}")
+            warp.assert_rows_close(warp_got[n].cpu(), pairs[n][4], pairs[n][5], f"{what} warp row {n}")
+
+    def cached(stream):
+        """The two buffers the cache holds for (stream, 2, H, W): each of the size its own entry asks for."""
+        lib, ws = _lib.lib(), {}
+        for entry in ("video_metrics", "warp_error"):
+            ws[entry] = metrics._WORKSPACES[(entry, dev.index, stream, 2, H, W)]
+            assert ws[entry].numel() * 8 == getattr(lib, f"ir2rgb_{entry}_workspace_bytes")(2, H, W)
+        assert ws["video_metrics"].numel() > ws["warp_error"].numel()
+        assert ws["video_metrics"].data_ptr() != ws["warp_error"].data_ptr()
+        return ws
+
+    # this stream: warp_error first, so that the SSIM call finds the smaller buffer already cached for (stream, N, H, W)
+    warp_first, ssim_first = metrics.warp_error(*warp_in), metrics.video_metrics(*ssim_in)
+    check(ssim_first, warp_first, "first")
+    assert torch.equal(metrics.warp_error(*warp_in), warp_first) and torch.equal(metrics.video_metrics(*ssim_in), ssim_first)
+    main = cached(_lib.current_stream(ssim_first))
+    side = torch.cuda.Stream(dev)
+    side.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(side):               # a second stream, the other order
+        again = [(metrics.video_metrics(*ssim_in), metrics.warp_error(*warp_in)) for _ in range(2)]
+        side_key = _lib.current_stream(ssim_first)
+    side.synchronize()
+    for s, w in again:
+        assert torch.equal(s, ssim_first) and torch.equal(w, warp_first)
+    check(*again[0], "side stream")
+    other = cached(side_key)
+    assert all(main[e].data_ptr() != other[e].data_ptr() for e in main)        # streams never share a buffer
+
+
 def test_frames_far_into_a_long_batch(dev):
     """Byte offsets of the last frames lie past 2^31: they score what the same frames score alone."""
     from ir2rgb_amd import metrics
