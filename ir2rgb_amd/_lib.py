@@ -207,14 +207,15 @@ class _Entry:
     """Namespace of the library's entry points (fastcall wrapper where one exists, else the ctypes function)."""
 
 
-_ERRNAMES = {-1: "IR2RGB_EINVAL (bad size/parameter)", -2: "IR2RGB_ENOSUP (not supported)",
+IR2RGB_ENOSUP = -2   # include/ir2rgb_hip.h: the one status a caller may treat as an answer (flownet2_hip.corr_nhwc)
+_ERRNAMES = {-1: "IR2RGB_EINVAL (bad size/parameter)", IR2RGB_ENOSUP: "IR2RGB_ENOSUP (not supported)",
              -3: "IR2RGB_EALIGN (misaligned buffer)"}
 
 
 def check(rc, what):
     if rc != 0:
         if rc < 0:
-            if rc == -2:
+            if rc == IR2RGB_ENOSUP:
                 raise NotImplementedError(f"{what}: {_ERRNAMES[rc]}")
             raise ValueError(f"{what}: {_ERRNAMES.get(rc, rc)}")
         raise Ir2rgbError(f"{what}: HIP call failed (hipError_t {rc})")

@@ -27,22 +27,23 @@
 
 #include "common.h"
 
-static void out_shape(int H, int W, int pad, int ksize, int md, int s1, int s2, int *oc, int *oh, int *ow) {
+// The one validation of the operator's sizes and parameters, and its output geometry (oh / ow may come out <= 0: the
+// launchers reject that, the shape query reports it).
+static int corr_shape(int N, int C, int H, int W, int pad, int ksize, int md, int s1, int s2, int *oc, int *oh, int *ow) {
+    if (N < 0 || C < 0 || H < 0 || W < 0) return IR2RGB_EINVAL;
+    if (s1 < 1 || s2 < 1 || ksize < 1 || !(ksize & 1) || pad < 0 || md < 0) return IR2RGB_EINVAL;
     int krad = (ksize - 1) / 2, border = krad + md;
     int pH = H + 2 * pad, pW = W + 2 * pad, drad = md / s2;
     *oc = (2 * drad + 1) * (2 * drad + 1);
     *oh = (int)ceilf((float)(pH - 2 * border) / (float)s1);
     *ow = (int)ceilf((float)(pW - 2 * border) / (float)s1);
+    return IR2RGB_OK;
 }
 
 extern "C" int ir2rgb_correlation_out_shape(int C, int H, int W, int pad_size, int kernel_size,
                                             int max_displacement, int stride1, int stride2, int *outC, int *outH,
                                             int *outW) {
-    (void)C;
-    if (stride1 < 1 || stride2 < 1 || kernel_size < 1 || !(kernel_size & 1) || pad_size < 0 || max_displacement < 0)
-        return IR2RGB_EINVAL;
-    out_shape(H, W, pad_size, kernel_size, max_displacement, stride1, stride2, outC, outH, outW);
-    return IR2RGB_OK;
+    return corr_shape(0, C, H, W, pad_size, kernel_size, max_displacement, stride1, stride2, outC, outH, outW);
 }
 
 // ----------------------------------------------------------------------------------------
@@ -55,43 +56,99 @@ extern "C" int ir2rgb_correlation_out_shape(int C, int H, int W, int pad_size, i
 //   one-wave-per-unit layout, which is what hides the L2/HBM latency of the operand loads.
 //   Reduction: two wave64 xor-shuffles combine the lane quarters, the channel halves meet in LDS.
 // ----------------------------------------------------------------------------------------
+typedef __attribute__((ext_vector_type(2))) float corr_f2;
+
+// What both fast kernels share: the constants of a unit, what a lane of it owns, and the epilogue.
+template <int DR, int S2, int T0>
+struct CorrUnit {
+    static constexpr int D = 2 * DR + 1;
+    static constexpr int TMAX = T0 > D - T0 ? T0 : D - T0;  // displacements per wave (first half is the larger)
+    static constexpr int HALO = S2 * DR;
+    static constexpr int NB = 8 + S2 * (TMAX - 1);           // f2 floats needed per lane per channel
+    static constexpr int NB4 = (NB + 3) / 4;
+    static_assert(HALO % 4 == 0 && (S2 * T0) % 4 == 0, "f2 windows must keep float4 alignment");
+    typedef float Red[TMAX * 8][64];                         // per ti half [acc index][lane]: partial sums of channel half 1
+
+    int lane, wave, th, ch;                                  // th / ch: displacement half, channel half of this wave
+    int xc, tj, y, n, t0, nt, xo, cs, x0, y2;
+    bool row_ok, lane_ok;
+    long hw;
+
+    __device__ CorrUnit(long unit, int xchunks, int H, int W) {
+        lane = threadIdx.x & 63;
+        wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+        th = wave & 1, ch = wave >> 1;
+        xc = (int)(unit % xchunks); unit /= xchunks;
+        tj = (int)(unit % D) - DR;  unit /= D;
+        y = (int)(unit % H);
+        n = (int)(unit / H);
+        t0 = th ? T0 : 0, nt = th ? D - T0 : T0;             // this wave's ti range [t0, t0+nt)
+        xo = lane & 15, cs = lane >> 4;
+        x0 = xc * 128 + xo * 8;
+        y2 = y + tj * S2;
+        row_ok = (y2 >= 0) && (y2 < H);                      // workgroup-uniform
+        lane_ok = x0 < W;
+        hw = (long)H * W;
+    }
+
+    // acc[t][k] = pixel pair k of displacement t0 + t.  Two wave64 xor-shuffles give every lane the wave's sum; the
+    // channel halves meet in LDS (red[2]: waves with ch == 1 publish, waves with ch == 0 add and store).
+    __device__ void finish(corr_f2 (&acc)[TMAX][4], Red *red, float *__restrict__ out, int H, int W, float inv_nelems) const {
+#pragma unroll
+        for (int t = 0; t < TMAX; ++t)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                corr_f2 v = acc[t][k];
+                v.x += __shfl_xor(v.x, 16, 64); v.y += __shfl_xor(v.y, 16, 64);
+                v.x += __shfl_xor(v.x, 32, 64); v.y += __shfl_xor(v.y, 32, 64);
+                acc[t][k] = v;
+            }
+        if (ch == 1) {
+#pragma unroll
+            for (int t = 0; t < TMAX; ++t)
+#pragma unroll
+                for (int k = 0; k < 4; ++k) { red[th][t * 8 + 2 * k][lane] = acc[t][k].x; red[th][t * 8 + 2 * k + 1][lane] = acc[t][k].y; }
+        }
+        __syncthreads();
+        if (ch == 0 && lane_ok) {
+            float *o = out + (((long)n * (D * D) + (long)(tj + DR) * D + t0) * H + y) * (long)W + x0;
+#pragma unroll
+            for (int t = 0; t < TMAX; ++t) {
+                if (t < nt && (t & 3) == cs) {   // lane quarter cs stores rows t = cs, cs+4, ...
+                    float r[8];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        r[2 * k] = (acc[t][k].x + red[th][t * 8 + 2 * k][lane]) * inv_nelems;
+                        r[2 * k + 1] = (acc[t][k].y + red[th][t * 8 + 2 * k + 1][lane]) * inv_nelems;
+                    }
+                    float4 *q = reinterpret_cast<float4 *>(o + (long)t * hw);
+                    q[0] = make_float4(r[0], r[1], r[2], r[3]);
+                    q[1] = make_float4(r[4], r[5], r[6], r[7]);
+                }
+            }
+        }
+    }
+};
+
 template <int DR, int S2, int T0>
 __global__ void __launch_bounds__(256)
 corr_fwd_tile(const float *__restrict__ f1, const float *__restrict__ f2, float *__restrict__ out, int C, int H,
               int W, int xchunks, float inv_nelems) {
-    constexpr int D = 2 * DR + 1;
-    constexpr int TMAX = T0 > D - T0 ? T0 : D - T0;  // displacements per wave (first half is the larger)
-    constexpr int HALO = S2 * DR;
-    constexpr int NB = 8 + S2 * (TMAX - 1);           // f2 floats needed per lane per channel
-    constexpr int NB4 = (NB + 3) / 4;
-    static_assert(HALO % 4 == 0 && (S2 * T0) % 4 == 0, "f2 windows must keep float4 alignment");
-    __shared__ float red[2][TMAX * 8][64];            // [ti half][acc index][lane]: partial sums of channel half 1
+    typedef CorrUnit<DR, S2, T0> U;
+    constexpr int TMAX = U::TMAX, HALO = U::HALO, NB4 = U::NB4;
+    __shared__ typename U::Red red[2];
+    const U u(blockIdx.x, xchunks, H, W);
+    const int n = u.n, y = u.y, y2 = u.y2, cs = u.cs, ch = u.ch, x0 = u.x0, nt = u.nt;
+    const long hw = u.hw;
+    const int xb = x0 - HALO + S2 * u.t0;            // first f2 column of this wave's window (multiple of 4)
 
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int th = wave & 1, ch = wave >> 1;          // displacement half, channel half
-    long unit = blockIdx.x;
-    const int xc = (int)(unit % xchunks); unit /= xchunks;
-    const int tj = (int)(unit % D) - DR;  unit /= D;
-    const int y = (int)(unit % H);
-    const int n = (int)(unit / H);
-
-    const int t0 = th ? T0 : 0, nt = th ? D - T0 : T0;   // this wave's ti range [t0, t0+nt)
-    const int xo = lane & 15, cs = lane >> 4;
-    const int x0 = xc * 128 + xo * 8;
-    const int y2 = y + tj * S2;
-    const bool row_ok = (y2 >= 0) && (y2 < H);       // workgroup-uniform
-    const bool lane_ok = x0 < W;
-    const long hw = (long)H * W;
-    const int xb = x0 - HALO + S2 * t0;              // first f2 column of this wave's window (multiple of 4)
-
-    float acc[TMAX][8];
+    corr_f2 acc[TMAX][4];
 #pragma unroll
     for (int t = 0; t < TMAX; ++t)
 #pragma unroll
-        for (int m = 0; m < 8; ++m) acc[t][m] = 0.f;
+        for (int k = 0; k < 4; ++k) acc[t][k] = (corr_f2){0.f, 0.f};
 
-    if (row_ok && lane_ok) {
+    if (u.row_ok && u.lane_ok) {
         const float *p1 = f1 + ((long)n * C) * hw + (long)y * W + x0;
         const float *p2 = f2 + ((long)n * C) * hw + (long)y2 * W + xb;
         bool inb[NB4];
@@ -117,42 +174,10 @@ corr_fwd_tile(const float *__restrict__ f1, const float *__restrict__ f2, float 
             for (int t = 0; t < TMAX; ++t)
 #pragma unroll
                 for (int m = 0; m < 8; ++m)
-                    if (t < nt) acc[t][m] = fmaf(a[m], b[m + S2 * t], acc[t][m]);
+                    if (t < nt) acc[t][m >> 1][m & 1] = fmaf(a[m], b[m + S2 * t], acc[t][m >> 1][m & 1]);
         }
     }
-
-    // lane quarters -> every lane holds the wave's sum
-#pragma unroll
-    for (int t = 0; t < TMAX; ++t)
-#pragma unroll
-        for (int m = 0; m < 8; ++m) {
-            float v = acc[t][m];
-            v += __shfl_xor(v, 16, 64);
-            v += __shfl_xor(v, 32, 64);
-            acc[t][m] = v;
-        }
-    // channel halves meet in LDS: waves with ch == 1 publish, waves with ch == 0 add and store
-    if (ch == 1) {
-#pragma unroll
-        for (int t = 0; t < TMAX; ++t)
-#pragma unroll
-            for (int m = 0; m < 8; ++m) red[th][t * 8 + m][lane] = acc[t][m];
-    }
-    __syncthreads();
-    if (ch == 0 && lane_ok) {
-        float *o = out + (((long)n * (D * D) + (long)(tj + DR) * D + t0) * H + y) * (long)W + x0;
-#pragma unroll
-        for (int t = 0; t < TMAX; ++t) {
-            if (t < nt && (t & 3) == cs) {   // lane quarter cs stores rows t = cs, cs+4, ...
-                float r[8];
-#pragma unroll
-                for (int m = 0; m < 8; ++m) r[m] = (acc[t][m] + red[th][t * 8 + m][lane]) * inv_nelems;
-                float4 *q = reinterpret_cast<float4 *>(o + (long)t * hw);
-                q[0] = make_float4(r[0], r[1], r[2], r[3]);
-                q[1] = make_float4(r[4], r[5], r[6], r[7]);
-            }
-        }
-    }
+    u.finish(acc, red, out, H, W, inv_nelems);
 }
 
 // ----------------------------------------------------------------------------------------
@@ -173,53 +198,36 @@ corr_fwd_tile(const float *__restrict__ f1, const float *__restrict__ f2, float 
 //     touch 16 distinct 16-byte bank windows (even ones for one quarter, odd ones for the other);
 //   * the FMAs are packed: a pixel pair times a pixel pair of the shifted window (stride2 = 2 shifts by whole
 //     pairs), v_pk_fma_f32 -- 48 instructions per channel instead of 96.
-// One s_barrier + one counted vmcnt per 8-channel stage.  Reduction and stores as in corr_fwd_tile.
+// One s_barrier + one counted vmcnt per 8-channel stage.  Reduction and stores: CorrUnit::finish, the ring as scratch.
 // ----------------------------------------------------------------------------------------
-typedef __attribute__((ext_vector_type(2))) float corr_f2;
-
 template <int DR, int S2, int T0>
 __global__ void __launch_bounds__(256)
 corr_fwd_lds(const float *__restrict__ f1, const float *__restrict__ f2, float *__restrict__ out, int C, int H, int W,
              int xchunks, float inv_nelems, unsigned in_bytes) {
     static_assert(S2 == 2, "packed form: a displacement step shifts the window by one pixel pair");
-    constexpr int D = 2 * DR + 1;
-    constexpr int TMAX = T0 > D - T0 ? T0 : D - T0;
-    constexpr int HALO = S2 * DR;                       // 20
-    constexpr int NB = 8 + S2 * (TMAX - 1), NB4 = (NB + 3) / 4;   // 30 floats -> 8 chunks per lane and channel
+    typedef CorrUnit<DR, S2, T0> U;
+    constexpr int D = U::D, TMAX = U::TMAX, HALO = U::HALO /* 20 */, NB4 = U::NB4;   // NB = 30 floats -> 8 chunks per lane and channel
     constexpr int F1P = 40, F2P = 48;                   // row pitches in 16-byte slots (32 / 44 data chunks + shift + pad)
     constexpr int F2C = 44;                             // data chunks of an f2 row: x in [x_chunk - 20, x_chunk + 156)
     constexpr int F1S = 8 * F1P, SLOTS = F1S + 8 * F2P; // 320 + 384 slots per stage: f1 ends on an instruction boundary
     constexpr int NDMA = SLOTS / 64, NF1 = F1S / 64;    // 11 DMA instructions per stage, the first 5 read f1
     constexpr int PERW = (NDMA + 3) / 4;                // 3 per wave (wave 3: its third is a dummy)
     constexpr int STAGE = NDMA * 1024, NST = 4;         // four stages: three in flight while one is consumed
-    static_assert(HALO % 4 == 0 && (S2 * T0) % 4 == 0, "f2 windows must keep float4 alignment");
     static_assert(F1S % 64 == 0 && SLOTS % 64 == 0, "regions must end on DMA instruction boundaries");
     constexpr int RED = 2 * TMAX * 8 * 64 * 4;          // reduction scratch (re-uses the ring after the last stage)
     constexpr int RING = NST * STAGE > RED ? NST * STAGE : RED;
     __shared__ __attribute__((aligned(1024))) unsigned char smem[RING + 1024];
     unsigned char *const dummy = smem + RING;
 
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int th = wave & 1, ch = wave >> 1;
     // XCD-aware unit ids: workgroup b runs on XCD b % 8, and the eight L2s (4 MB each) do not share.  Units are
     // numbered (n, y, tj, x chunk) with y slowest; giving XCD k the k-th contiguous eighth of them makes the units that
     // read the same f1 row (all 21 tj of a y) and the same f2 row ((y, tj) and (y + 2, tj - 1)) neighbours in ONE L2:
     // with round-robin ids every XCD streamed all 16.8 MB of both tensors through its own 4 MB.
     long unit = blockIdx.x;
     if ((gridDim.x & 7) == 0) unit = (long)(blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
-    const int xc = (int)(unit % xchunks); unit /= xchunks;
-    const int tj = (int)(unit % D) - DR;  unit /= D;
-    const int y = (int)(unit % H);
-    const int n = (int)(unit / H);
-
-    const int t0 = th ? T0 : 0, nt = th ? D - T0 : T0;
-    const int xo = lane & 15, cs = lane >> 4;
-    const int x0 = xc * 128 + xo * 8;
-    const int y2 = y + tj * S2;
-    const bool row_ok = (y2 >= 0) && (y2 < H);       // workgroup-uniform
-    const bool lane_ok = x0 < W;
-    const long hw = (long)H * W;
+    const U u(unit, xchunks, H, W);
+    const int lane = u.lane, wave = u.wave, th = u.th, ch = u.ch, xc = u.xc, y = u.y, n = u.n, t0 = u.t0, xo = u.xo, cs = u.cs, y2 = u.y2;
+    const long hw = u.hw;
 
     corr_f2 acc[TMAX][4];
 #pragma unroll
@@ -227,7 +235,7 @@ corr_fwd_lds(const float *__restrict__ f1, const float *__restrict__ f2, float *
 #pragma unroll
         for (int k = 0; k < 4; ++k) acc[t][k] = (corr_f2){0.f, 0.f};
 
-    if (row_ok) {
+    if (u.row_ok) {
         const rsrc_t r1 = make_rsrc(f1, in_bytes), r2 = make_rsrc(f2, in_bytes);
         // ---- per-lane DMA source offsets (bytes) of this wave's instructions: slot -> (tensor, row, chunk) ----
         unsigned voff[PERW];
@@ -301,40 +309,7 @@ corr_fwd_lds(const float *__restrict__ f1, const float *__restrict__ f2, float *
         __builtin_amdgcn_s_barrier();                // the ring is free: it becomes the reduction scratch
     }
 
-    float (*red)[TMAX * 8][64] = reinterpret_cast<float (*)[TMAX * 8][64]>(smem);
-#pragma unroll
-    for (int t = 0; t < TMAX; ++t)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            corr_f2 v = acc[t][k];
-            v.x += __shfl_xor(v.x, 16, 64); v.y += __shfl_xor(v.y, 16, 64);
-            v.x += __shfl_xor(v.x, 32, 64); v.y += __shfl_xor(v.y, 32, 64);
-            acc[t][k] = v;
-        }
-    if (ch == 1) {
-#pragma unroll
-        for (int t = 0; t < TMAX; ++t)
-#pragma unroll
-            for (int k = 0; k < 4; ++k) { red[th][t * 8 + 2 * k][lane] = acc[t][k].x; red[th][t * 8 + 2 * k + 1][lane] = acc[t][k].y; }
-    }
-    __syncthreads();
-    if (ch == 0 && lane_ok) {
-        float *o = out + (((long)n * (D * D) + (long)(tj + DR) * D + t0) * H + y) * (long)W + x0;
-#pragma unroll
-        for (int t = 0; t < TMAX; ++t) {
-            if (t < nt && (t & 3) == cs) {
-                float r[8];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    r[2 * k] = (acc[t][k].x + red[th][t * 8 + 2 * k][lane]) * inv_nelems;
-                    r[2 * k + 1] = (acc[t][k].y + red[th][t * 8 + 2 * k + 1][lane]) * inv_nelems;
-                }
-                float4 *q = reinterpret_cast<float4 *>(o + (long)t * hw);
-                q[0] = make_float4(r[0], r[1], r[2], r[3]);
-                q[1] = make_float4(r[4], r[5], r[6], r[7]);
-            }
-        }
-    }
+    u.finish(acc, reinterpret_cast<typename U::Red *>(smem), out, H, W, inv_nelems);
 }
 
 // ----------------------------------------------------------------------------------------
@@ -431,19 +406,12 @@ corr_bwd_kernel(const float *__restrict__ f1, const float *__restrict__ f2, cons
     }
 }
 
-static int check_params(int N, int C, int H, int W, int pad, int ksize, int md, int s1, int s2) {
-    if (N < 0 || C < 0 || H < 0 || W < 0) return IR2RGB_EINVAL;
-    if (s1 < 1 || s2 < 1 || ksize < 1 || !(ksize & 1) || pad < 0 || md < 0) return IR2RGB_EINVAL;
-    return IR2RGB_OK;
-}
-
 extern "C" int ir2rgb_correlation_fwd(const float *in1, const float *in2, float *out, int N, int C, int H, int W,
                                       int pad_size, int kernel_size, int max_displacement, int stride1,
                                       int stride2, void *stream) {
-    int rc = check_params(N, C, H, W, pad_size, kernel_size, max_displacement, stride1, stride2);
-    if (rc) return rc;
     int oc, oh, ow;
-    out_shape(H, W, pad_size, kernel_size, max_displacement, stride1, stride2, &oc, &oh, &ow);
+    int rc = corr_shape(N, C, H, W, pad_size, kernel_size, max_displacement, stride1, stride2, &oc, &oh, &ow);
+    if (rc) return rc;
     if (oh <= 0 || ow <= 0) return IR2RGB_EINVAL;
     long total = (long)N * oc * oh * ow;
     if (total == 0) return IR2RGB_OK;
@@ -472,11 +440,10 @@ extern "C" int ir2rgb_correlation_fwd(const float *in1, const float *in2, float 
 extern "C" int ir2rgb_correlation_bwd(const float *in1, const float *in2, const float *gout, float *gin1,
                                       float *gin2, int N, int C, int H, int W, int pad_size, int kernel_size,
                                       int max_displacement, int stride1, int stride2, void *stream) {
-    int rc = check_params(N, C, H, W, pad_size, kernel_size, max_displacement, stride1, stride2);
+    int oc, oh, ow;
+    int rc = corr_shape(N, C, H, W, pad_size, kernel_size, max_displacement, stride1, stride2, &oc, &oh, &ow);
     if (rc) return rc;
     if (stride1 != 1) return IR2RGB_ENOSUP;
-    int oc, oh, ow;
-    out_shape(H, W, pad_size, kernel_size, max_displacement, stride1, stride2, &oc, &oh, &ow);
     if (oh <= 0 || ow <= 0) return IR2RGB_EINVAL;
     long total = (long)N * C * H * W;
     if (total == 0) return IR2RGB_OK;

@@ -37,9 +37,13 @@ class FlowNet(torch.nn.Module):
             return flow.view(b, n, 2, h, w), conf.view(b, n, 1, h, w)
         return self.compute_flow_and_conf(input_A, input_B, side)
 
+    @staticmethod
+    def _key(shape, im):
+        return tuple(shape), im.dtype, str(im.device)
+
     def will_replay(self, n, im):
         """True when a call on ``n`` frame pairs shaped like ``im`` [., 3, H, W] would be a graph replay (no lazy work)."""
-        return isinstance(self._graphs.get(((n,) + tuple(im.shape[1:]), im.dtype, str(im.device))), tuple)
+        return isinstance(self._graphs.get(self._key((n,) + tuple(im.shape[1:]), im)), tuple)
 
     def compute_flow_and_conf(self, im1, im2, side=None):
         """FlowNet2 is frozen, runs without autograd and with fixed shapes: ~330 small launches per call.
@@ -47,7 +51,7 @@ class FlowNet(torch.nn.Module):
         confidence mask) is captured into a HIP graph and replayed -- one launch, no host work between
         the kernels.  Any failure to capture falls back to the eager path for that shape (logged once)."""
         self.ran_on = None
-        key = (tuple(im1.shape), im1.dtype, str(im1.device))
+        key = self._key(im1.shape, im1)
         ent = self._graphs.get(key)
         if not self.use_graph or not im1.is_cuda or ent is False:
             return self._flow_and_conf_eager(im1, im2)

@@ -47,43 +47,31 @@ class View:
         return self.buf.shape[2], self.buf.shape[3]
 
 
-class Workspace:
-    """Per-(sub-network, input shape) pool of NHWC buffers, allocated and zero-filled once.  Buffers are
-    handed out in call order; pad channels are never written, so they stay zero across calls, and every
-    real channel is overwritten by its producer on each forward."""
-    _current = None
+class _Run:
+    """One call of a sub-network: its batch, dtype and device, and the pool of NHWC buffers of (net, input shape, dtype,
+    device), allocated and zero-filled on the first such call and handed out in call order after that.  Pad channels are
+    never written, so they stay zero across calls; every real channel is overwritten by its producer on each forward.
+    Pools live ON the sub-network module (not in a table keyed by id(net): ids are recycled once a network is garbage
+    collected)."""
 
-    def __init__(self):
-        self.bufs, self.cursor = [], 0
+    def __init__(self, net, x, dtype):
+        self.n, self.dtype, self.device, self.cursor = x.shape[0], dtype, x.device, 0
+        self.pool = net.__dict__.setdefault("_ir2rgb_workspaces", {}).setdefault((tuple(x.shape), dtype, x.device), [])
 
-    @classmethod
-    def activate(cls, net, key):
-        """The pool of (net, key), created on first use.  Pools live ON the sub-network module (not in a
-        table keyed by id(net): ids are recycled once a network is garbage collected)."""
-        pools = net.__dict__.setdefault("_ir2rgb_workspaces", {})
-        ws = pools.get(key)
-        if ws is None:
-            ws = pools[key] = Workspace()
-        ws.cursor = 0
-        cls._current = ws
-        return ws
-
-    def take(self, shape, dtype, device):
-        if self.cursor < len(self.bufs):
-            b = self.bufs[self.cursor]
-            if tuple(b.shape) != tuple(shape) or b.dtype != dtype or b.device != device:
-                raise RuntimeError("FlowNet2 workspace: allocation sequence changed")
-        else:
-            b = torch.zeros(shape, dtype=dtype, device=device).contiguous(memory_format=torch.channels_last)
-            self.bufs.append(b)
+    def buf(self, ld, h, w):
+        shape = (self.n, ld, h, w)
+        if self.cursor == len(self.pool):
+            self.pool.append(torch.zeros(shape, dtype=self.dtype, device=self.device).contiguous(memory_format=torch.channels_last))
+        b = self.pool[self.cursor]
+        if tuple(b.shape) != shape:
+            raise RuntimeError("FlowNet2 workspace: allocation sequence changed")
         self.cursor += 1
         return b
 
-
-def new_buf(n, ld, h, w, dtype, device):
-    if Workspace._current is not None:
-        return Workspace._current.take((n, ld, h, w), dtype, device)
-    return torch.zeros((n, ld, h, w), dtype=dtype, device=device).contiguous(memory_format=torch.channels_last)
+    def conv_out(self, mod, hw):
+        """A buffer of its own for the result of the nn.Conv2d ``mod`` on an input of size ``hw``, as a View."""
+        h, w = ((s + 2 * p - k) // st + 1 for s, k, st, p in zip(hw, mod.kernel_size, mod.stride, mod.padding))
+        return View(self.buf(_up64(mod.out_channels), h, w), 0, mod.out_channels)
 
 
 def _pad_cin(cin_to, transposed):
@@ -144,7 +132,7 @@ def corr_nhwc(mod, av, bv, yv, slope):
         rc = _lib.lib().ir2rgb_correlation_nhwc_half(av.buf, av.ld, av.off, bv.buf, bv.ld, bv.off, yv.buf, 1, yv.ld,
                                                      yv.off, float(slope), n, av.ch, h, w, C._TORCH2DT[av.buf.dtype],
                                                      _lib.current_stream(av.buf))
-    if rc == -2:        # IR2RGB_ENOSUP
+    if rc == _lib.IR2RGB_ENOSUP:
         return False
     _lib.check(rc, "correlation_nhwc_half")
     return True
@@ -169,18 +157,24 @@ class _Decoder:
     SKIP = {5: 512, 4: 512, 3: 256, 2: 128}
     DEC = {5: 512, 4: 256, 3: 128, 2: 64}
 
-    def __init__(self, n, h6, w6, dtype, device):
-        self.cat = {}
-        for lvl in (5, 4, 3, 2):
-            s = 2 ** (6 - lvl)
-            width = self.SKIP[lvl] + self.DEC[lvl] + 2
-            self.cat[lvl] = new_buf(n, _up64(width), h6 * s, w6 * s, dtype, device)
+    def __init__(self, ctx, h6, w6):
+        self.ctx = ctx
+        self.cat = {lvl: ctx.buf(_up64(self.SKIP[lvl] + self.DEC[lvl] + 2), h6 << (6 - lvl), w6 << (6 - lvl)) for lvl in (5, 4, 3, 2)}
 
     def skip_view(self, lvl):
         return View(self.cat[lvl], 0, self.SKIP[lvl])
 
     def full_view(self, lvl):
         return View(self.cat[lvl], 0, self.SKIP[lvl] + self.DEC[lvl] + 2)
+
+    def encode(self, net, x, levels):
+        """convK -> convK_1 for each level K of ``levels``; level K's result is the skip slice of its concatenation buffer
+        (level 6, which has none: a dense buffer)."""
+        for lvl in levels:
+            a, b = getattr(net, f"conv{lvl}")[0], getattr(net, f"conv{lvl}_1")[0]
+            x = conv(x, a, self.ctx.conv_out(a, x.hw), LEAKY01)
+            x = conv(x, b, self.skip_view(lvl) if lvl in self.cat else self.ctx.conv_out(b, x.hw), LEAKY01)
+        return x
 
     def run(self, net, feat6, inter=False):
         n = feat6.n
@@ -195,94 +189,70 @@ class _Decoder:
             feat = self.full_view(lvl - 1)
             if inter:
                 ic = getattr(net, f"inter_conv{lvl - 1}")[0]
-                ibuf = new_buf(n, _up64(ic.out_channels), nxt.shape[2], nxt.shape[3], nxt.dtype, nxt.device)
-                flow_in = conv(feat, ic, View(ibuf, 0, ic.out_channels), 0)
+                flow_in = conv(feat, ic, self.ctx.conv_out(ic, feat.hw), 0)
             else:
                 flow_in = feat
         h, w = feat.hw
         return predict(flow_in, net.predict_flow2, n, h, w)
 
 
-def _dense(n, ch, h, w, dtype, device):
-    return View(new_buf(n, _up64(ch), h, w, dtype, device), 0, ch)
+def _begin(net, x, dtype):
+    """-> (run context, decoder) of one FlowNetC / S / SD call on ``x`` [N, C, H, W], H and W multiples of 64."""
+    ctx = _Run(net, x, dtype)
+    return ctx, _Decoder(ctx, x.shape[2] // 64, x.shape[3] // 64)
 
 
 def flownetc(net, x, dtype):
     """x [N,6,H,W] fp32 (two normalised images) -> flow2 [N,2,H/4,W/4] fp32 (reference FlowNetC.py:75-126)."""
-    Workspace.activate(net, (tuple(x.shape), dtype, x.device))
-    n, _, H, W = x.shape
-    dev = x.device
-    dec = _Decoder(n, H // 64, W // 64, dtype, dev)
+    ctx, dec = _begin(net, x, dtype)
     feats = []
     for img, skip in ((x[:, 0:3], True), (x[:, 3:6], False)):
-        c1 = first_conv(img, net.conv1[0], _dense(n, 64, H // 2, W // 2, dtype, dev), dtype)
-        c2 = conv(c1, net.conv2[0], dec.skip_view(2) if skip else _dense(n, 128, H // 4, W // 4, dtype, dev), LEAKY01)
-        feats.append(conv(c2, net.conv3[0], _dense(n, 256, H // 8, W // 8, dtype, dev), LEAKY01))
+        c1 = first_conv(img, net.conv1[0], ctx.conv_out(net.conv1[0], img.shape[2:]), dtype)
+        c2 = conv(c1, net.conv2[0], dec.skip_view(2) if skip else ctx.conv_out(net.conv2[0], c1.hw), LEAKY01)
+        feats.append(conv(c2, net.conv3[0], ctx.conv_out(net.conv3[0], c2.hw), LEAKY01))
     a3, b3 = feats
-    merged = new_buf(n, 512, H // 8, W // 8, dtype, dev)                           # [redir 32 | corr 441 | pad]
+    merged = ctx.buf(512, *a3.hw)                                                  # [redir 32 | corr 441 | pad]
     conv(a3, net.conv_redir[0], View(merged, 0, 32), LEAKY01)
     if not corr_nhwc(net.corr, a3, b3, View(merged, 32, 441), 0.1):                # MFMA cost volume + corr_activation
         cost = net.corr(L.to_nchw_f32(a3.buf), L.to_nchw_f32(b3.buf))             # (shapes it does not cover: scalar kernel, fp32)
         put_nchw(cost, View(merged, 32, 441), act=LEAKY01)
     c3 = conv(View(merged, 0, 473), net.conv3_1[0], dec.skip_view(3), LEAKY01)
-    c4 = conv(conv(c3, net.conv4[0], _dense(n, 512, H // 16, W // 16, dtype, dev), LEAKY01), net.conv4_1[0], dec.skip_view(4), LEAKY01)
-    c5 = conv(conv(c4, net.conv5[0], _dense(n, 512, H // 32, W // 32, dtype, dev), LEAKY01), net.conv5_1[0], dec.skip_view(5), LEAKY01)
-    c6 = conv(conv(c5, net.conv6[0], _dense(n, 1024, H // 64, W // 64, dtype, dev), LEAKY01), net.conv6_1[0],
-              _dense(n, 1024, H // 64, W // 64, dtype, dev), LEAKY01)
-    return dec.run(net, c6)
+    return dec.run(net, dec.encode(net, c3, (4, 5, 6)))
 
 
 def flownets(net, x, dtype):
     """x [N,12,H,W] fp32 -> flow2 (reference FlowNetS.py:57-93)."""
-    Workspace.activate(net, (tuple(x.shape), dtype, x.device))
-    n, _, H, W = x.shape
-    dev = x.device
-    dec = _Decoder(n, H // 64, W // 64, dtype, dev)
-    c1 = first_conv(x, net.conv1[0], _dense(n, 64, H // 2, W // 2, dtype, dev), dtype)
+    ctx, dec = _begin(net, x, dtype)
+    c1 = first_conv(x, net.conv1[0], ctx.conv_out(net.conv1[0], x.shape[2:]), dtype)
     c2 = conv(c1, net.conv2[0], dec.skip_view(2), LEAKY01)
-    c3 = conv(conv(c2, net.conv3[0], _dense(n, 256, H // 8, W // 8, dtype, dev), LEAKY01), net.conv3_1[0], dec.skip_view(3), LEAKY01)
-    c4 = conv(conv(c3, net.conv4[0], _dense(n, 512, H // 16, W // 16, dtype, dev), LEAKY01), net.conv4_1[0], dec.skip_view(4), LEAKY01)
-    c5 = conv(conv(c4, net.conv5[0], _dense(n, 512, H // 32, W // 32, dtype, dev), LEAKY01), net.conv5_1[0], dec.skip_view(5), LEAKY01)
-    c6 = conv(conv(c5, net.conv6[0], _dense(n, 1024, H // 64, W // 64, dtype, dev), LEAKY01), net.conv6_1[0],
-              _dense(n, 1024, H // 64, W // 64, dtype, dev), LEAKY01)
-    return dec.run(net, c6)
+    return dec.run(net, dec.encode(net, c2, (3, 4, 5, 6)))
 
 
 def flownetsd(net, x, dtype):
     """x [N,6,H,W] fp32 -> flow2 (reference FlowNetSD.py:66-105)."""
-    Workspace.activate(net, (tuple(x.shape), dtype, x.device))
-    n, _, H, W = x.shape
-    dev = x.device
-    dec = _Decoder(n, H // 64, W // 64, dtype, dev)
-    c0 = first_conv(x, net.conv0[0], _dense(n, 64, H, W, dtype, dev), dtype)
-    c1 = conv(conv(c0, net.conv1[0], _dense(n, 64, H // 2, W // 2, dtype, dev), LEAKY01), net.conv1_1[0],
-              _dense(n, 128, H // 2, W // 2, dtype, dev), LEAKY01)
-    c2 = conv(conv(c1, net.conv2[0], _dense(n, 128, H // 4, W // 4, dtype, dev), LEAKY01), net.conv2_1[0], dec.skip_view(2), LEAKY01)
-    c3 = conv(conv(c2, net.conv3[0], _dense(n, 256, H // 8, W // 8, dtype, dev), LEAKY01), net.conv3_1[0], dec.skip_view(3), LEAKY01)
-    c4 = conv(conv(c3, net.conv4[0], _dense(n, 512, H // 16, W // 16, dtype, dev), LEAKY01), net.conv4_1[0], dec.skip_view(4), LEAKY01)
-    c5 = conv(conv(c4, net.conv5[0], _dense(n, 512, H // 32, W // 32, dtype, dev), LEAKY01), net.conv5_1[0], dec.skip_view(5), LEAKY01)
-    c6 = conv(conv(c5, net.conv6[0], _dense(n, 1024, H // 64, W // 64, dtype, dev), LEAKY01), net.conv6_1[0],
-              _dense(n, 1024, H // 64, W // 64, dtype, dev), LEAKY01)
-    return dec.run(net, c6, inter=True)
+    ctx, dec = _begin(net, x, dtype)
+    c0 = first_conv(x, net.conv0[0], ctx.conv_out(net.conv0[0], x.shape[2:]), dtype)
+    c1 = conv(c0, net.conv1[0], ctx.conv_out(net.conv1[0], c0.hw), LEAKY01)
+    c1 = conv(c1, net.conv1_1[0], ctx.conv_out(net.conv1_1[0], c1.hw), LEAKY01)
+    return dec.run(net, dec.encode(net, c1, (2, 3, 4, 5, 6)), inter=True)
 
 
 def flownetfusion(net, x, dtype):
     """x [N,11,H,W] fp32 -> flow0 [N,2,H,W] (reference FlowNetFusion.py:47-66)."""
-    Workspace.activate(net, (tuple(x.shape), dtype, x.device))
+    ctx = _Run(net, x, dtype)
     n, _, H, W = x.shape
-    dev = x.device
-    cat0 = new_buf(n, 128, H, W, dtype, dev)            # [conv0 64 | deconv0 16 | flow1_up 2 | pad]
-    cat1 = new_buf(n, 192, H // 2, W // 2, dtype, dev)  # [conv1 128 | deconv1 32 | flow2_up 2 | pad]
+    cat0 = ctx.buf(128, H, W)            # [conv0 64 | deconv0 16 | flow1_up 2 | pad]
+    cat1 = ctx.buf(192, H // 2, W // 2)  # [conv1 128 | deconv1 32 | flow2_up 2 | pad]
     c0 = first_conv(x, net.conv0[0], View(cat0, 0, 64), dtype)
-    c1 = conv(conv(c0, net.conv1[0], _dense(n, 64, H // 2, W // 2, dtype, dev), LEAKY01), net.conv1_1[0], View(cat1, 0, 128), LEAKY01)
-    c2 = conv(conv(c1, net.conv2[0], _dense(n, 128, H // 4, W // 4, dtype, dev), LEAKY01), net.conv2_1[0],
-              _dense(n, 128, H // 4, W // 4, dtype, dev), LEAKY01)
+    c1 = conv(conv(c0, net.conv1[0], ctx.conv_out(net.conv1[0], c0.hw), LEAKY01), net.conv1_1[0], View(cat1, 0, 128), LEAKY01)
+    c2 = conv(c1, net.conv2[0], ctx.conv_out(net.conv2[0], c1.hw), LEAKY01)
+    c2 = conv(c2, net.conv2_1[0], ctx.conv_out(net.conv2_1[0], c2.hw), LEAKY01)
     flow2 = predict(c2, net.predict_flow2, n, H // 4, W // 4)
     flow_up(flow2, net.upsampled_flow2_to_1, View(cat1, 160, 2))
     conv(c2, net.deconv1[0], View(cat1, 128, 32), LEAKY01, transposed=True)
-    i1 = conv(View(cat1, 0, 162), net.inter_conv1[0], _dense(n, 32, H // 2, W // 2, dtype, dev), 0)
+    i1 = conv(View(cat1, 0, 162), net.inter_conv1[0], ctx.conv_out(net.inter_conv1[0], (H // 2, W // 2)), 0)
     flow1 = predict(i1, net.predict_flow1, n, H // 2, W // 2)
     flow_up(flow1, net.upsampled_flow1_to_0, View(cat0, 80, 2))
     conv(View(cat1, 0, 162), net.deconv0[0], View(cat0, 64, 16), LEAKY01, transposed=True)
-    i0 = conv(View(cat0, 0, 82), net.inter_conv0[0], _dense(n, 16, H, W, dtype, dev), 0)
+    i0 = conv(View(cat0, 0, 82), net.inter_conv0[0], ctx.conv_out(net.inter_conv0[0], (H, W)), 0)
     return predict(i0, net.predict_flow0, n, H, W)

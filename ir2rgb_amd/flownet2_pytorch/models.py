@@ -6,12 +6,14 @@ networks/{FlowNetC,FlowNetS,FlowNetSD,FlowNetFusion,submodules}.py so that the p
 variant: ``conv*.0`` = Conv2d, ``deconv*.0`` = ConvTranspose2d).  Only ``FlowNet2`` is built (the
 C/S/SD/CS/CSS variants are unused by ir2rgb).
 
-Scope: the convolution stacks here are ordinary torch convolutions on
-the GPU (0.53 TFLOP per pair, frozen, no_grad); what is hand-written is what the reference
-hand-wrote -- Correlation, Resample2d, ChannelNorm -- plus the fused warp->diff->norm step
-(ir2rgb_warp_diff_norm_fwd) that replaces three launches at models.py:109-111, :121-123.
-``conv_dtype`` selects the torch convolution precision (bf16 channels_last by default, matching
-the reference's optional --fp16 path in spirit; the three operators always run in fp32).
+What runs (0.53 TFLOP per pair, frozen, no_grad): by default every sub-network's
+convolution stack goes through the MFMA engine of ir2rgb_amd/flownet2_hip.py, which executes this parameter
+tree (``FlowNet2._net``), next to what the reference hand-wrote -- Correlation, Resample2d, ChannelNorm --
+and the fused warp->diff->norm step (ir2rgb_warp_diff_norm_fwd) that replaces three launches at
+models.py:109-111, :121-123.  The ``forward`` methods of the sub-networks, ordinary torch convolutions, are
+the test reference: ``use_hip_convs = False`` runs them, in ``conv_dtype`` (autocast, channels_last) or fp32.
+``conv_dtype`` is also the engine's operand type (bf16 by default; float32 selects bf16 there); the three
+operators always run in fp32.
 """
 import torch
 import torch.nn as nn
@@ -49,7 +51,7 @@ def _flownet_init(module):
 
 
 class _Refiner(nn.Module):
-    """Shared coarse-to-fine decoder of FlowNetC / FlowNetS: levels 6 -> 2."""
+    """Coarse-to-fine decoder of FlowNetC / FlowNetS / FlowNetSD: levels 6 -> 2."""
 
     def _build_decoder(self, up_bias):
         self.deconv5, self.deconv4, self.deconv3, self.deconv2 = deconv(1024, 512), deconv(1026, 256), deconv(770, 128), deconv(386, 64)
@@ -58,13 +60,15 @@ class _Refiner(nn.Module):
         for a, b in ((6, 5), (5, 4), (4, 3), (3, 2)):
             setattr(self, f"upsampled_flow{a}_to_{b}", nn.ConvTranspose2d(2, 2, 4, 2, 1, bias=up_bias))
 
-    def _decode(self, c6, c5, c4, c3, c2):
-        feat, skips = c6, {5: c5, 4: c4, 3: c3, 2: c2}
+    def _decode(self, c6, c5, c4, c3, c2, inter=False):
+        """``inter`` (FlowNetSD): predict_flow reads the level's inter_conv, not the concatenation itself."""
+        feat, flow_in, skips = c6, c6, {5: c5, 4: c4, 3: c3, 2: c2}
         for lvl in (6, 5, 4, 3):
-            flow = getattr(self, f"predict_flow{lvl}")(feat)
+            flow = getattr(self, f"predict_flow{lvl}")(flow_in)
             up = getattr(self, f"upsampled_flow{lvl}_to_{lvl - 1}")(flow)
             feat = torch.cat((skips[lvl - 1], getattr(self, f"deconv{lvl - 1}")(feat), up), 1)
-        return self.predict_flow2(feat)
+            flow_in = getattr(self, f"inter_conv{lvl - 1}")(feat) if inter else feat
+        return self.predict_flow2(flow_in)
 
 
 class FlowNetC(_Refiner):
@@ -113,7 +117,7 @@ class FlowNetS(_Refiner):
         return self._decode(c6, c5, c4, c3, c2)
 
 
-class FlowNetSD(nn.Module):
+class FlowNetSD(_Refiner):   # (its own decoder modules: built below, not by _build_decoder)
     def __init__(self):
         super().__init__()
         self.conv0 = conv(6, 64)
@@ -139,13 +143,7 @@ class FlowNetSD(nn.Module):
         c4 = self.conv4_1(self.conv4(c3))
         c5 = self.conv5_1(self.conv5(c4))
         c6 = self.conv6_1(self.conv6(c5))
-        feat, flow_in, skips = c6, c6, {5: c5, 4: c4, 3: c3, 2: c2}
-        for lvl in (6, 5, 4, 3):
-            flow = getattr(self, f"predict_flow{lvl}")(flow_in)
-            up = getattr(self, f"upsampled_flow{lvl}_to_{lvl - 1}")(flow)
-            feat = torch.cat((skips[lvl - 1], getattr(self, f"deconv{lvl - 1}")(feat), up), 1)
-            flow_in = getattr(self, f"inter_conv{lvl - 1}")(feat)
-        return self.predict_flow2(flow_in)
+        return self._decode(c6, c5, c4, c3, c2, inter=True)
 
 
 class FlowNetFusion(nn.Module):
@@ -172,8 +170,12 @@ class FlowNetFusion(nn.Module):
         return self.predict_flow0(self.inter_conv0(cat0))
 
 
+_HIP_ENGINE = {FlowNetC: "flownetc", FlowNetS: "flownets", FlowNetSD: "flownetsd", FlowNetFusion: "flownetfusion"}  # in flownet2_hip
+
+
 class FlowNet2(nn.Module):
     """inputs [B,3,2,H,W] (H, W multiples of 64) -> flow [B,2,H,W] fp32 (reference models.py:96-161)."""
+    use_hip_convs = True  # False: torch convolutions (kept as the GPU reference for tests/test_flownet2_gpu.py)
 
     def __init__(self, args=None, batchNorm=False, div_flow=20.0, fp16=False, conv_dtype=torch.bfloat16):
         super().__init__()
@@ -193,16 +195,13 @@ class FlowNet2(nn.Module):
         self.flownetfusion = FlowNetFusion()
         _flownet_init(self)
 
-    use_hip_convs = True  # False: torch convolutions (kept as the GPU reference for tests/test_flownet2_gpu.py)
-
     def _net(self, net, x):
         """One sub-network.  Product path: the MFMA engine of ir2rgb_amd/flownet2_hip.py; test reference:
         the torch convolution stack in conv_dtype / channels_last.  Result in fp32 either way."""
         if self.use_hip_convs:
             from .. import flownet2_hip as FH
-            run = {FlowNetC: FH.flownetc, FlowNetS: FH.flownets, FlowNetSD: FH.flownetsd, FlowNetFusion: FH.flownetfusion}
             dt = torch.bfloat16 if self.conv_dtype == torch.float32 else self.conv_dtype
-            return run[type(net)](net, x.float().contiguous(), dt)
+            return getattr(FH, _HIP_ENGINE[type(net)])(net, x.float().contiguous(), dt)
         if self.conv_dtype == torch.float32:
             return net(x)
         with torch.autocast("cuda", dtype=self.conv_dtype):

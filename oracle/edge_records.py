@@ -275,7 +275,7 @@ FLOW_FORMS = (
 
 
 def corr_form(N, C, H, W, pad, k, md, s1, s2, aligned=True):
-    """The kernel ir2rgb_correlation_fwd launches (correlation.hip:453-468) and, for corr_fwd_lds, how many 8-channel
+    """The kernel ir2rgb_correlation_fwd launches (its dispatch in correlation.hip) and, for corr_fwd_lds, how many 8-channel
     stages its 4-stage ring sees and whether the grid is renumbered over the XCDs (a multiple of 8 workgroups)."""
     fast = k == 1 and s1 == 1 and pad == md and s2 == 2 and md // s2 == 10 and md == 20 and W % 8 == 0 and aligned and C > 0
     if not fast:

@@ -73,7 +73,7 @@ def correlation(f1, f2, pad, k, md, s1, s2, clamp_border=False):
 
 
 def correlation_bwd(f1, f2, gout, pad, k, md, s2):
-    """stride1 = 1.  -> (gin1, gin2, S1, S2, L1, L2) with the windows of corr_bwd_kernel (correlation.hip:372-432,
+    """stride1 = 1.  -> (gin1, gin2, S1, S2, L1, L2) with the windows of corr_bwd_kernel (correlation.hip,
     oracle/ops_ref.c): in padded coordinates (y, x) = (by + pad, bx + pad),
 
       gin1[n,c,by,bx] = 1/(k^2 C) sum_tc f2[n,c,by + j2,bx + i2] * sum of gout[n,tc] over [y-kr-md, y+kr-md] x [x-kr-md, x+kr-md]

@@ -45,6 +45,30 @@ def test_subnetwork_vs_torch_convs(dev, net, name, cin):
     assert err <= 1e-2, err
 
 
+@pytest.mark.parametrize("name,cin", [("flownetc", 6), ("flownets_1", 12), ("flownets_d", 6), ("flownetfusion", 11)])
+def test_subnetwork_pools_under_alternating_shapes(dev, net, name, cin):
+    """One module called at [1, cin, 128, 192], then [2, cin, 128, 192], then the first input again: each call draws its
+    buffers from the pool of its own (shape, dtype, device), so the third result is the first one bit for bit and no pool
+    grows after its first use."""
+    from ir2rgb_amd import flownet2_hip as FH
+    sub = getattr(net, name)
+    run = {"flownetc": FH.flownetc, "flownets_1": FH.flownets, "flownets_d": FH.flownetsd, "flownetfusion": FH.flownetfusion}[name]
+    g = torch.Generator().manual_seed(cin)
+    x1 = (torch.randn(1, cin, 128, 192, generator=g) * 0.5).to(dev)
+    x2 = (torch.randn(2, cin, 128, 192, generator=g) * 0.5).to(dev)
+    outs, first_use = [], {}
+    with torch.no_grad():
+        for x in (x1, x2, x1):
+            outs.append(run(sub, x, torch.bfloat16))
+            for key, pool in sub._ir2rgb_workspaces.items():
+                first_use.setdefault(key, len(pool))
+    assert outs[0].shape[0] == 1 and outs[1].shape[0] == 2 and torch.isfinite(outs[1]).all()
+    assert torch.equal(outs[2], outs[0])
+    keys = {(tuple(x.shape), torch.bfloat16, x.device) for x in (x1, x2)}
+    assert keys <= set(first_use) and all(first_use[k] > 0 for k in keys)
+    assert {key: len(pool) for key, pool in sub._ir2rgb_workspaces.items()} == first_use
+
+
 def test_flownet2_composed(dev, net):
     g = torch.Generator().manual_seed(8)
     base = torch.rand(1, 3, 128 + 8, 192 + 8, generator=g)
