@@ -692,6 +692,44 @@ typedef struct ir2rgb_panel {
 long ir2rgb_visuals_workspace_bytes(int n_flow_panels, int H, int W);
 int ir2rgb_visuals_u8(const ir2rgb_panel *panels, int n, int H, int W, float *workspace, uint8_t *out, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * JPEG output (jpeg.hip): baseline JPEG files of uint8 frames, equal byte for byte to the files Pillow (libjpeg)
+ * writes with Image.save(f, "JPEG", quality=q, subsampling=..., restart_marker_rows=restart_rows); the rules are
+ * restated in ir2rgb_amd/jpeg.py (jpeg_reference), which is the definition.
+ *   src [N][H][W][C] uint8, C in {1, 3}.  mode IR2RGB_JPEG_444 / _420 (C = 3: YCbCr, interleaved MCUs) or IR2RGB_JPEG_L
+ *   (one component: channel 0 at pixel stride C, so a one-channel panel of a three-channel stack needs no copy).
+ *   out [N][capacity] uint8: file n = the header, then the scan with FF D0+(i mod 8) after every restart_rows MCU
+ *   rows, then FF D9; lengths [N] int32 = its size.  Bytes of out past the length are not written.
+ * header (device, header_bytes bytes) is everything up to and including SOS, built on the host; tables (device,
+ * uint32 [672]) come from the same host objects: quantisation [2][64] in natural order (luminance, chrominance), DC
+ * codes [2][16] and AC codes [2][256] indexed by symbol as (code length << 16 | code).  max_dc_len / max_ac_len
+ * (1..16) are the longest code lengths of those tables; lengths read from the tables are clamped to them and
+ * quantisation entries to [1, 255].
+ * Capacity: a block codes to at most bits = (max_dc_len + 11) + 63 * (max_ac_len + 10) bits -- its DC code, and at
+ * most 63 AC codes of at most max_ac_len + 10 bits, since every AC code (a coefficient, ZRL, EOB) accounts for at
+ * least one of the 63 positions that no other code accounts for.  A restart interval of B = restart_rows * MCUs per
+ * row * blocks per MCU blocks is at most ceil(B * bits / 8) bytes with its padding, twice that after byte stuffing
+ * (rounded up to 16), plus 2 marker bytes: ir2rgb_jpeg_capacity_bytes = header_bytes + intervals * that.
+ * The workspace is the caller's, ir2rgb_jpeg_workspace_bytes(...) bytes (both counts negative for invalid sizes):
+ * the quantised blocks int16 [N][blocks][64] in coding and zigzag order, the byte count of every interval, and one
+ * capacity-sized scratch region per interval.  Every part is written before it is read.  Three launches whatever N
+ * and the pixels are; integers only.  No buffer may alias out or the workspace.
+ * IR2RGB_EINVAL: a NULL pointer, N outside [1, 65535], H or W outside [1, 65535], C or mode unknown or C != 3 in a
+ * colour mode, restart_rows < 1 or an interval above 65535 MCUs, header_bytes < 1, code lengths outside [1, 16],
+ * capacity or workspace_bytes too small, a worst-case file above 2^31 - 1 bytes; IR2RGB_EALIGN: workspace off a
+ * 16-byte, tables or lengths off a 4-byte boundary.  Both before any launch.
+ * ------------------------------------------------------------------------------------------ */
+#define IR2RGB_JPEG_444 0
+#define IR2RGB_JPEG_420 1
+#define IR2RGB_JPEG_L 2
+#define IR2RGB_JPEG_TABLE_WORDS 672
+
+long ir2rgb_jpeg_workspace_bytes(int N, int H, int W, int mode, int restart_rows, int max_dc_len, int max_ac_len);
+long ir2rgb_jpeg_capacity_bytes(int H, int W, int mode, int restart_rows, int header_bytes, int max_dc_len, int max_ac_len);
+int ir2rgb_jpeg_encode_u8(const uint8_t *src, uint8_t *out, int *lengths, void *workspace, long workspace_bytes,
+                          const uint8_t *header, int header_bytes, const unsigned *tables, int N, int C, int H, int W, int mode,
+                          int restart_rows, int max_dc_len, int max_ac_len, long capacity, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

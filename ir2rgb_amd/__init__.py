@@ -7,7 +7,8 @@ first use and its absence is an error (there is no CPU fallback).
 __version__ = "0.1.0"
 
 __all__ = ["VideoTranslator", "VideoScore", "video_metrics", "ssim_reference", "warp_error", "warp_error_reference",
-           "warp_bound", "FrameScaler", "img_params", "resample_coeffs", "resize_reference", "TrainingSchedule", "LossLog", "fit", "Snapshots", "to_u8_reference", "flow_to_rgb_reference"]
+           "warp_bound", "FrameScaler", "img_params", "resample_coeffs", "resize_reference", "TrainingSchedule", "LossLog", "fit", "Snapshots", "to_u8_reference", "flow_to_rgb_reference",
+           "JpegEncoder", "jpeg_reference"]
 
 
 def __getattr__(name):
@@ -24,6 +25,9 @@ def __getattr__(name):
     if name in ("Snapshots", "to_u8_reference", "flow_to_rgb_reference"):
         from . import visuals
         return getattr(visuals, name)
+    if name in ("JpegEncoder", "jpeg_reference"):
+        from . import jpeg
+        return getattr(jpeg, name)
     if name == "TrainingSchedule":
         from .schedule import TrainingSchedule
         return TrainingSchedule

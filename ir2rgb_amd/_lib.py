@@ -158,6 +158,9 @@ PROTOTYPES = {
     "ir2rgb_frame_scale_u8": (c_int, [P, P, P, c_long, P, P, c_int, P, P, c_int] + [c_int] * 12 + [P]),
     "ir2rgb_visuals_workspace_bytes": (c_long, [c_int] * 3),
     "ir2rgb_visuals_u8": (c_int, [_ppanel, c_int, c_int, c_int, P, P, P]),
+    "ir2rgb_jpeg_workspace_bytes": (c_long, [c_int] * 7),
+    "ir2rgb_jpeg_capacity_bytes": (c_long, [c_int] * 7),
+    "ir2rgb_jpeg_encode_u8": (c_int, [P, P, P, P, c_long, P, c_int, P] + [c_int] * 8 + [c_long, P]),
 }
 
 _lib = None

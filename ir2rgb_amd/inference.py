@@ -124,6 +124,7 @@ class VideoTranslator:
         tr.reset()                                                           # a new sequence (test_vid2vid.py:39-40)
         rgb = tr.push(ir_u8)                  # uint8 [H,W,C] -> uint8 [H,W,3] device tensor; None for the first tG-1 frames
         for rgb in tr.translate(frames): ...
+        paths = tr.save(frames, out_dir)      # the same frames as JPEG files, encoded on the device
 
     ``**opt`` takes the option names and defaults of ``Vid2VidTrainer`` (``n_scales_spatial``, ``first_layer_gen_filters``
     (alias ``ngf``), ``n_input_gen_frames``, ``no_flow``, ``compute_dtype`` ...).  ``netG``: a trainer's generator list, used
@@ -202,6 +203,7 @@ class VideoTranslator:
             g.compute_dtype = o["compute_dtype"]
             g.train(norm_stats == "batch")
         self.seq = SequenceState(self.tG)
+        self._jpeg = (None, None)       # (options, JpegEncoder) of the last save()
         self.scaler = self.scaler_rgb = None
         if scaler is not None or source_size is not None:
             self._set_scaler(scaler, source_size, scale_opt, scale_rng)
@@ -349,6 +351,37 @@ class VideoTranslator:
             out = self.push(f, real_rgb[i] if i < len(real_rgb) else None)
             if out is not None:
                 yield out
+
+    def save(self, frames, out_dir, real_rgb=None, pattern="%06d.jpg", **jpeg_options):
+        """``translate(frames, real_rgb)`` written to ``out_dir`` as one JPEG file per output frame (what the reference's
+        test script does with ``save_images``): output ``k`` goes to ``pattern % k``.  -> the list of paths.
+
+        The files are encoded on the device (``ir2rgb_amd.jpeg.JpegEncoder``; ``jpeg_options``: ``quality``,
+        ``subsampling``, ``restart_rows``, Pillow's defaults otherwise) and are the bytes Pillow writes for the same frame
+        and options.  Frame ``k`` is submitted to the encoder before file ``k - 1`` is collected and written, so the device
+        encodes (and translates on) while the host writes.  The encoder's launches follow the step on the current stream;
+        they are not part of the captured graph."""
+        from .jpeg import JpegEncoder
+        key = tuple(sorted(jpeg_options.items()))
+        if self._jpeg[0] != key:
+            self._jpeg = (key, JpegEncoder(self.device, self.H, self.W, channels=3, **jpeg_options))
+        enc = self._jpeg[1]
+        os.makedirs(out_dir, exist_ok=True)
+        paths = []
+
+        def write_oldest():
+            data, = enc.collect()
+            paths.append(os.path.join(out_dir, pattern % len(paths)))
+            with open(paths[-1], "wb") as f:
+                f.write(data)
+
+        for k, out in enumerate(self.translate(frames, real_rgb)):
+            enc.submit(out)
+            if k:
+                write_oldest()
+        if enc._pending:
+            write_oldest()
+        return paths
 
     def evaluate(self, frames, targets, real_rgb=None, data_range="reference", temporal=None):
         """``translate(frames, real_rgb)`` scored against a ground-truth RGB track (reference scripts/ssim_metric.py):

@@ -203,13 +203,23 @@ class Snapshots:
     ``{out_dir}/images/epoch%.3d_%s.{fmt}`` (the reference's labels, visualizer.py:58-62; one-channel panels as mode L) at
     the start of the next ``take`` or in ``flush()``, after that event.  ``html``: ``{out_dir}/index.html`` lists every
     epoch, newest first, in the two rows of visualizer.py:84-89.  ``freq`` is the reference's ``display_freq``: ``fit``
-    takes a snapshot after every sequence that brings ``total_steps`` to a multiple of it."""
+    takes a snapshot after every sequence that brings ``total_steps`` to a multiple of it.
 
-    def __init__(self, device, out_dir, freq=100, fmt="jpg", html=True, input_panel="reference"):
+    ``encoder``: ``"host"`` (default) copies the raw stack out and lets Pillow compress it in ``write_pending``.
+    ``"device"`` compresses the panels on the device (ir2rgb_amd.jpeg.JpegEncoder with Pillow's defaults: quality 75,
+    4:2:0, mode L for one-channel panels, one restart marker per MCU row) inside ``take``; only the file sizes and then the
+    compressed bytes are copied.  It needs ``fmt="jpg"``.  A decoder reads the same pixels from either file."""
+
+    def __init__(self, device, out_dir, freq=100, fmt="jpg", html=True, input_panel="reference", encoder="host"):
         if freq < 1:
             raise ValueError("Snapshots: freq >= 1")
         if input_panel not in ("reference", "normalised"):
             raise ValueError("input_panel: 'reference' or 'normalised'")
+        if encoder not in ("host", "device"):
+            raise ValueError("encoder: 'host' (Pillow) or 'device' (csrc/jpeg.hip)")
+        if encoder == "device" and fmt != "jpg":
+            raise ValueError("Snapshots: encoder='device' writes JPEG files (fmt='jpg')")
+        self.encoder = encoder
         self.device, self.out_dir, self.freq, self.fmt, self.html = torch.device(device), str(out_dir), int(freq), fmt, html
         self.input_panel = input_panel
         self.img_dir = os.path.join(self.out_dir, "images")
@@ -219,6 +229,7 @@ class Snapshots:
         self._stack = self._workspace = None
         self._host = [None, None]
         self._pending = None            # (host buffer index, event, epoch, [(name, channels)])
+        self._jpeg = None               # encoder="device": see _reserve_jpeg
 
     def due(self, total_steps):
         """train_vid2vid.py:46 with ``total_steps`` as it stands after the sequence."""
@@ -229,8 +240,31 @@ class Snapshots:
             self.flush()
             self._stack = torch.empty((n, H, W, 3), dtype=torch.uint8, device=self.device)
             self._workspace = torch.empty(max(workspace_elems(n_flow, H, W), 1), dtype=torch.float32, device=self.device)
-            self._host = [torch.empty((n, H, W, 3), dtype=torch.uint8, pin_memory=True) for _ in range(2)]
+            if self.encoder == "device":
+                self._reserve_jpeg(n, H, W)
+            else:
+                self._host = [torch.empty((n, H, W, 3), dtype=torch.uint8, pin_memory=True) for _ in range(2)]
             self._shape = (n, H, W, n_flow)
+
+    def _reserve_jpeg(self, n, H, W):
+        """The device encoders (three-channel panels; channel 0 of the stack as mode L), one output row and one size per
+        panel, and the pinned staging of the sizes and of one file."""
+        from .jpeg import JpegEncoder
+        enc = {3: JpegEncoder(self.device, H, W), 1: JpegEncoder(self.device, H, W, channels=3, subsampling="L")}
+        cap = max(e.capacity for e in enc.values())
+        self._jpeg = dict(enc=enc, out=torch.empty((n, cap), dtype=torch.uint8, device=self.device),
+                          lengths=torch.empty(n, dtype=torch.int32, device=self.device),
+                          workspace=torch.empty(max(e.workspace_bytes(1) for e in enc.values()), dtype=torch.uint8,
+                                                device=self.device),
+                          host_lengths=torch.empty(n, dtype=torch.int32, pin_memory=True),
+                          host=torch.empty(cap, dtype=torch.uint8, pin_memory=True))
+
+    def _encode_panels(self, plist):
+        j = self._jpeg
+        for i, (_, _, t) in enumerate(plist):
+            j["enc"][1 if t.shape[0] == 1 else 3].encode_into(self._stack[i:i + 1], j["out"][i:i + 1], j["lengths"][i:i + 1],
+                                                             j["workspace"])
+        j["host_lengths"].copy_(j["lengths"], non_blocking=True)
 
     def take(self, trainer, epoch, fake_B_first):
         """Snapshot of the trainer's last window (``last_inputs`` / ``last_outputs``) and the sequence's first generated
@@ -243,7 +277,10 @@ class Snapshots:
         with torch.cuda.device(self.device):
             compose(plist, self._stack, self._workspace)
             slot = self.count % 2
-            self._host[slot].copy_(self._stack, non_blocking=True)
+            if self.encoder == "device":
+                self._encode_panels(plist)
+            else:
+                self._host[slot].copy_(self._stack, non_blocking=True)
             event = torch.cuda.Event()
             event.record()
             # FlowNet2's next replay overwrites flow_ref / conf_ref and may run AHEAD of this stream (it is ordered after
@@ -260,10 +297,24 @@ class Snapshots:
         slot, event, epoch, names = self._pending
         self._pending = None
         event.synchronize()
-        write_images(self.img_dir, epoch, names, self._host[slot].numpy(), self.fmt)
+        if self.encoder == "device":
+            self._write_files(epoch, names)
+        else:
+            write_images(self.img_dir, epoch, names, self._host[slot].numpy(), self.fmt)
         self.names = [name for name, _ in names]
         if self.html:
             write_index(self.out_dir, epoch, self.names, self.fmt)
+
+    def _write_files(self, epoch, names):
+        from .jpeg import fetch
+        j = self._jpeg
+        os.makedirs(self.img_dir, exist_ok=True)
+        for i, (label, _) in enumerate(names):
+            m = int(j["host_lengths"][i])
+            if not 0 < m <= j["out"].shape[1]:
+                raise RuntimeError(f"Snapshots: panel {label!r} reports {m} bytes")
+            with open(os.path.join(self.img_dir, image_name(epoch, label, self.fmt)), "wb") as f:
+                f.write(fetch(j["out"][i, :m], j["host"]))         # (on a copy stream: not behind the windows queued since)
 
     def flush(self):
         """Writes the snapshot that is still on its way (``fit`` calls this before it returns)."""
