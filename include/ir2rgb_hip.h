@@ -730,6 +730,50 @@ int ir2rgb_jpeg_encode_u8(const uint8_t *src, uint8_t *out, int *lengths, void *
                           const uint8_t *header, int header_bytes, const unsigned *tables, int N, int C, int H, int W, int mode,
                           int restart_rows, int max_dc_len, int max_ac_len, long capacity, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * JPEG input (jpeg_decode.hip): baseline JPEG files decoded into uint8 frames, equal pixel for pixel to what Pillow
+ * (libjpeg-turbo) decodes, np.asarray(Image.open(f)); the rules are restated in ir2rgb_amd/jpeg_decode.py
+ * (decode_reference for the pixels, entropy_model for the parallel entropy decode), which is the definition.
+ *   files: the scan bytes (everything behind SOS up to the closing marker, still byte-stuffed, restart markers
+ *   included) of N files, one after the other, any alignment; file_offsets int32 [N + 1]: file n is bytes
+ *   [file_offsets[n], file_offsets[n + 1]) of files.
+ *   segments int32 [N][n_segments][4]: one record per restart interval, (begin, end, first MCU, MCUs) with the byte
+ *   range relative to the file's scan bytes and without the marker; a file without DRI has one record; records a file
+ *   does not use are all zero.  tables int32 [N][IR2RGB_JPEGD_TABLE_WORDS], per file: the quantisation table of every
+ *   component [3][64] in natural order; the Huffman table slot (0..1) of every component, DC [3] then AC [3], 2 words
+ *   unused; four Huffman tables DC 0, DC 1, AC 0, AC 1 of 288 words: limit [16], offset [16], values [256] -- the code of
+ *   a 16-bit window w has the smallest length l with w < limit[l - 1] and the symbol values[offset[l - 1] + (w >> (16 -
+ *   l))].  All files of a call share H, W and mode (IR2RGB_JPEG_444 / _420 / _422: three components, YCbCr, luminance
+ *   sampled 1x1 / 2x2 / 2x1; IR2RGB_JPEG_L: one component); tables, restart intervals and sizes are per file.
+ *   out [N][H][W][C_out] uint8; C_out = 3 in mode L replicates the channel.  status [N] int32: 0, or the IR2RGB_JPEGD_E*
+ *   bits of the damage the decode of file n met (the pixels of such a file are unspecified but written).
+ * A segment's bytes are cut into subsequences of sub_bytes (>= 1; enlarged per segment to ceil(bytes /
+ * IR2RGB_JPEGD_THREADS) when it has more than that many), which one workgroup decodes in parallel by relaxation: see
+ * jpeg_decode.hip.  The result does not depend on sub_bytes.  Every read of files stays inside the record's range
+ * clamped to the file's; no decoded value is used as an index unclamped; records are clamped to the frame's MCUs.
+ * The workspace is the caller's, ir2rgb_jpeg_decode_workspace_bytes(...) bytes (negative for invalid sizes): the
+ * coefficients int16 [N][blocks][64], the component planes on their block grids, and (status bits, relaxation rounds)
+ * int32 [N][n_segments][2] at its end.  Every part is written before it is read.  Three launches whatever N and the
+ * files are; integers only.  No buffer may alias out, status or the workspace.
+ * IR2RGB_EINVAL: a NULL pointer, N or n_segments outside [1, 65535], H or W outside [1, 65535], C_out or mode
+ * unknown or C_out != 3 in a colour mode, sub_bytes < 1, workspace_bytes too small, more than 2^31 - 1 coefficient
+ * bytes; IR2RGB_EALIGN: workspace off a 16-byte, file_offsets, segments, tables or status off a 4-byte boundary.
+ * Both before any launch.
+ * ------------------------------------------------------------------------------------------ */
+#define IR2RGB_JPEG_422 3
+#define IR2RGB_JPEGD_TABLE_WORDS 1352
+#define IR2RGB_JPEGD_THREADS 512
+#define IR2RGB_JPEGD_ECODE 1     /* 16 bits that are no Huffman code */
+#define IR2RGB_JPEGD_EINDEX 2    /* a coefficient index past 63 */
+#define IR2RGB_JPEGD_EBLOCKS 4   /* the segment does not hold its MCUs' blocks */
+#define IR2RGB_JPEGD_ELEFTOVER 8 /* more than the padding is left behind the last block */
+#define IR2RGB_JPEGD_ESEGMENT 16 /* a segment record outside the frame's MCUs */
+
+long ir2rgb_jpeg_decode_workspace_bytes(int N, int H, int W, int mode, int n_segments);
+int ir2rgb_jpeg_decode_u8(const uint8_t *files, const int *file_offsets, const int *segments, const int *tables, uint8_t *out,
+                          int *status, void *workspace, long workspace_bytes, int N, int C_out, int H, int W, int mode,
+                          int n_segments, int sub_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

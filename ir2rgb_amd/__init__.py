@@ -8,7 +8,7 @@ __version__ = "0.1.0"
 
 __all__ = ["VideoTranslator", "VideoScore", "video_metrics", "ssim_reference", "warp_error", "warp_error_reference",
            "warp_bound", "FrameScaler", "img_params", "resample_coeffs", "resize_reference", "TrainingSchedule", "LossLog", "fit", "Snapshots", "to_u8_reference", "flow_to_rgb_reference",
-           "JpegEncoder", "jpeg_reference"]
+           "JpegEncoder", "jpeg_reference", "JpegDecoder", "decode_reference", "FolderSequences"]
 
 
 def __getattr__(name):
@@ -28,6 +28,12 @@ def __getattr__(name):
     if name in ("JpegEncoder", "jpeg_reference"):
         from . import jpeg
         return getattr(jpeg, name)
+    if name in ("JpegDecoder", "decode_reference"):
+        from . import jpeg_decode
+        return getattr(jpeg_decode, name)
+    if name == "FolderSequences":
+        from .frames import FolderSequences
+        return FolderSequences
     if name == "TrainingSchedule":
         from .schedule import TrainingSchedule
         return TrainingSchedule

@@ -161,6 +161,8 @@ PROTOTYPES = {
     "ir2rgb_jpeg_workspace_bytes": (c_long, [c_int] * 7),
     "ir2rgb_jpeg_capacity_bytes": (c_long, [c_int] * 7),
     "ir2rgb_jpeg_encode_u8": (c_int, [P, P, P, P, c_long, P, c_int, P] + [c_int] * 8 + [c_long, P]),
+    "ir2rgb_jpeg_decode_workspace_bytes": (c_long, [c_int] * 5),
+    "ir2rgb_jpeg_decode_u8": (c_int, [P] * 7 + [c_long] + [c_int] * 7 + [P]),
 }
 
 _lib = None

@@ -161,3 +161,109 @@ def scaled_sequence(ir_u8, rgb_u8, scaler=None, rng=None, **scale_opt):
     a = scaler.with_channels(c)(ir_u8.contiguous(), normalised=True)
     b = scaler.with_channels(3)(rgb_u8.contiguous(), normalised=True)
     return a.view(1, t * c, h, w), b.view(1, t * 3, h, w), scaler
+
+
+def video_params(cur_seq_len, index, rng=None, **opt):
+    """Which frames of a sequence of ``cur_seq_len`` files one training item reads, as the reference's ``get_video_params``
+    chooses them (data/transform.py:116-131, the training branch): options ``n_frames_total``, ``n_input_gen_frames``,
+    ``max_frames_per_gpu``, ``max_t_step``, ``gen_gpus``, ``batch_size`` (the reference's names).  ``rng``: a
+    ``numpy.random``-like source (the module itself by default, or a ``RandomState``), drawn from in the reference's order:
+    ``randint(max_t_step)`` for the frame spacing, then ``randint(offset_max)`` for the first frame -- so a seeded run
+    reproduces the reference's choice.  ``is_train=False`` is its test branch: tG frames from ``index`` on, no draw.
+    -> (n_frames_total, start_idx, t_step)."""
+    import numpy as np
+    npr = rng if rng is not None else np.random
+    n_frames_total, tG = int(opt["n_frames_total"]), int(opt.get("n_input_gen_frames", 3))
+    if not opt.get("is_train", True):
+        return tG, int(index), 1
+    n_frames_total = min(n_frames_total, cur_seq_len - tG + 1)
+    if n_frames_total < 1:
+        raise ValueError(f"video_params: a sequence of {cur_seq_len} frames is shorter than n_input_gen_frames = {tG}")
+    n_gpus = opt.get("gen_gpus", 1) if opt.get("batch_size", 1) == 1 else 1
+    n_frames_per_load = min(n_frames_total, opt.get("max_frames_per_gpu", 1) * n_gpus)
+    n_loadings = n_frames_total // n_frames_per_load
+    n_frames_total = n_frames_per_load * n_loadings + tG - 1
+    max_t_step = min(opt.get("max_t_step", 1), (cur_seq_len - 1) // max(n_frames_total - 1, 1))
+    t_step = int(npr.randint(max_t_step)) + 1
+    offset_max = max(1, cur_seq_len - (n_frames_total - 1) * t_step)
+    start_idx = int(npr.randint(offset_max))
+    return n_frames_total, start_idx, t_step
+
+
+_JPEG_NAMES = (".jpg", ".JPG", ".jpeg", ".JPEG")
+_IMAGE_NAMES = _JPEG_NAMES + (".pgm", ".PGM", ".png", ".PNG", ".ppm", ".PPM", ".bmp", ".BMP", ".tiff", ".txt", ".json")
+
+
+def grouped_files(directory):
+    """The reference's ``make_grouped_dataset`` (data/image_folder.py:37-49): a sorted walk, one sorted list of image files
+    per folder that holds any."""
+    import os
+    if not os.path.isdir(directory):
+        raise ValueError(f"{directory} does not exist or is not a directory")
+    groups = []
+    for root, _, names in sorted(os.walk(directory)):
+        paths = [os.path.join(root, f) for f in sorted(names) if f.endswith(_IMAGE_NAMES)]
+        if paths:
+            groups.append(paths)
+    return groups
+
+
+class FolderSequences:
+    """The ``sequences`` object ``training.fit`` takes, over a folder of JPEG frames, decoded and scaled on the device.
+
+    ``root`` is walked as the reference's loader does (``IR2RGBBaseDataset``, data/dataset/vid2vid.py:59-69): every folder
+    whose path holds ``lwir`` is an infrared sequence, every one that holds ``visible`` the RGB sequence paired with it by
+    sorted order; the two lists and every pair must be equally long.  Annotations are not read (the IR -> RGB path never
+    uses them).  ``sequence(index, n_frames_total)`` draws ``video_params`` and then ``transform.img_params`` from ``rng``
+    (default: the ``random`` module and ``numpy.random``, as the reference), decodes both tracks (``JpegDecoder``) and hands
+    them to ``scaled_sequence`` with one ``FrameScaler`` parameter set for the sequence -> ``[1, T, C, H, W]`` tensors.
+    ``options``: ``video_params``' and ``img_params``' (the reference's names), ``input_nc`` (3: infrared files become
+    three equal channels like ``Image.convert('RGB')``; 1: the grey channel), ``rng`` = (random-like, numpy.random-like)."""
+
+    def __init__(self, device, root, input_nc=3, rng=None, **options):
+        import os
+        self.device, self.root, self.input_nc, self.rng, self.options = torch.device(device), root, int(input_nc), rng, options
+        groups = sorted(grouped_files(root))
+        self.ir_paths = sorted(g for g in groups if "lwir" in g[0])
+        self.rgb_paths = sorted(g for g in groups if "visible" in g[0])
+        if not self.ir_paths or len(self.ir_paths) != len(self.rgb_paths):
+            raise ValueError(f"{root}: {len(self.ir_paths)} lwir and {len(self.rgb_paths)} visible sequences")
+        for a, b in zip(self.ir_paths, self.rgb_paths):
+            if len(a) != len(b):
+                raise ValueError(f"{os.path.dirname(a[0])}: {len(a)} frames, {os.path.dirname(b[0])}: {len(b)}")
+            for p in a + b:
+                if not p.endswith(_JPEG_NAMES):
+                    raise ValueError(f"{p}: not a JPEG file (JPEG frames only)")
+        self.seq_len_max = max(len(p) for p in self.ir_paths)
+        self._decoders = {}
+        self.last = None                # (index, n_frames_total, start_idx, t_step, scaler) of the last sequence()
+
+    def __len__(self):
+        return len(self.ir_paths)
+
+    def _decode(self, paths, channels):
+        from .jpeg_decode import JpegDecoder, parse
+        with open(paths[0], "rb") as f:
+            info = parse(f.read())
+        key = (info.H, info.W, info.mode, channels)
+        if key not in self._decoders:
+            self._decoders[key] = JpegDecoder(self.device, info.H, info.W, info.mode, channels=channels)
+        try:
+            return self._decoders[key].decode(paths)
+        except NotImplementedError as e:
+            raise ValueError(str(e)) from None
+
+    def sequence(self, index, n_frames_total):
+        index %= len(self)
+        ir_paths, rgb_paths = self.ir_paths[index], self.rgb_paths[index]
+        opt = dict(self.options, n_frames_total=n_frames_total)
+        n, start, step = video_params(len(ir_paths), index, rng=None if self.rng is None else self.rng[1], **opt)
+        picked = [start + i * step for i in range(n)]
+        ir = self._decode([ir_paths[i] for i in picked], self.input_nc)
+        rgb = self._decode([rgb_paths[i] for i in picked], 3)
+        scale_opt = {k: v for k, v in self.options.items() if k in ("dataset_scale", "dataset_crop", "load_size", "fine_size",
+                                                                     "dataset_mode", "is_train", "flip")}
+        a, b, scaler = scaled_sequence(ir, rgb, rng=self.rng, **scale_opt)
+        self.last = (index, n, start, step, scaler)
+        h, w = scaler.out_hw
+        return a.view(1, n, self.input_nc, h, w), b.view(1, n, 3, h, w)
