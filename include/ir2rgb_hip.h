@@ -631,6 +631,31 @@ int ir2rgb_warp_error_u8(const uint8_t *prev, const uint8_t *cur, const float *f
                          void *workspace, long workspace_bytes, int N, int H, int W, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Colour scores (colour_metrics.hip): RGB PSNR and the CIELAB error of pred against orig, per frame, in fp64 on
+ * the device -- what the gray-only scores above cannot see.  orig, pred: uint8 [N][H][W][3]; lin: 256 doubles on
+ * the device, the sRGB decoding of a byte (c = v/255; c/12.92 if c <= 0.04045 else ((c + 0.055)/1.055)^2.4),
+ * formed once by the caller.  N in [1, 65535], H, W >= 1, 3*H*W < 2^31.  For every pixel of either frame
+ *   r, g, b = lin[R], lin[G], lin[B]
+ *   tX = (0.412453 r + 0.357580 g + 0.180423 b) / 0.95047,  tY = (0.212671 r + 0.715160 g + 0.072169 b) / 1.0,
+ *   tZ = (0.019334 r + 0.119193 g + 0.950227 b) / 1.08883                 (scikit-image's rgb2lab: D65, 2 degrees)
+ *   f(t) = cbrt(t) if t > 0.008856 else 7.787 t + 16/116
+ *   L = 116 f(tY) - 16,  a = 500 (f(tX) - f(tY)),  b = 200 (f(tY) - f(tZ))
+ * and with dL, da, db the differences orig - pred:  dE = sqrt(dL^2 + da^2 + db^2) (CIE76),  dC = sqrt(da^2 + db^2),
+ *   out[n] = {mse = sum (orig - pred)^2 / (3 H W) in byte units,  psnr = 10 log10(65025 / mse),
+ *             delta_e = sum dE / (H W),  delta_l = sum |dL| / (H W),  delta_c = sum dC / (H W)}.
+ * No special cases: identical frames give {0, +inf, 0, 0, 0}.  mse is exact (a sum of integers below 2^53); the
+ * Lab sums have a fixed order: results are bit-reproducible and frames never mix.
+ * The workspace is the caller's: ir2rgb_colour_metrics_workspace_bytes(N, H, W) bytes (negative for invalid
+ * sizes), fully written before it is read.  Two launches.  W % 4 == 0 with orig and pred on 4-byte boundaries
+ * takes dword loads, everything else the scalar form of the same code.
+ * IR2RGB_EINVAL: NULL orig / pred / lin / out / workspace, sizes out of range, workspace too small;
+ * IR2RGB_EALIGN: out, lin or workspace off an 8-byte boundary.  Both before any launch.
+ * ------------------------------------------------------------------------------------------ */
+long ir2rgb_colour_metrics_workspace_bytes(int N, int H, int W);
+int ir2rgb_colour_metrics_u8(const uint8_t *orig, const uint8_t *pred, const double *lin, double *out, void *workspace,
+                             long workspace_bytes, int N, int H, int W, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Frame scaling (frame_scale.hip): the loader's Image.resize(..., BICUBIC), crop and flip (reference
  * data/transform.py:64-113) on uint8 frames, equal to Pillow's 8-bit resampler byte for byte.
  *   src [N][Hs][Ws][C] uint8, C in {1, 3}  --scale-->  [new_h][new_w]  --crop-->  rows [crop_y, crop_y + Hc),

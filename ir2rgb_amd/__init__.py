@@ -7,7 +7,7 @@ first use and its absence is an error (there is no CPU fallback).
 __version__ = "0.1.0"
 
 __all__ = ["VideoTranslator", "VideoScore", "video_metrics", "ssim_reference", "warp_error", "warp_error_reference",
-           "warp_bound", "FrameScaler", "img_params", "resample_coeffs", "resize_reference", "TrainingSchedule", "LossLog", "fit", "Snapshots", "to_u8_reference", "flow_to_rgb_reference",
+           "warp_bound", "colour_metrics", "colour_reference", "colour_bound", "srgb_table", "FrameScaler", "img_params", "resample_coeffs", "resize_reference", "TrainingSchedule", "LossLog", "fit", "Snapshots", "to_u8_reference", "flow_to_rgb_reference",
            "JpegEncoder", "jpeg_reference", "JpegDecoder", "decode_reference", "FolderSequences"]
 
 
@@ -16,7 +16,8 @@ def __getattr__(name):
     if name == "VideoTranslator":
         from .inference import VideoTranslator
         return VideoTranslator
-    if name in ("VideoScore", "video_metrics", "ssim_reference", "warp_error", "warp_error_reference", "warp_bound"):
+    if name in ("VideoScore", "video_metrics", "ssim_reference", "warp_error", "warp_error_reference", "warp_bound",
+                "colour_metrics", "colour_reference", "colour_bound", "srgb_table"):
         from . import metrics
         return getattr(metrics, name)
     if name in ("FrameScaler", "img_params", "resample_coeffs", "resize_reference"):

@@ -154,6 +154,8 @@ PROTOTYPES = {
     "ir2rgb_video_metrics_u8": (c_int, [P] * 5 + [c_long] + [c_int] * 3 + [P]),
     "ir2rgb_warp_error_workspace_bytes": (c_long, [c_int] * 3),
     "ir2rgb_warp_error_u8": (c_int, [P] * 6 + [c_long] + [c_int] * 3 + [P]),
+    "ir2rgb_colour_metrics_workspace_bytes": (c_long, [c_int] * 3),
+    "ir2rgb_colour_metrics_u8": (c_int, [P] * 5 + [c_long] + [c_int] * 3 + [P]),
     "ir2rgb_frame_scale_workspace_bytes": (c_long, [c_int] * 10),
     "ir2rgb_frame_scale_u8": (c_int, [P, P, P, c_long, P, P, c_int, P, P, c_int] + [c_int] * 12 + [P]),
     "ir2rgb_visuals_workspace_bytes": (c_long, [c_int] * 3),

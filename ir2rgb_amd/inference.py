@@ -383,7 +383,7 @@ class VideoTranslator:
             write_oldest()
         return paths
 
-    def evaluate(self, frames, targets, real_rgb=None, data_range="reference", temporal=None):
+    def evaluate(self, frames, targets, real_rgb=None, data_range="reference", temporal=None, colour=False):
         """``translate(frames, real_rgb)`` scored against a ground-truth RGB track (reference scripts/ssim_metric.py):
         output ``k`` is compared with ``targets[tG-1+k]`` -- ``targets`` is indexed like ``frames``, uint8 [H,W,3] each
         (camera-size ones are scaled like the frames), moved to the device if needed.
@@ -397,13 +397,17 @@ class VideoTranslator:
         gives ``warp_error(P_k-1, P_k, flow, conf)`` for the outputs and ``warp_error(T_k-1, T_k, flow, conf)`` for the
         targets as the baseline (``VideoScore.add_pair``; ``result()`` then has ``warp_l1``, ``warp_mse``, ``truth_warp_l1``,
         ``truth_warp_mse``, ``coverage``, ``pairs`` and ``per_pair``).  All of it is enqueued on the current stream after
-        the step; None (default) scores frame by frame only."""
+        the step; None (default) scores frame by frame only.
+
+        ``colour``: with True every output is also scored in colour against its target (``colour_metrics``: RGB PSNR and
+        the CIELAB error, which the gray-only scores cannot see; ``result()`` then has ``mse``, ``psnr``, ``delta_e``,
+        ``delta_l``, ``delta_c`` and ``per_frame_colour``).  False (default) launches and allocates nothing more."""
         from .metrics import VideoScore
         if not hasattr(targets, "__getitem__"):
             targets = list(targets)
         if temporal is not None and not callable(temporal):
             raise TypeError(f"evaluate: temporal is a callable (cur, prev) -> (flow, conf), got {type(temporal)}")
-        score = VideoScore(data_range)
+        score = VideoScore(data_range, colour)
         prev = None                                                     # (output, target) of the step before
         for k, out in enumerate(self.translate(frames, real_rgb)):
             i = self.seq.output_frame(k)

@@ -60,15 +60,52 @@ There are no special cases: SC = 0 gives 0/0 = NaN as IEEE does; a NaN flow vect
 pair (the clamp keeps a NaN, so ax / ay carry it) and leaves every other pair of the batch bit-unchanged; an infinite flow
 vector lands on the border like any large one.  No address leaves the frame: indices are clamped as integers, a NaN
 coordinate maps to index 0.
+
+Colour: RGB PSNR and the CIELAB error of a frame against its target (csrc/colour_metrics.hip).  Every score above is taken
+after ``rgb2gray`` or between consecutive frames: a translator that outputs the right luminance and no colour at all scores
+an SSIM of 0.9998 against the 64x128 colour test image of tests/test_colour_metrics_cpu.py while the two lie a mean CIELAB
+distance of 63.0 apart (about 2.3 is already visible).
+
+* ``colour_metrics(orig_u8, pred_u8)``    -> fp64 device tensor [N,5]: mse, psnr, delta_e, delta_l, delta_c per frame
+* ``colour_reference(orig_u8, pred_u8)``  the same definition in plain torch fp64 on any device
+* ``colour_bound(H, W, psnr)``            how far two fp64 evaluations of the definition may lie apart, [5]
+* ``srgb_table(device)``                  the 256 doubles both of them read
+* ``VideoScore(colour=True)``             collects the rows beside the others
+
+Two uint8 frames ``orig`` and ``pred``, [H,W,3] with H, W >= 1; the constants are scikit-image's ``rgb2lab`` (D65, 2 degree
+observer).  Everything is fp64:
+
+    lin[v], v = 0..255:  c = v/255;  lin = c/12.92 if c <= 0.04045 else ((c + 0.055)/1.055)**2.4
+        formed once on the host in Python floats (``srgb_table``): kernel and reference read the same 256 doubles
+    r, g, b = lin[R], lin[G], lin[B]
+    tX = (0.412453 r + 0.357580 g + 0.180423 b) / 0.95047        products and sums left to right, then the division
+    tY = (0.212671 r + 0.715160 g + 0.072169 b) / 1.0
+    tZ = (0.019334 r + 0.119193 g + 0.950227 b) / 1.08883
+    f(t) = cbrt(t) if t > 0.008856 else 7.787 t + 16.0/116.0
+    L = 116 f(tY) - 16        a = 500 (f(tX) - f(tY))        b = 200 (f(tY) - f(tZ))
+
+    per pixel, with dL, da, db the differences orig - pred:
+        dE = sqrt(dL*dL + da*da + db*db)     (CIE76)
+        dC = sqrt(da*da + db*db)             (the distance in the colour plane: what a gray-only score cannot see)
+    per frame:
+        mse     = (sum over pixels and channels of (orig - pred)**2 in byte units) / (3 H W)
+        psnr    = 10 * log10(65025.0 / mse)
+        delta_e = sum dE / (H W)        delta_l = sum |dL| / (H W)        delta_c = sum dC / (H W)
+
+There are no special cases: identical frames give ``mse = 0``, ``psnr = +inf`` (65025/0) and exact zeros in the three Lab
+columns, and one such frame makes the movie's mean ``psnr`` infinite.  ``mse`` is a sum of integers below 2**53, the same
+double in any order; the three Lab sums have a fixed order on the device (bit-reproducible, frames never mix).
 """
 import math
 
+import numpy
 import torch
 
 from . import _lib
 
 __all__ = ["video_metrics", "ssim_reference", "VideoScore", "ssim_bound", "l2_bound", "RANGE_BOUND",
-           "warp_error", "warp_error_reference", "warp_bound"]
+           "warp_error", "warp_error_reference", "warp_bound",
+           "colour_metrics", "colour_reference", "colour_bound", "srgb_table"]
 
 # ---------------------------------------------------------------------------------------------
 # The bound between two fp64 evaluations of the definition (written down before any kernel ran).
@@ -161,6 +198,47 @@ def warp_bound(H, W, flow, weight=None):
     r = A / SC
     return torch.stack([(dS1 + U * 3 * 255 * A) / (127.5 * n), dS2 / (255 ** 2 * 3 * SC) + r * dSC / SC + 3 * U * r,
                         (dSC + U * A) / (H * W)], 1)
+
+
+# ---------------------------------------------------------------------------------------------
+# The bound between two fp64 evaluations of the colour scores (written down before the kernel first ran).
+#
+#   lin       both evaluations read the same 256 doubles                                      -> 0
+#   t         three products, two sums, one division on values with t <= 1.0001               -> <= 6u relative
+#   f         cube-root branch: the 6u of t arrive divided by 3 (2u), the library's cbrt adds E_cbrt = 2u -- ASSUMED for
+#             either side: the device library documents <= 1 ulp for its fp64 cbrt and so does glibc for the one behind
+#             numpy.cbrt, f <= 1.0001; nobody has measured either.  Should a GPU test disagree, that is a finding: E_cbrt is
+#             then widened to a documented figure, never fitted to the observed error -- plus one u of slack
+#                                                                                             -> <= 5u absolute
+#             linear branch: 7.787 * 6u * 0.008856, one product, one sum                      -> <= 2u absolute
+#             No colour sits near the branch: over all 2**24 colours and the three rows the smallest |t - 0.008856| is
+#             2.24e-9, nine orders above 6u (tests/test_colour_metrics_cpu.py repeats the sweep)
+#   Lab       L = 116 f - 16: 116 * 5u + its own two roundings on values <= 116              -> |dL| <= 800u
+#             a = 500 (fX - fY): 500 * 10u + the roundings of a difference <= 1 and a product <= 500   -> <= 2**13 u
+#             b = 200 (fY - fZ)                                                               -> <= 2**12 u
+#             per frame; twice that for the difference of two frames' values
+#   pixel     dE, |dL| and dC are 1-Lipschitz in (dL, da, db): the vector moves by <= 2 (800 + 2**13 + 2**12) u < 2**15 u
+#             less their own roundings (three squares, two sums, one correctly rounded sqrt on values <= 300: <= 4 * 300u),
+#             inside the same figure                                                          -> E_px = 2**15 u
+#   mean      H W terms <= 300 summed in any order and divided once                           -> (H W + 1) * 300u
+#   columns 2-4: 2**15 u + (H W + 1) * 300u       1.7e-8 at 512x1024, 2.1e-11 at 16x32
+#   mse       exact                                                                           -> 0
+#   psnr      one division (u relative in the argument = u / ln 10 absolute in log10), log10 at <= 2 ulp of a value <= 15,
+#             one product by 10                                                               -> 8u + 4u |psnr|
+#             an infinite psnr (identical frames) is compared as a pattern, not by distance
+# A skipped gamma, a white point of (1,1,1), channels read as BGR, a dropped linear branch, |d chroma| for dC or means over
+# 3 H W move a Lab column by more than 1e-3 (tests/test_colour_metrics_cpu.py).
+# ---------------------------------------------------------------------------------------------
+E_CBRT = 2 * U
+
+
+def colour_bound(H, W, psnr=None):
+    """Largest difference between two fp64 evaluations of ``colour_metrics`` on an H x W frame: fp64 [5] for the columns
+    mse, psnr, delta_e, delta_l, delta_c.  ``psnr``: the frame's value (a float or a one-element tensor); None takes the
+    largest finite one a frame of this size can have, ``10 log10(65025 * 3 H W)`` (one byte off by one)."""
+    p = 10.0 * math.log10(65025.0 * 3 * H * W) if psnr is None else abs(float(psnr))
+    lab = 2.0 ** 15 * U + (H * W + 1) * 300 * U
+    return torch.tensor([0.0, 8 * U + 4 * U * p, lab, lab, lab], dtype=torch.float64)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -299,6 +377,60 @@ def warp_error_reference(prev_u8, cur_u8, flow, weight=None):
     return torch.stack(rows)
 
 
+_LIN = {}
+
+
+def srgb_table(device=None):
+    """fp64 [256]: the sRGB decoding of a byte, ``c = v/255; c/12.92 if c <= 0.04045 else ((c + 0.055)/1.055)**2.4``, in
+    Python floats (``math.pow``) on the host, as a tensor on ``device`` (default: the CPU).  One tensor per device, made at
+    the first call and never modified: ``colour_metrics`` and ``colour_reference`` read the same 256 doubles."""
+    device = torch.device("cpu" if device is None else device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    t = _LIN.get(device)
+    if t is None:
+        c = [v / 255 for v in range(256)]
+        lin = [x / 12.92 if x <= 0.04045 else math.pow((x + 0.055) / 1.055, 2.4) for x in c]
+        t = _LIN[device] = torch.tensor(lin, dtype=torch.float64).to(device)
+    return t
+
+
+def _cbrt(t):
+    return torch.from_numpy(numpy.cbrt(t.cpu().numpy())).to(t.device)
+
+
+def _lab(img_u8):
+    """uint8 [...,3] -> (L, a, b), fp64 [...] each, in the operation order of csrc/colour_metrics.hip."""
+    v = srgb_table(img_u8.device)[img_u8.long()]
+    r, g, b = v[..., 0], v[..., 1], v[..., 2]
+    tx = (0.412453 * r + 0.357580 * g + 0.180423 * b) / 0.95047
+    ty = (0.212671 * r + 0.715160 * g + 0.072169 * b) / 1.0
+    tz = (0.019334 * r + 0.119193 * g + 0.950227 * b) / 1.08883
+    fx, fy, fz = (torch.where(t > 0.008856, _cbrt(t), 7.787 * t + 16.0 / 116.0) for t in (tx, ty, tz))
+    return 116.0 * fy - 16.0, 500.0 * (fx - fy), 200.0 * (fy - fz)
+
+
+def colour_reference(orig_u8, pred_u8):
+    """``colour_metrics`` in plain torch fp64 on whatever device the frames are on: uint8 [H,W,3] or [N,H,W,3] -> fp64
+    [N,5] (mse, psnr, delta_e, delta_l, delta_c).  Written from the formulas of this module's docstring in the operation
+    order of csrc/colour_metrics.hip; the two differ in the order of the three Lab sums and in the cube root
+    (``colour_bound``).  The cube root is ``numpy.cbrt`` on a CPU copy of ``t`` -- the C library's ``cbrt``, documented
+    within 1 ulp -- and not ``torch.pow(t, 1/3)``, which is a ``pow`` with a rounded exponent and carries no such claim."""
+    orig_u8, pred_u8, _ = _frames(orig_u8, pred_u8, "colour_reference", "expected dtype {}", "a frame", 1)
+    N, H, W = orig_u8.shape[:3]
+    rows = []
+    for n in range(N):
+        d = orig_u8[n].to(torch.float64) - pred_u8[n].to(torch.float64)
+        mse = (d * d).sum() / (3 * H * W)
+        (Lo, ao, bo), (Lp, ap, bp) = _lab(orig_u8[n]), _lab(pred_u8[n])
+        dL, da, db = Lo - Lp, ao - ap, bo - bp
+        dE, dC = (dL * dL + da * da + db * db).sqrt(), (da * da + db * db).sqrt()
+        peak = mse.new_tensor(65025.0)          # (a number / a tensor is reciprocal() * number in torch: two roundings)
+        rows.append(torch.stack([mse, 10.0 * torch.log10(peak / mse), dE.sum() / (H * W), dL.abs().sum() / (H * W),
+                                 dC.sum() / (H * W)]))
+    return torch.stack(rows)
+
+
 # ---------------------------------------------------------------------------------------------
 # the kernels
 # ---------------------------------------------------------------------------------------------
@@ -366,21 +498,43 @@ def warp_error(prev_u8, cur_u8, flow, weight=None):
     return out
 
 
+def colour_metrics(orig_u8, pred_u8):
+    """Colour scores of ``pred_u8`` against the ground truth ``orig_u8``: uint8 [H,W,3] or [N,H,W,3] device tensors -> fp64
+    device tensor [N,5] with the columns mse, psnr, delta_e, delta_l, delta_c (``ir2rgb_colour_metrics_u8``; the definition
+    is in this module's docstring).  Enqueued on the current stream; nothing synchronises the host (the device's
+    ``srgb_table`` is copied once, at the first call).
+
+    CPU tensors, other dtypes and non-contiguous tensors raise."""
+    dev = _lib.require_device(orig_u8, pred_u8, dtype=torch.uint8)
+    orig_u8, pred_u8, _ = _frames(orig_u8, pred_u8, "colour_metrics", "expected dtype {}", "a frame", 1)
+    N, H, W = orig_u8.shape[:3]
+    out = torch.empty((N, 5), dtype=torch.float64, device=dev)
+    ws = _workspace("colour_metrics", "N <= 65535, H, W >= 1, 3*H*W < 2**31", dev, _lib.current_stream(out), N, H, W)
+    _lib.launch("ir2rgb_colour_metrics_u8", out, orig_u8, pred_u8, srgb_table(dev), out, ws, ws.numel() * 8, N, H, W)
+    return out
+
+
 class VideoScore:
     """The movie scores of scripts/ssim_metric.py: ``add(orig_u8, pred_u8)`` appends the per-frame rows of
     ``video_metrics`` on the device, ``result()`` averages them (``ssim_movie`` / ``mse_movie``) and is the only call that
     synchronises.  ``add_pair`` collects the temporal rows (``warp_error`` of the prediction, and of the ground truth as the
-    baseline: how much of the error is the flow's own); ``result()`` reports them only when a pair was added."""
+    baseline: how much of the error is the flow's own); ``result()`` reports them only when a pair was added.  With
+    ``colour=True`` every ``add`` also appends the rows of ``colour_metrics``; ``result()`` then reports their column means
+    too (one pair of identical frames makes the movie's ``psnr`` infinite).  Without it nothing more is launched."""
 
-    def __init__(self, data_range="reference"):
+    def __init__(self, data_range="reference", colour=False):
         self.data_range = data_range
+        self.colour = bool(colour)
         self._rows = []
         self._pair_rows = []
+        self._colour_rows = []
 
     def add(self, orig_u8, pred_u8):
         """One frame [H,W,3] or several [N,H,W,3]; -> their rows [N,3] (device)."""
         rows = video_metrics(orig_u8, pred_u8, self.data_range)
         self._rows.append(rows)
+        if self.colour:
+            self._colour_rows.append(colour_metrics(orig_u8, pred_u8))
         return rows
 
     @property
@@ -412,6 +566,12 @@ class VideoScore:
             raise ValueError("VideoScore: no pair was added")
         return torch.cat(self._pair_rows)
 
+    def per_frame_colour(self):
+        """fp64 [frames,5] device tensor (mse, psnr, delta_e, delta_l, delta_c), in the order added."""
+        if not self._colour_rows:
+            raise ValueError("VideoScore: no colour row was added (VideoScore(colour=True))")
+        return torch.cat(self._colour_rows)
+
     def result(self):
         per = self.per_frame()
         ssim, l2 = per[:, :2].mean(0).tolist()
@@ -420,4 +580,8 @@ class VideoScore:
             pp = self.per_pair()
             res.update(zip(("warp_l1", "warp_mse", "truth_warp_l1", "truth_warp_mse", "coverage"), pp.mean(0).tolist()))
             res.update(pairs=pp.shape[0], per_pair=pp)
+        if self._colour_rows:
+            pc = self.per_frame_colour()
+            res.update(zip(("mse", "psnr", "delta_e", "delta_l", "delta_c"), pc.mean(0).tolist()))
+            res.update(per_frame_colour=pc)
         return res

@@ -7,8 +7,8 @@ bench.py configuration), 50 frames after warm-up, three ways on the same weights
   (c) graph     VideoTranslator(use_graph=True): one HIP-graph replay per frame
 
 Each figure: device events around the 50 frames and one synchronise; the three ways alternate over ``--rounds`` rounds and
-the median round is reported (frames/s, ms/frame).  The two frame-I/O kernels, the score of one frame
-(ir2rgb_amd.metrics.video_metrics) and the two passes of frame scaling (ir2rgb_amd.transform.FrameScaler, 512x640x3 ->
+the median round is reported (frames/s, ms/frame).  The two frame-I/O kernels, the scores of one frame
+(ir2rgb_amd.metrics.video_metrics, colour_metrics) and the two passes of frame scaling (ir2rgb_amd.transform.FrameScaler, 512x640x3 ->
 832x1024 and -> 416x512) are timed alone beside the bytes they move (computed from the shapes).  Needs the GPU;
 prints one JSON document and writes it to ``--out``.
 
@@ -101,7 +101,9 @@ def kernel_times(dev, H, W, reps=200):
             ("frame_push_u8 (T=3, one level)", lambda: I.frame_push(frame, h0), px + (2 * TG - 1) * 4 * px),
             ("frame_finish_u8 (T=2, uint8 image)", lambda: I.frame_finish(x, hb, img), 4 * px + (2 * (TG - 1) - 1) * 4 * px + px),
             # both uint8 frames are read by the reduce pass and again (from L2 / Infinity Cache) by the window pass
-            ("video_metrics_u8 (one frame, three launches)", lambda: M.video_metrics(truth, frame), 2 * 2 * px)):
+            ("video_metrics_u8 (one frame, three launches)", lambda: M.video_metrics(truth, frame), 2 * 2 * px),
+            # both uint8 frames once (and six fp64 cube roots per pixel, which no byte count shows)
+            ("colour_metrics_u8 (one frame, two launches)", lambda: M.colour_metrics(truth, frame), 2 * px)):
         us = many(f)
         res[name] = {"us_per_launch": round(us, 2), "bytes_moved": int(byts), "GB_per_s": round(byts / us / 1e3, 1)}
     res.update(scale_times(dev, many))
