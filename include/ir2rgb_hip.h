@@ -799,6 +799,31 @@ int ir2rgb_jpeg_decode_u8(const uint8_t *files, const int *file_offsets, const i
                           int *status, void *workspace, long workspace_bytes, int N, int C_out, int H, int W, int mode,
                           int n_segments, int sub_bytes, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Raw thermal input (thermal_agc.hip): a camera's automatic gain control on the device, integers only.  x: uint16
+ * [N][H][W], N consecutive frames of one sequence (2-byte aligned, nothing more) -> out uint8 [N][H][W][channels],
+ * channels 1 or 3 (the byte repeated).  Per frame: the 65536-bin histogram, clipped at plateau in mode 0 (plateau
+ * equalisation) and taken as it is in mode 1 (percentile window with tail_ppm parts per million cut at either end),
+ * is blended in Q16 into the damped histogram S with weight 65536 - a_q (a_q = round(damping 65536) in 0..65535);
+ * the table comes from the running sum of S.  The definition, which the kernels equal bit for bit, is
+ * ir2rgb_amd.thermal.agc_reference; thermal_agc.hip restates it.
+ *   state   int64 [65537] on the device, the caller's, kept from call to call: S, and in word 65536 the
+ *           sequence-start flag -- 0: the next frame starts a sequence (S = g << 16); the call sets it to 1.  A new
+ *           sequence is a memset of that word; the rest of a fresh state may hold anything.
+ *   lut     uint8 [N][65536], levels int32 [N][2] ((v0, v1) or (lo, hi)): written per frame.
+ * The workspace is the caller's, ir2rgb_thermal_agc_workspace_bytes(N, H, W) bytes (negative for invalid sizes): the
+ * per-frame histograms.  IT MUST BE ALL ZERO ON ENTRY and is all zero again when the call's work is done (the table
+ * pass zeroes what it has read), so a caller clears it once, when it allocates it.
+ * N in [1, 65535], H, W >= 1, H W <= 2^26.  Three launches whatever the frames hold, no host synchronisation.
+ * IR2RGB_EINVAL: a NULL pointer, sizes or parameters out of range (plateau < 1, tail_ppm outside [0, 500000)),
+ * workspace too small; IR2RGB_EALIGN: x off a 2-byte, levels off a 4-byte, state, lut or workspace off a 16-byte
+ * boundary.  Both before any launch.
+ * ------------------------------------------------------------------------------------------ */
+long ir2rgb_thermal_agc_workspace_bytes(int N, int H, int W);
+int ir2rgb_thermal_agc_u16(const uint16_t *x, uint8_t *out, long long *state, uint8_t *lut, int *levels, void *workspace,
+                           long workspace_bytes, int N, int H, int W, int channels, int mode, int plateau, int a_q,
+                           int tail_ppm, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,7 +8,7 @@ __version__ = "0.1.0"
 
 __all__ = ["VideoTranslator", "VideoScore", "video_metrics", "ssim_reference", "warp_error", "warp_error_reference",
            "warp_bound", "colour_metrics", "colour_reference", "colour_bound", "srgb_table", "FrameScaler", "img_params", "resample_coeffs", "resize_reference", "TrainingSchedule", "LossLog", "fit", "Snapshots", "to_u8_reference", "flow_to_rgb_reference",
-           "JpegEncoder", "jpeg_reference", "JpegDecoder", "decode_reference", "FolderSequences"]
+           "JpegEncoder", "jpeg_reference", "JpegDecoder", "decode_reference", "FolderSequences", "ThermalAGC", "agc_reference"]
 
 
 def __getattr__(name):
@@ -32,6 +32,9 @@ def __getattr__(name):
     if name in ("JpegDecoder", "decode_reference"):
         from . import jpeg_decode
         return getattr(jpeg_decode, name)
+    if name in ("ThermalAGC", "agc_reference"):
+        from . import thermal
+        return getattr(thermal, name)
     if name == "FolderSequences":
         from .frames import FolderSequences
         return FolderSequences

@@ -165,6 +165,8 @@ PROTOTYPES = {
     "ir2rgb_jpeg_encode_u8": (c_int, [P, P, P, P, c_long, P, c_int, P] + [c_int] * 8 + [c_long, P]),
     "ir2rgb_jpeg_decode_workspace_bytes": (c_long, [c_int] * 5),
     "ir2rgb_jpeg_decode_u8": (c_int, [P] * 7 + [c_long] + [c_int] * 7 + [P]),
+    "ir2rgb_thermal_agc_workspace_bytes": (c_long, [c_int] * 3),
+    "ir2rgb_thermal_agc_u16": (c_int, [P] * 6 + [c_long] + [c_int] * 8 + [P]),
 }
 
 _lib = None

@@ -21,7 +21,11 @@ batch statistics.  What this module adds is what a frame loop needs around that 
   initialisation differ there); ``reset()`` keeps the graph;
 * camera-size frames: with ``source_size`` (or a ``FrameScaler``) uint8 frames of the camera's size are scaled, cropped and
   flipped on the device exactly as the reference's loader does with Pillow (ir2rgb_amd.transform, csrc/frame_scale.hip)
-  into the staging buffer ``ir2rgb_frame_push_u8`` reads; the two launches are part of the captured step.
+  into the staging buffer ``ir2rgb_frame_push_u8`` reads; the two launches are part of the captured step;
+* raw thermal frames: with ``agc`` (an ``ir2rgb_amd.thermal.ThermalAGC``) 16-bit counts are tone-mapped on the device
+  (csrc/thermal_agc.hip) into the staging buffer the scaler or ``ir2rgb_frame_push_u8`` reads; its three launches are part
+  of the captured step too, and its damped histogram and sequence-start flag live on the device, so a replay needs no
+  host argument.
 
 There is no CPU path: a CPU device raises, as everywhere in this package.
 """
@@ -150,12 +154,19 @@ class VideoTranslator:
     ``FrameScaler`` built elsewhere (the translator works on a ``clone()`` of it: same tables, a workspace of its own).  Either way its result size must be ``(height, width)``.  Frames that already have the
     network's size, and every fp32 frame, are taken as before.
 
+    ``agc``: an ``ir2rgb_amd.thermal.ThermalAGC`` for raw thermal input (the translator works on a ``clone()`` of it: same
+    options, state and workspace of its own).  ``push``, ``translate``, ``evaluate`` and ``save`` then also take uint16 or
+    int16 (reinterpreted as unsigned) ``[Hs,Ws]`` frames of the camera's counts, which are tone-mapped to 8 bits on the
+    device before anything else happens to them.  The AGC's size is the scaler's ``src_hw`` when there is a scaler, else
+    ``(height, width)``; its ``channels`` is ``input_nc``.  ``reset()`` also starts the AGC's sequence anew.  Without
+    ``agc`` nothing is allocated or launched for it and a 16-bit frame is the ``TypeError`` it always was.
+
     Nothing requires grad and no parameter or packed weight is written.  Returned tensors are the caller's own (copies of
     the static buffers the graph works on)."""
 
     def __init__(self, device, height, width, netG=None, checkpoint_dir=None, which_epoch="latest", first_frame="zeros",
                  norm_stats="batch", use_graph=True, source_size=None, scaler=None, scale_opt=None, scale_rng=None,
-                 weights="raw", **opt):
+                 weights="raw", agc=None, **opt):
         device = torch.device(device)
         if weights not in ("raw", "ema"):
             raise ValueError(f"weights: 'raw' (the last step's parameters) or 'ema' (their moving average), got {weights!r}")
@@ -209,6 +220,9 @@ class VideoTranslator:
             self._set_scaler(scaler, source_size, scale_opt, scale_rng)
         elif scale_opt is not None:
             raise ValueError("VideoTranslator: scale_opt needs source_size")
+        self.agc = None
+        if agc is not None:
+            self._set_agc(agc)
         self._alloc()
 
     def _set_scaler(self, scaler, source_size, scale_opt, scale_rng):
@@ -231,6 +245,17 @@ class VideoTranslator:
         # scaler's workspace, and nothing the caller does with the scaler handed in may touch that buffer
         self.scaler = scaler.clone()
         self.scaler_rgb = self.scaler if C == 3 else scaler.with_channels(3)
+
+    def _set_agc(self, agc):
+        from .thermal import ThermalAGC
+        if not isinstance(agc, ThermalAGC):
+            raise TypeError(f"VideoTranslator: agc is an ir2rgb_amd.thermal.ThermalAGC, got {type(agc)}")
+        hw = self.scaler.src_hw if self.scaler is not None else (self.H, self.W)
+        if agc.hw != hw or agc.channels != self.opt["input_nc"] or agc.device != self.device:
+            raise ValueError(f"VideoTranslator: the AGC gives {agc.channels}-channel frames of {agc.hw} on {agc.device}, "
+                             f"{self.opt['input_nc']}-channel frames of {hw} on {self.device} needed")
+        # a private copy, as with the scaler: the captured step holds the addresses of its state and workspace
+        self.agc = agc.clone()
 
     @staticmethod
     def _build_generators(o):
@@ -259,6 +284,8 @@ class VideoTranslator:
                       "f32": torch.zeros((C, self.H, self.W), dtype=torch.float32, device=dev)}
         if self.scaler is not None:     # a camera-size frame waits here; the step scales it into stage["u8"]
             self.stage["cam"] = torch.zeros((*self.scaler.src_hw, C), dtype=torch.uint8, device=dev)
+        if self.agc is not None:        # raw counts wait here; the step tone-maps them into stage["cam"] or stage["u8"]
+            self.stage["raw"] = torch.zeros(self.agc.hw, dtype=torch.int16, device=dev)
         self.image = torch.zeros((self.H, self.W, 3), dtype=torch.uint8, device=dev)
         self._graphs = {}               # staging kind -> CUDAGraph of one non-first step
         self._eager_steps = 0
@@ -269,6 +296,8 @@ class VideoTranslator:
         self.seq.reset()
         for h in self.hist_B:           # generate_first_frame, no_first_img: a zero history (generator.py:219-220)
             h.zero_()
+        if self.agc is not None:
+            self.agc.reset()
 
     def set_history(self, frames_per_scale):
         """Replace the generated-frame history: ``frames_per_scale[i]`` fp32 [tG-1,3,h_i,w_i], index 0 = full resolution,
@@ -308,6 +337,9 @@ class VideoTranslator:
                 want = tuple(frame.shape)                   # camera size: scaled on the device before it is used
         elif frame.dtype == torch.float32:
             want = (channels, self.H, self.W)
+        elif self.agc is not None and what == "push" and frame.dtype in (torch.uint16, torch.int16):
+            frame = frame.view(torch.int16)                 # the camera's counts: the same bits, a dtype torch can copy
+            want = self.agc.hw
         else:
             raise TypeError(f"{what}: uint8 [H,W,C] or normalised fp32 [C,H,W] expected, got {frame.dtype}")
         if tuple(frame.shape) != want:
@@ -317,6 +349,10 @@ class VideoTranslator:
     def _camera_size(self, frame):
         return self.scaler is not None and frame.dtype == torch.uint8 and tuple(frame.shape[:2]) == self.scaler.src_hw
 
+    def _tone_map(self, raw):
+        """Raw counts -> the uint8 staging buffer of their size (``stage["cam"]`` with a scaler, else ``stage["u8"]``)."""
+        return self.agc(raw, out=self.stage["cam" if self.scaler is not None else "u8"])
+
     def _rgb_frame(self, frame, what):
         """An RGB frame (first real frames, targets) at the network's size: camera-size uint8 frames are scaled."""
         frame = self._as_frame(frame, 3, what)
@@ -324,8 +360,8 @@ class VideoTranslator:
 
     def push(self, ir_u8, real_rgb_u8=None):
         """One input frame (uint8 [H,W,C], or [Hs,Ws,C] with ``source_size``; a normalised fp32 [C,H,W] tensor is taken
-        too).  Returns the translated frame as a uint8 [H,W,3] device tensor, or None while fewer than tG input frames have
-        been pushed.  With ``first_frame="real"`` the first tG-1 calls of a sequence also take that frame's real RGB image."""
+        too; with ``agc`` also the camera's 16-bit counts, uint16 or int16 [Hs,Ws]).  Returns the translated frame as a
+        uint8 [H,W,3] device tensor, or None while fewer than tG input frames have been pushed.  With ``first_frame="real"`` the first tG-1 calls of a sequence also take that frame's real RGB image."""
         with torch.no_grad():
             frame = self._as_frame(ir_u8, self.opt["input_nc"], "push")
             warming = self.seq.warming
@@ -333,11 +369,15 @@ class VideoTranslator:
                 if real_rgb_u8 is None:
                     raise ValueError("first_frame='real': the first tG-1 frames of a sequence need real_rgb_u8")
                 self._push_levels(self._rgb_frame(real_rgb_u8, "push(real_rgb_u8)"), self.hist_B)
-            camera = self._camera_size(frame)
+            raw = frame.dtype == torch.int16
             if not self.seq.push():
+                if raw:
+                    frame = self._tone_map(frame)
+                camera = self._camera_size(frame)
                 self._push_levels(self.scaler(frame, out=self.stage["u8"]) if camera else frame, self.hist_A)
                 return None
-            kind = "cam" if camera else ("u8" if frame.dtype == torch.uint8 else "f32")
+            camera = self._camera_size(frame)
+            kind = "raw" if raw else ("cam" if camera else ("u8" if frame.dtype == torch.uint8 else "f32"))
             self.stage[kind].copy_(frame)
             self._step(kind)
             return self.image.clone()
@@ -450,6 +490,9 @@ class VideoTranslator:
     # ------------------------------------------------------------------ one frame
     def _step_body(self, kind, first):
         """push + generate_frame_infer for every scale (generator.py:191-195, :197-215) on the static buffers."""
+        if kind == "raw":
+            self._tone_map(self.stage["raw"])
+            kind = "cam" if self.scaler is not None else "u8"
         if kind == "cam":
             self.scaler(self.stage["cam"], out=self.stage["u8"])
             kind = "u8"

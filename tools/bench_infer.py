@@ -107,9 +107,25 @@ def kernel_times(dev, H, W, reps=200):
         us = many(f)
         res[name] = {"us_per_launch": round(us, 2), "bytes_moved": int(byts), "GB_per_s": round(byts / us / 1e3, 1)}
     res.update(scale_times(dev, many))
+    res.update(agc_times(dev, many))
     res["note"] = ("bytes_moved counts the in-place history shift (slots read and written) beside the frame itself: "
                    f"{px / 1e6:.2f} MB of bytes and {4 * px / 1e6:.2f} MB of fp32 per full-size frame")
     return res
+
+
+def agc_times(dev, many, hs=512, ws=640, C=3):
+    """ThermalAGC (three launches per call) on one raw frame of the camera's size, a narrow-band scene: the histogram and
+    the map pass read the 16-bit frame once each, the table pass reads and zeroes the 256 KB of bins, reads and writes the
+    512 KB of state twice over and writes the 64 KB table; the map pass writes the uint8 frame."""
+    from ir2rgb_amd.thermal import ThermalAGC
+    g = torch.Generator().manual_seed(0)
+    raw = (7000 + 40 * torch.randn(hs, ws, generator=g)).round().clamp(0, 65535).to(torch.int16).to(dev)
+    agc = ThermalAGC(dev, hs, ws, channels=C)
+    out = agc(raw)
+    us = many(lambda: agc(raw, out=out))
+    byts = 2 * 2 * hs * ws + 2 * 4 * 65536 + 3 * 8 * 65536 + 65536 + hs * ws * C
+    return {f"thermal_agc_u16 {hs}x{ws} -> uint8 x{C} (one frame, three launches)": {
+        "us_per_call": round(us, 2), "bytes_moved": int(byts), "GB_per_s": round(byts / us / 1e3, 1)}}
 
 
 def scale_times(dev, many, hs=512, ws=640, C=3):
