@@ -24,34 +24,24 @@
 // positions that no other code accounts for.  An interval of B blocks is therefore at most ceil(B * blk_bits / 8) bytes
 // with its padding and twice that after stuffing: the size of its scratch region and, plus two marker bytes per interval
 // and the header, ir2rgb_jpeg_capacity_bytes.  Sample coordinates are clamped to the frame, table indices to the tables.
-#include "common.h"
-#include "u8.h"         // the bytes of a dword
+#include "jpeg_common.h"    // shared with jpeg_decode.hip: modes, ZZ, DCT multipliers, descale, scan_inclusive, align16, jpeg_grid
+#include "u8.h"             // the bytes of a dword
 
 namespace {
 
-constexpr int MODE_444 = 0, MODE_420 = 1, MODE_L = 2;
-constexpr int TAB_DC = 128, TAB_AC = 160, TAB_WORDS = 672;          // quantisation [2][64], DC [2][16], AC [2][256]
+constexpr int TAB_DC = 128, TAB_AC = 160, TAB_WORDS = IR2RGB_JPEG_TABLE_WORDS;      // quantisation [2][64], DC [2][16], AC [2][256]
 constexpr int ENT_THREADS = 128;                                    // blocks per chunk of the entropy kernel
 constexpr int BLK_WORDS = 53;                                       // LDS words per block: 1696 bits >= 27 + 63 * 26
 constexpr int BUF_WORDS = ENT_THREADS * BLK_WORDS + 2;
 constexpr int PACK_THREADS = 256;
 
-struct Geom {
-    int H, W, C, mode;
-    int bpm;                    // blocks per MCU
-    int mcus_per_row, mcu_rows;
+struct Geom : JpegGrid {
     int wib, hib;               // real luminance blocks per row / column
     int rows_per_int, n_int;    // MCU rows per restart interval, intervals per frame
-    int nblk;                   // blocks per frame
     int max_dc, max_ac;
     int header_bytes;
     long int_cap;               // scratch bytes per interval
 };
-
-// natural index of zigzag position k
-__device__ constexpr unsigned char ZZ[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                                             41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                                             30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 
 // ---- samples ----------------------------------------------------------------------------------------------------------
 // jccolor with 16 fraction bits, FIX(x) = int(x * 65536 + 0.5)
@@ -79,8 +69,6 @@ template <int MODE> __device__ __forceinline__ int sample(const uint8_t *f, cons
 }
 
 // ---- jfdctint -----------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int descale(int x, int n) { return (x + (1 << (n - 1))) >> n; }
-
 // one pass over 8 values d[0], d[S], ... d[7 S]; FIRST: rows (results scaled by 4), else columns
 template <int S, bool FIRST> __device__ __forceinline__ void fdct8(int *d) {
     constexpr int N = FIRST ? 13 - 2 : 13 + 2;
@@ -89,14 +77,14 @@ template <int S, bool FIRST> __device__ __forceinline__ void fdct8(int *d) {
     const int t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
     d[0] = FIRST ? (t10 + t11) << 2 : descale(t10 + t11, 2);
     d[4 * S] = FIRST ? (t10 - t11) << 2 : descale(t10 - t11, 2);
-    int z1 = (t12 + t13) * 4433;
-    d[2 * S] = descale(z1 + t13 * 6270, N);
-    d[6 * S] = descale(z1 - t12 * 15137, N);
+    int z1 = (t12 + t13) * F0_541;
+    d[2 * S] = descale(z1 + t13 * F0_765, N);
+    d[6 * S] = descale(z1 - t12 * F1_847, N);
     z1 = t4 + t7;
     int z2 = t5 + t6, z3 = t4 + t6, z4 = t5 + t7;
-    const int z5 = (z3 + z4) * 9633;
-    t4 *= 2446, t5 *= 16819, t6 *= 25172, t7 *= 12299;
-    z1 *= -7373, z2 *= -20995, z3 = z3 * -16069 + z5, z4 = z4 * -3196 + z5;
+    const int z5 = (z3 + z4) * F1_175;
+    t4 *= F0_298, t5 *= F2_053, t6 *= F3_072, t7 *= F1_501;
+    z1 *= -F0_899, z2 *= -F2_562, z3 = z3 * -F1_961 + z5, z4 = z4 * -F0_390 + z5;
     d[7 * S] = descale(t4 + z1 + z3, N);
     d[5 * S] = descale(t5 + z2 + z4, N);
     d[3 * S] = descale(t6 + z2 + z3, N);
@@ -208,22 +196,6 @@ __device__ int encode_block(const int16_t *__restrict__ blk, int pred, const uns
     return pos;
 }
 
-// inclusive sum over the workgroup's ENT_THREADS values in a fixed order; *total: the sum of all
-__device__ __forceinline__ int scan_inclusive(int v, int *sh, int *total) {
-    const int t = threadIdx.x;
-    __syncthreads();
-    sh[t] = v;
-    __syncthreads();
-    for (int d = 1; d < ENT_THREADS; d <<= 1) {
-        const int x = t >= d ? sh[t - d] : 0;
-        __syncthreads();
-        sh[t] += x;
-        __syncthreads();
-    }
-    *total = sh[ENT_THREADS - 1];
-    return sh[t];
-}
-
 __global__ void __launch_bounds__(ENT_THREADS)
 jpeg_entropy_kernel(const int16_t *__restrict__ coefs, const unsigned *__restrict__ tables, uint8_t *__restrict__ scratch,
                     int *__restrict__ int_len, Geom g) {
@@ -257,7 +229,7 @@ jpeg_entropy_kernel(const int16_t *__restrict__ coefs, const unsigned *__restric
         const int16_t *blk = cf + (long)j * 64;
         const int len = live ? encode_block<false>(blk, pred, dc, ac, g.max_dc, g.max_ac, nullptr, 0) : 0;
         int sum;
-        const int end = scan_inclusive(len, sh, &sum);
+        const int end = scan_inclusive<ENT_THREADS>(len, sh, &sum);
         const int total = carry_bits + sum;
         const int words = (total + 31) / 32 + 1;
         for (int w = t; w < words; w += ENT_THREADS) buf[w] = w == 0 ? carry_val << 24 : 0u;
@@ -273,7 +245,7 @@ jpeg_entropy_kernel(const int16_t *__restrict__ coefs, const unsigned *__restric
         int ff = 0;
         for (int b = lo; b < hi; ++b) ff += stream_byte(buf, b) == 0xffu;
         int all_ff;
-        const int ff_end = scan_inclusive(ff, sh, &all_ff);
+        const int ff_end = scan_inclusive<ENT_THREADS>(ff, sh, &all_ff);
         uint8_t *o = dst + out_pos + lo + (ff_end - ff);
         for (int b = lo; b < hi; ++b) {
             const unsigned v = stream_byte(buf, b);
@@ -314,24 +286,14 @@ jpeg_pack_kernel(const uint8_t *__restrict__ scratch, const int *__restrict__ in
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------
-long align16(long v) { return (v + 15) & ~15L; }
-
-// IR2RGB_OK and the geometry, or IR2RGB_EINVAL
+// IR2RGB_OK and the geometry, or IR2RGB_EINVAL.  4:2:2 is read (jpeg_decode.hip), not written.
 int geometry(int N, int C, int H, int W, int mode, int restart_rows, int max_dc, int max_ac, int header_bytes, Geom *g) {
-    if (N < 1 || N > 65535 || H < 1 || W < 1 || H > 65535 || W > 65535 || restart_rows < 1) return IR2RGB_EINVAL;
-    if (mode < MODE_444 || mode > MODE_L || (C != 1 && C != 3) || (mode != MODE_L && C != 3)) return IR2RGB_EINVAL;
+    if (mode == MODE_422 || restart_rows < 1 || jpeg_grid(N, C, H, W, mode, g) != IR2RGB_OK) return IR2RGB_EINVAL;
     if (max_dc < 1 || max_dc > 16 || max_ac < 1 || max_ac > 16 || header_bytes < 0 || header_bytes > 65535) return IR2RGB_EINVAL;
-    const int mcu = mode == MODE_420 ? 16 : 8;
-    g->H = H, g->W = W, g->C = C, g->mode = mode;
-    g->bpm = mode == MODE_420 ? 6 : (mode == MODE_444 ? 3 : 1);
-    g->mcus_per_row = (W + mcu - 1) / mcu, g->mcu_rows = (H + mcu - 1) / mcu;
     g->wib = (W + 7) / 8, g->hib = (H + 7) / 8;
     if ((long)restart_rows * g->mcus_per_row > 65535) return IR2RGB_EINVAL;        // the DRI field
     g->rows_per_int = restart_rows < g->mcu_rows ? restart_rows : g->mcu_rows;
     g->n_int = (g->mcu_rows + g->rows_per_int - 1) / g->rows_per_int;
-    const long nblk = (long)g->mcu_rows * g->mcus_per_row * g->bpm;
-    if (nblk * N > 0x7fffffffL / 64) return IR2RGB_EINVAL;
-    g->nblk = (int)nblk;
     g->max_dc = max_dc, g->max_ac = max_ac, g->header_bytes = header_bytes;
     const long blk_bits = (max_dc + 11) + 63L * (max_ac + 10);
     const long int_blocks = (long)g->rows_per_int * g->mcus_per_row * g->bpm;

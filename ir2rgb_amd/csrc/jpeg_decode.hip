@@ -27,31 +27,21 @@
 // 1-bits), every table index is clamped to its table, k never passes 64 (a block ends there), 16 bits that are no code are
 // consumed as symbol 0 (so every symbol consumes at least one bit and the loops end), a coefficient is stored only into a
 // block of the segment, and segment records are clamped to the frame's MCUs.  Only the write pass reports errors.
-#include "common.h"
+#include "jpeg_common.h"    // shared with jpeg.hip: modes, ZZ, DCT multipliers, descale, scan_inclusive, align16, jpeg_grid
 
 namespace {
 
-constexpr int MODE_444 = IR2RGB_JPEG_444, MODE_420 = IR2RGB_JPEG_420, MODE_L = IR2RGB_JPEG_L, MODE_422 = IR2RGB_JPEG_422;
 constexpr int TAB_COMP = 192, TAB_HUFF = 200, HUFF_WORDS = 288, TAB_WORDS = IR2RGB_JPEGD_TABLE_WORDS;
 constexpr int ENT_THREADS = IR2RGB_JPEGD_THREADS;
 constexpr int PIX_THREADS = 256;
 
-struct DGeom {
-    int H, W, C, mode, ncomp;
-    int hs, vs;                 // luminance sampling factors
-    int bpm;                    // blocks per MCU
-    int mcus_per_row, mcu_rows, n_mcus;
-    int nblk;                   // blocks per file
+struct DGeom : JpegGrid {
+    int ncomp, n_mcus;
     int pw[3], ph[3];           // component planes (block grids)
     long po[3], plane_bytes;    // their byte offsets inside a file's planes, and the size of all
     int dw, dh;                 // real size of the chroma planes
     int n_seg;                  // segment records per file
 };
-
-// natural index of zigzag position k
-__device__ constexpr unsigned char ZZ[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                                             41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                                             30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 
 // ---- entropy decoding ---------------------------------------------------------------------------------------------------
 // byte i >= 0 of a segment of n bytes; past the end the reader supplies 1-bits
@@ -153,22 +143,6 @@ __device__ void decode_run(const uint8_t *d, int n, const Tables &T, const DGeom
     }
 }
 
-// inclusive sum over the workgroup's ENT_THREADS values in a fixed order; *total: the sum of all
-__device__ __forceinline__ int scan_inclusive(int v, int *sh, int *total) {
-    const int t = threadIdx.x;
-    __syncthreads();
-    sh[t] = v;
-    __syncthreads();
-    for (int d = 1; d < ENT_THREADS; d <<= 1) {
-        const int x = t >= d ? sh[t - d] : 0;
-        __syncthreads();
-        sh[t] += x;
-        __syncthreads();
-    }
-    *total = sh[ENT_THREADS - 1];
-    return sh[t];
-}
-
 __global__ void __launch_bounds__(ENT_THREADS)
 jpegd_entropy_kernel(const uint8_t *__restrict__ files, const int *__restrict__ file_offsets, const int *__restrict__ segments,
                      const int *__restrict__ tables, int16_t *__restrict__ coefs, int *__restrict__ seg_info, DGeom g,
@@ -230,7 +204,7 @@ jpegd_entropy_kernel(const uint8_t *__restrict__ files, const int *__restrict__ 
     // the first output block of every subsequence
     const int seg_blocks = n_mcus * g.bpm;
     int total;
-    const int before = scan_inclusive(active ? count : 0, sh, &total) - (active ? count : 0);
+    const int before = scan_inclusive<ENT_THREADS>(active ? count : 0, sh, &total) - (active ? count : 0);
     if (t == 0 && total != seg_blocks) status |= IR2RGB_JPEGD_EBLOCKS;
     int16_t *out = coefs + ((long)n * g.nblk + (long)first * g.bpm) * 64;
     uint4 *out4 = reinterpret_cast<uint4 *>(out);
@@ -248,7 +222,7 @@ jpegd_entropy_kernel(const uint8_t *__restrict__ files, const int *__restrict__ 
     for (int m = m0; m < m1; ++m)
         for (int j = 0; j < g.bpm; ++j) sum[j < ny ? 0 : j - ny + 1] += out[((long)m * g.bpm + j) * 64];
     int pred[3];
-    for (int c = 0; c < 3; ++c) pred[c] = scan_inclusive(sum[c], sh, &total) - sum[c];
+    for (int c = 0; c < 3; ++c) pred[c] = scan_inclusive<ENT_THREADS>(sum[c], sh, &total) - sum[c];
     for (int m = m0; m < m1; ++m)
         for (int j = 0; j < g.bpm; ++j) {
             const int c = j < ny ? 0 : j - ny + 1;
@@ -262,21 +236,19 @@ jpegd_entropy_kernel(const uint8_t *__restrict__ files, const int *__restrict__ 
 }
 
 // ---- jidctint -------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int descale(int x, int n) { return (x + (1 << (n - 1))) >> n; }
-
 // one pass over 8 values d[0], d[S], ... d[7 S]
 template <int S, int SHIFT> __device__ __forceinline__ void idct8(int *d) {
     int z2 = d[2 * S], z3 = d[6 * S];
-    int z1 = (z2 + z3) * 4433;
-    int t2 = z1 - z3 * 15137, t3 = z1 + z2 * 6270;
+    int z1 = (z2 + z3) * F0_541;
+    int t2 = z1 - z3 * F1_847, t3 = z1 + z2 * F0_765;
     int t0 = (d[0] + d[4 * S]) << 13, t1 = (d[0] - d[4 * S]) << 13;
     const int t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
     t0 = d[7 * S], t1 = d[5 * S], t2 = d[3 * S], t3 = d[S];
     z1 = t0 + t3, z2 = t1 + t2, z3 = t0 + t2;
     int z4 = t1 + t3;
-    const int z5 = (z3 + z4) * 9633;
-    t0 *= 2446, t1 *= 16819, t2 *= 25172, t3 *= 12299;
-    z1 *= -7373, z2 *= -20995, z3 = z3 * -16069 + z5, z4 = z4 * -3196 + z5;
+    const int z5 = (z3 + z4) * F1_175;
+    t0 *= F0_298, t1 *= F2_053, t2 *= F3_072, t3 *= F1_501;
+    z1 *= -F0_899, z2 *= -F2_562, z3 = z3 * -F1_961 + z5, z4 = z4 * -F0_390 + z5;
     t0 += z1 + z3, t1 += z2 + z4, t2 += z2 + z3, t3 += z1 + z4;
     d[0] = descale(t10 + t3, SHIFT), d[7 * S] = descale(t10 - t3, SHIFT);
     d[S] = descale(t11 + t2, SHIFT), d[6 * S] = descale(t11 - t2, SHIFT);
@@ -377,21 +349,11 @@ jpegd_pixels_kernel(const uint8_t *__restrict__ planes, const int *__restrict__ 
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------
-long align16(long v) { return (v + 15) & ~15L; }
-
 // IR2RGB_OK and the geometry, or IR2RGB_EINVAL
 int geometry(int N, int C, int H, int W, int mode, int n_segments, DGeom *g) {
-    if (N < 1 || N > 65535 || H < 1 || W < 1 || H > 65535 || W > 65535 || n_segments < 1 || n_segments > 65535) return IR2RGB_EINVAL;
-    if (mode < MODE_444 || mode > MODE_422 || (C != 1 && C != 3) || (mode != MODE_L && C != 3)) return IR2RGB_EINVAL;
-    g->H = H, g->W = W, g->C = C, g->mode = mode, g->n_seg = n_segments;
-    g->ncomp = mode == MODE_L ? 1 : 3;
-    g->hs = (mode == MODE_420 || mode == MODE_422) ? 2 : 1;
-    g->vs = mode == MODE_420 ? 2 : 1;
-    g->bpm = mode == MODE_L ? 1 : g->hs * g->vs + 2;
-    g->mcus_per_row = (W + 8 * g->hs - 1) / (8 * g->hs), g->mcu_rows = (H + 8 * g->vs - 1) / (8 * g->vs);
-    const long n_mcus = (long)g->mcus_per_row * g->mcu_rows, nblk = n_mcus * g->bpm;
-    if (nblk * N > 0x7fffffffL / 64 || (long)N * n_segments > 0x7fffffffL / 8) return IR2RGB_EINVAL;
-    g->n_mcus = (int)n_mcus, g->nblk = (int)nblk;
+    if (n_segments < 1 || n_segments > 65535 || jpeg_grid(N, C, H, W, mode, g) != IR2RGB_OK) return IR2RGB_EINVAL;
+    if ((long)N * n_segments > 0x7fffffffL / 8) return IR2RGB_EINVAL;
+    g->n_seg = n_segments, g->ncomp = mode == MODE_L ? 1 : 3, g->n_mcus = g->mcus_per_row * g->mcu_rows;
     g->dw = (W + g->hs - 1) / g->hs, g->dh = (H + g->vs - 1) / g->vs;
     long off = 0;
     for (int c = 0; c < 3; ++c) {

@@ -1,6 +1,6 @@
 // u8.h -- the byte vocabulary of the 8-bit image boundary: fp32 <-> 8-bit image values and pixel bytes inside dwords.
 // Users: frame_io.hip (inference), frame_scale.hip (the loader's resize), visuals.hip (training snapshots),
-// video_metrics.hip and warp_error.hip (the scores).
+// video_metrics.hip and warp_error.hip (the scores), jpeg.hip (the bytes of its bit stream).
 //
 // Written with the round-to-nearest intrinsics so that no contraction or reassociation can change the arithmetic:
 //   to_u8         trunc(clip((x + 1) / 2 * 255, 0, 255))     numpy: ((x + 1) / 2.0 * 255.0).clip(0, 255).astype(uint8)

@@ -419,7 +419,7 @@ class VideoTranslator:
             enc.submit(out)
             if k:
                 write_oldest()
-        if enc._pending:
+        if enc.in_flight:
             write_oldest()
         return paths
 

@@ -31,17 +31,14 @@ restart   every ``restart_rows`` MCU rows: pad with 1-bits to a byte, FF D0+(n m
           interval is padded the same way and followed by FF D9.  The restart interval is the unit of parallelism of the
           device path, so ``restart_rows=0`` (no markers) exists in ``jpeg_reference`` only.
 header    SOI, JFIF APP0 (1.01, units 0, density 1x1), one DQT per table, SOF0, one DHT per table, DRI, SOS.
+shared    what the decoder (``jpeg_decode``) needs as well is stated once, in ``jpeg_common``.
 """
 import numpy as np
 
+from .jpeg_common import WRITTEN_MODES as MODES         # the index is the ``mode`` of include/ir2rgb_hip.h
+from .jpeg_common import ZIGZAG, F, Geometry, InFlight, code_lengths, descale, fix
+
 __all__ = ["jpeg_reference", "JpegEncoder", "quality_tables", "header", "MODES"]
-
-MODES = ("4:4:4", "4:2:0", "L")            # the index is the ``mode`` of include/ir2rgb_hip.h
-
-# natural (row-major) index of zigzag position k
-ZIGZAG = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21,
-                   28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61,
-                   54, 47, 55, 62, 63], dtype=np.int64)
 
 BASE_LUMA = np.array([16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56,
                       14, 17, 22, 29, 51, 87, 80, 62, 18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92,
@@ -81,10 +78,6 @@ COUNTERS = ("zrl", "stuffed", "max_dc_size", "max_ac_size", "eob_only_blocks", "
             "padded_chroma_cols_bias1", "padded_chroma_cols_bias2", "intervals", "rst_wrapped")
 
 
-def _fix(x):
-    return int(x * 65536 + 0.5)
-
-
 # ---------------------------------------------------------------------------------------------
 # tables and header
 # ---------------------------------------------------------------------------------------------
@@ -99,37 +92,10 @@ def huffman_codes(spec):
     """(bits, values) -> (code, length) int arrays indexed by symbol (length 0: no code), Annex C."""
     bits, vals = spec
     code, length = np.zeros(256, dtype=np.int64), np.zeros(256, dtype=np.int64)
-    c, k = 0, 0
-    for n in range(1, 17):
-        for _ in range(bits[n - 1]):
-            code[vals[k]], length[vals[k]] = c, n
-            c, k = c + 1, k + 1
-        c <<= 1
+    for n, first, k in code_lengths(bits):
+        for j in range(bits[n - 1]):
+            code[vals[k + j]], length[vals[k + j]] = first + j, n
     return code, length
-
-
-class Geometry:
-    """Block and restart geometry of one frame (the arithmetic csrc/jpeg.hip: geometry() repeats)."""
-
-    def __init__(self, H, W, mode, restart_rows):
-        if mode not in MODES:
-            raise ValueError(f"subsampling: one of {MODES}, got {mode!r}")
-        H, W, restart_rows = int(H), int(W), int(restart_rows)
-        if H < 1 or W < 1 or H > 65535 or W > 65535:
-            raise ValueError(f"a JPEG frame is 1..65535 pixels a side, got {H}x{W}")
-        if restart_rows < 0:
-            raise ValueError("restart_rows >= 0")
-        self.H, self.W, self.mode, self.restart_rows = H, W, mode, restart_rows
-        self.mcu = 16 if mode == "4:2:0" else 8
-        self.blocks_per_mcu = {"4:4:4": 3, "4:2:0": 6, "L": 1}[mode]
-        self.mcus_per_row, self.mcu_rows = -(-W // self.mcu), -(-H // self.mcu)
-        self.wib, self.hib = -(-W // 8), -(-H // 8)                 # real Y blocks
-        self.rows_per_interval = restart_rows if restart_rows else self.mcu_rows
-        self.n_intervals = -(-self.mcu_rows // self.rows_per_interval)
-        self.restart_interval = restart_rows * self.mcus_per_row
-        if self.restart_interval > 65535:
-            raise ValueError("restart interval above 65535 MCUs")
-        self.n_blocks = self.mcu_rows * self.mcus_per_row * self.blocks_per_mcu
 
 
 def _segment(marker, payload):
@@ -143,7 +109,7 @@ def header(H, W, quality=75, subsampling="4:2:0", restart_rows=1):
     out = b"\xff\xd8" + _segment(0xE0, b"JFIF\x00\x01\x01\x00\x00\x01\x00\x01\x00\x00")
     for i, t in enumerate(quality_tables(quality)[:1 if grey else 2]):
         out += _segment(0xDB, bytes([i]) + bytes(int(v) for v in t[ZIGZAG]))
-    comps = [(1, 0x11, 0)] if grey else [(1, 0x22 if subsampling == "4:2:0" else 0x11, 0), (2, 0x11, 1), (3, 0x11, 1)]
+    comps = [(1, g.hs << 4 | g.vs, 0)] + ([] if grey else [(2, 0x11, 1), (3, 0x11, 1)])
     out += _segment(0xC0, bytes([8]) + H.to_bytes(2, "big") + W.to_bytes(2, "big") + bytes([len(comps)])
                     + b"".join(bytes(c) for c in comps))
     for i, (dc, ac) in enumerate([(DC_LUMA, AC_LUMA), (DC_CHROMA, AC_CHROMA)][:1 if grey else 2]):
@@ -160,9 +126,9 @@ def header(H, W, quality=75, subsampling="4:2:0", restart_rows=1):
 # ---------------------------------------------------------------------------------------------
 def _ycc(rgb):
     r, g, b = (rgb[..., i].astype(np.int64) for i in range(3))
-    y = (_fix(.299) * r + _fix(.587) * g + _fix(.114) * b + 32768) >> 16
-    cb = (-_fix(.16874) * r - _fix(.33126) * g + _fix(.5) * b + (128 << 16) + 32767) >> 16
-    cr = (_fix(.5) * r - _fix(.41869) * g - _fix(.08131) * b + (128 << 16) + 32767) >> 16
+    y = (fix(.299) * r + fix(.587) * g + fix(.114) * b + 32768) >> 16
+    cb = (-fix(.16874) * r - fix(.33126) * g + fix(.5) * b + (128 << 16) + 32767) >> 16
+    cr = (fix(.5) * r - fix(.41869) * g - fix(.08131) * b + (128 << 16) + 32767) >> 16
     return y, cb, cr
 
 
@@ -190,14 +156,6 @@ def _h2v2(c, g, counters):
     return _extend(d, 8 * g.mcu_rows, out_cols)
 
 
-F = dict(f0_298=2446, f0_390=3196, f0_541=4433, f0_765=6270, f0_899=7373, f1_175=9633, f1_501=12299, f1_847=15137, f1_961=16069,
-         f2_053=16819, f2_562=20995, f3_072=25172)
-
-
-def _descale(x, n):
-    return (x + (1 << (n - 1))) >> n
-
-
 def _fdct_pass(d, first):
     """jfdctint's one-dimensional pass along the last axis of ``d`` int64 [..., 8]."""
     t0, t7, t1, t6 = d[..., 0] + d[..., 7], d[..., 0] - d[..., 7], d[..., 1] + d[..., 6], d[..., 1] - d[..., 6]
@@ -208,18 +166,18 @@ def _fdct_pass(d, first):
     if first:
         out[..., 0], out[..., 4] = (t10 + t11) << 2, (t10 - t11) << 2
     else:
-        out[..., 0], out[..., 4] = _descale(t10 + t11, 2), _descale(t10 - t11, 2)
+        out[..., 0], out[..., 4] = descale(t10 + t11, 2), descale(t10 - t11, 2)
     z1 = (t12 + t13) * F["f0_541"]
-    out[..., 2] = _descale(z1 + t13 * F["f0_765"], n)
-    out[..., 6] = _descale(z1 - t12 * F["f1_847"], n)
+    out[..., 2] = descale(z1 + t13 * F["f0_765"], n)
+    out[..., 6] = descale(z1 - t12 * F["f1_847"], n)
     z1, z2, z3, z4 = t4 + t7, t5 + t6, t4 + t6, t5 + t7
     z5 = (z3 + z4) * F["f1_175"]
     t4, t5, t6, t7 = t4 * F["f0_298"], t5 * F["f2_053"], t6 * F["f3_072"], t7 * F["f1_501"]
     z1, z2, z3, z4 = -z1 * F["f0_899"], -z2 * F["f2_562"], -z3 * F["f1_961"] + z5, -z4 * F["f0_390"] + z5
-    out[..., 7] = _descale(t4 + z1 + z3, n)
-    out[..., 5] = _descale(t5 + z2 + z4, n)
-    out[..., 3] = _descale(t6 + z2 + z3, n)
-    out[..., 1] = _descale(t7 + z1 + z4, n)
+    out[..., 7] = descale(t4 + z1 + z3, n)
+    out[..., 5] = descale(t5 + z2 + z4, n)
+    out[..., 3] = descale(t6 + z2 + z3, n)
+    out[..., 1] = descale(t7 + z1 + z4, n)
     return out
 
 
@@ -332,7 +290,6 @@ def _codes():
 def entropy_scan(blocks, g, counters):
     """The blocks of a scan in coding order -> the bytes after SOS, EOI included."""
     codes = _codes()
-    comp_of = {"4:4:4": (0, 1, 2), "4:2:0": (0, 0, 0, 0, 1, 2), "L": (0,)}[g.mode]
     per_interval = g.rows_per_interval * g.mcus_per_row * g.blocks_per_mcu
     w = _Bits(counters)
     pred = [0, 0, 0]
@@ -341,7 +298,7 @@ def entropy_scan(blocks, g, counters):
             pred = [0, 0, 0]
         chunk = blocks[i * per_interval:(i + 1) * per_interval]
         for j, blk in enumerate(chunk):
-            c = comp_of[j % g.blocks_per_mcu]
+            c = g.comp_of[j % g.blocks_per_mcu]
             dc, ac = codes[min(c, 1)]
             _encode_block(w, blk, pred[c], dc, ac, counters)
             pred[c] = int(blk[0])
@@ -414,6 +371,15 @@ def fetch(src, pinned):
     return pinned[:m].numpy().tobytes()
 
 
+def fetch_file(row, length, pinned, who, floor=0, note=""):
+    """The file in the device row ``row`` whose size the device reported as ``length`` (read from pinned memory, after the
+    event behind both): the size is held to ``floor < length <= len(row)`` before ``fetch`` copies that many bytes."""
+    m = int(length)
+    if not floor < m <= row.shape[0]:
+        raise RuntimeError(f"{who} reports {m} bytes{note}")
+    return fetch(row[:m], pinned)
+
+
 class JpegEncoder:
     """JPEG files of uint8 device frames, encoded on the device (csrc/jpeg.hip), equal to ``jpeg_reference`` byte for byte.
 
@@ -452,8 +418,9 @@ class JpegEncoder:
         self._n = 0
         self._slots = [None, None]       # per slot: (out [n, capacity], lengths [n], pinned lengths, pinned bytes)
         self._ws = None
-        self._pending = []               # [(slot, n, event)] oldest first
-        self._turn = 0                   # nothing but header and tables is allocated before the first submit()
+        self._pending = InFlight("JpegEncoder")         # remembers n
+        self.in_flight = self._pending                  # public: len() is the submissions collect() has not handed back
+        # (nothing but header and tables is allocated before the first submit())
 
     def workspace_bytes(self, n):
         from . import _lib
@@ -499,9 +466,7 @@ class JpegEncoder:
     def submit(self, frames_u8):
         import torch
         f = self._frames(frames_u8)
-        if len(self._pending) == 2:
-            raise RuntimeError("JpegEncoder: two submissions are in flight; collect() one first")
-        slot = self._turn
+        slot = self._pending.slot()
         self._reserve(f.shape[0], slot)
         out, lengths, host_len, _ = self._slots[slot]
         n = f.shape[0]
@@ -509,28 +474,16 @@ class JpegEncoder:
             # the workspace is shared: launches of one stream run in order, and submit() is a one-stream interface
             self.encode_into(f, out[:n], lengths[:n])
             host_len[:n].copy_(lengths[:n], non_blocking=True)
-            event = torch.cuda.Event()
-            event.record()
-        self._pending.append((slot, n, event))
-        self._turn ^= 1
+            self._pending.push(n)
 
     def collect(self):
         """The files of the oldest submission in flight."""
-        if not self._pending:
-            raise RuntimeError("JpegEncoder: nothing was submitted")
-        slot, n, event = self._pending.pop(0)
+        slot, n = self._pending.pop()
         out, _, host_len, host = self._slots[slot]
-        event.synchronize()
-        files = []
-        for i in range(n):
-            m = int(host_len[i])
-            if not len(self.header) < m <= self.capacity:
-                raise RuntimeError(f"JpegEncoder: frame {i} reports {m} bytes (capacity {self.capacity})")
-            files.append(fetch(out[i, :m], host))
-        return files
+        return [fetch_file(out[i], host_len[i], host, f"JpegEncoder: frame {i}", len(self.header), f" (capacity {self.capacity})")
+                for i in range(n)]
 
     def encode(self, frames_u8):
-        if self._pending:
-            raise RuntimeError("JpegEncoder.encode: collect() what was submitted first")
+        self._pending.require_idle("encode")
         self.submit(frames_u8)
         return self.collect()

@@ -31,17 +31,17 @@ entry lies at or past its own end decodes nothing and hands the entry on).  Afte
 are the true ones, so at most n_sub rounds are needed; a round that changes no entry ends the loop earlier -- Huffman
 streams resynchronise, so that is the usual end.  Wrong-sync decodes read garbage by design: reads past the segment's end
 give 1-bits, 16 bits that are no code are consumed as symbol 0, k never passes 64.
+What the encoder (``jpeg``) needs as well is stated once, in ``jpeg_common``.
 """
 import os
 
 import numpy as np
 
-from .jpeg import ZIGZAG, F, _descale, _fix
+from .jpeg_common import MODES, SAMPLING, ZIGZAG, F, Geometry, InFlight, code_lengths, descale, fix
 
 __all__ = ["parse", "decode_reference", "entropy_model", "JpegDecoder", "MODES", "Info", "Segment"]
 
-MODES = ("4:4:4", "4:2:0", "L", "4:2:2")            # the index is the ``mode`` of include/ir2rgb_hip.h (JPEG input)
-_LUMA_SAMPLING = {(1, 1): "4:4:4", (2, 2): "4:2:0", (2, 1): "4:2:2"}
+_LUMA_SAMPLING = {hv: mode for mode, hv in SAMPLING.items() if mode != "L"}       # of a three-component frame
 
 # status bits of the write pass (include/ir2rgb_hip.h: IR2RGB_JPEGD_*)
 ERR_CODE, ERR_INDEX, ERR_BLOCKS, ERR_LEFTOVER, ERR_SEGMENT = 1, 2, 4, 8, 16
@@ -98,26 +98,6 @@ class Info:
     @property
     def geometry(self):
         return Geometry(self.H, self.W, self.mode)
-
-
-class Geometry:
-    """Block geometry of a frame (the arithmetic csrc/jpeg_decode.hip: geometry() repeats)."""
-
-    def __init__(self, H, W, mode):
-        if mode not in MODES:
-            raise ValueError(f"mode: one of {MODES}, got {mode!r}")
-        H, W = int(H), int(W)
-        if H < 1 or W < 1 or H > 65535 or W > 65535:
-            raise ValueError(f"a JPEG frame is 1..65535 pixels a side, got {H}x{W}")
-        self.H, self.W, self.mode = H, W, mode
-        self.hs, self.vs = {"4:4:4": (1, 1), "4:2:0": (2, 2), "L": (1, 1), "4:2:2": (2, 1)}[mode]
-        self.ncomp = 1 if mode == "L" else 3
-        self.blocks_per_mcu = 1 if mode == "L" else self.hs * self.vs + 2
-        self.mcus_per_row, self.mcu_rows = -(-W // (8 * self.hs)), -(-H // (8 * self.vs))
-        self.n_mcus = self.mcus_per_row * self.mcu_rows
-        self.n_blocks = self.n_mcus * self.blocks_per_mcu
-        self.comp_of = (0,) * (self.hs * self.vs) + ((1, 2) if self.ncomp == 3 else ())
-        self.dw, self.dh = -(-W // self.hs), -(-H // self.vs)           # the chroma planes' real size
 
 
 def _be16(d, i):
@@ -205,11 +185,8 @@ def parse(data, strict=True):
                     raise ValueError("JPEG: malformed DHT")
                 if tid > 1:
                     raise NotImplementedError(f"JPEG: Huffman table id {tid} (0..1 only)")
-                code = 0
-                for n_l, b in enumerate(bits, 1):
-                    code = (code + b) << 1
-                    if code > (2 << n_l):
-                        raise ValueError("JPEG: DHT assigns more codes than a length has")
+                if any(first + bits[n_l - 1] > 1 << n_l for n_l, first, _ in code_lengths(bits)):
+                    raise ValueError("JPEG: DHT assigns more codes than a length has")
                 info.huffman[(cls, tid)] = (bits, list(p[j + 17:j + 17 + nv]))
                 j += 17 + nv
         elif m == 0xDD:
@@ -291,15 +268,12 @@ def huffman_decode_table(spec):
     reads (the per-file table block) and what ``_lut`` expands."""
     bits, vals = spec
     limit, offset = np.zeros(16, dtype=np.int64), np.zeros(16, dtype=np.int64)
-    code, k, last = 0, 0, 0
-    for n in range(1, 17):
-        offset[n - 1] = k - code
-        code += bits[n - 1]
-        k += bits[n - 1]
+    last = 0
+    for n, first, k in code_lengths(bits):
+        offset[n - 1] = k - first
         if bits[n - 1]:
-            last = code << (16 - n)
+            last = (first + bits[n - 1]) << (16 - n)
         limit[n - 1] = last
-        code <<= 1
     values = np.zeros(256, dtype=np.int64)
     values[:len(vals)] = vals
     return limit, offset, values
@@ -550,10 +524,10 @@ def _idct_pass(d, shift):
     z1, z2, z3, z4 = -z1 * F["f0_899"], -z2 * F["f2_562"], -z3 * F["f1_961"] + z5, -z4 * F["f0_390"] + z5
     t0, t1, t2, t3 = t0 + z1 + z3, t1 + z2 + z4, t2 + z2 + z3, t3 + z1 + z4
     out = np.empty_like(d)
-    out[..., 0], out[..., 7] = _descale(t10 + t3, shift), _descale(t10 - t3, shift)
-    out[..., 1], out[..., 6] = _descale(t11 + t2, shift), _descale(t11 - t2, shift)
-    out[..., 2], out[..., 5] = _descale(t12 + t1, shift), _descale(t12 - t1, shift)
-    out[..., 3], out[..., 4] = _descale(t13 + t0, shift), _descale(t13 - t0, shift)
+    out[..., 0], out[..., 7] = descale(t10 + t3, shift), descale(t10 - t3, shift)
+    out[..., 1], out[..., 6] = descale(t11 + t2, shift), descale(t11 - t2, shift)
+    out[..., 2], out[..., 5] = descale(t12 + t1, shift), descale(t12 - t1, shift)
+    out[..., 3], out[..., 4] = descale(t13 + t0, shift), descale(t13 - t0, shift)
     return out
 
 
@@ -622,11 +596,11 @@ def upsample(plane, g, counters=None):
 
 
 def ycc_to_rgb(y, cb, cr):
-    fix = (lambda x: int(x * 65536)) if "fix_floor" in _FAULTS else _fix
+    fx = (lambda x: int(x * 65536)) if "fix_floor" in _FAULTS else fix
     cb, cr = cb - 128, cr - 128
-    r = y + ((fix(1.402) * cr + 32768) >> 16)
-    b = y + ((fix(1.772) * cb + 32768) >> 16)
-    gr = y + ((-fix(0.34414) * cb + 32768 - fix(0.71414) * cr) >> 16)
+    r = y + ((fx(1.402) * cr + 32768) >> 16)
+    b = y + ((fx(1.772) * cb + 32768) >> 16)
+    gr = y + ((-fx(0.34414) * cb + 32768 - fx(0.71414) * cr) >> 16)
     return np.clip(np.stack([r, gr, b], axis=-1), 0, 255).astype(np.uint8)
 
 
@@ -700,8 +674,7 @@ class JpegDecoder:
         self.sub_bytes = int(sub_bytes)
         self._slots = [None, None]      # per slot: [pinned staging, device staging, pinned status]
         self._ws = None
-        self._pending = []              # [(slot, names, out, event)] oldest first
-        self._turn = 0
+        self._pending = InFlight("JpegDecoder")         # remembers (names, out); len(): the submissions not collected yet
         self._last_ws, self._last_shape = None, None      # of the last decode_into (rounds())
 
     @classmethod
@@ -782,21 +755,19 @@ class JpegDecoder:
 
     def rounds(self):
         """Relaxation rounds of every (file, segment) of the last finished call, int32 [N, n_segments] (synchronises)."""
-        from . import _lib
         if self._last_shape is None:
             raise RuntimeError("JpegDecoder.rounds: nothing was decoded")
         n, n_seg = self._last_shape
-        off = _lib.query("ir2rgb_jpeg_decode_workspace_bytes", n, self.H, self.W, self.mode, n_seg) - 8 * n * n_seg
+        off = self.workspace_bytes(n, n_seg) - 8 * n * n_seg
         rec = self._last_ws[off:off + 8 * n * n_seg].cpu().numpy().view(np.int32).reshape(n, n_seg, 2)
         return rec[:, :, 1].copy()
 
     def submit(self, files, strict=True):
         import torch
-        if len(self._pending) == 2:
-            raise RuntimeError("JpegDecoder: two submissions are in flight; collect() one first")
+        slot = self._pending.slot()
         infos, names = self.prepare(files, strict=strict)
         block, n_seg, layout = self.pack(infos)
-        n, slot = len(infos), self._turn
+        n = len(infos)
         s = self._slots[slot]
         if s is None or s[0].numel() < block.size or s[2].numel() < n:
             size = max(block.size, 2 * s[0].numel() if s else 0)
@@ -810,17 +781,11 @@ class JpegDecoder:
             s[1][:block.size].copy_(s[0][:block.size], non_blocking=True)
             self.decode_into(s[1], n, n_seg, layout, out, status)
             s[2][:n].copy_(status, non_blocking=True)
-            event = torch.cuda.Event()
-            event.record()
-        self._pending.append((slot, names, out, event))
-        self._turn ^= 1
+            self._pending.push(names, out)
 
     def collect(self):
         """The frames of the oldest submission in flight, uint8 [N,H,W,C] on the device."""
-        if not self._pending:
-            raise RuntimeError("JpegDecoder: nothing was submitted")
-        slot, names, out, event = self._pending.pop(0)
-        event.synchronize()
+        slot, names, out = self._pending.pop()
         status = self._slots[slot][2][:len(names)].tolist()
         for name, st in zip(names, status):
             if st:
@@ -829,8 +794,7 @@ class JpegDecoder:
         return out
 
     def decode(self, files):
-        if self._pending:
-            raise RuntimeError("JpegDecoder.decode: collect() what was submitted first")
+        self._pending.require_idle("decode")
         self.submit(files)
         return self.collect()
 
@@ -838,8 +802,7 @@ class JpegDecoder:
         """Generator over uint8 [H,W,C] device frames of ``files`` in order; the next chunk of ``chunk`` files is parsed,
         uploaded and decoding while the frames of this one are consumed."""
         files = list(files)
-        if self._pending:
-            raise RuntimeError("JpegDecoder.frames: collect() what was submitted first")
+        self._pending.require_idle("frames")
         chunks = [files[i:i + chunk] for i in range(0, len(files), int(chunk))]
         if chunks:
             self.submit(chunks[0])

@@ -306,15 +306,14 @@ class Snapshots:
             write_index(self.out_dir, epoch, self.names, self.fmt)
 
     def _write_files(self, epoch, names):
-        from .jpeg import fetch
+        from .jpeg import fetch_file
         j = self._jpeg
         os.makedirs(self.img_dir, exist_ok=True)
         for i, (label, _) in enumerate(names):
-            m = int(j["host_lengths"][i])
-            if not 0 < m <= j["out"].shape[1]:
-                raise RuntimeError(f"Snapshots: panel {label!r} reports {m} bytes")
+            # (on a copy stream: not behind the windows queued since)
+            data = fetch_file(j["out"][i], j["host_lengths"][i], j["host"], f"Snapshots: panel {label!r}")
             with open(os.path.join(self.img_dir, image_name(epoch, label, self.fmt)), "wb") as f:
-                f.write(fetch(j["out"][i, :m], j["host"]))         # (on a copy stream: not behind the windows queued since)
+                f.write(data)
 
     def flush(self):
         """Writes the snapshot that is still on its way (``fit`` calls this before it returns)."""

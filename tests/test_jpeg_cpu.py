@@ -146,6 +146,14 @@ def test_header_and_quality_tables(goldens):
     assert np.array_equal(words[:64], J.quality_tables(75)[0]) and np.array_equal(words[64:128], J.quality_tables(75)[1])
     code, length = J.huffman_codes(J.AC_CHROMA)
     assert np.array_equal(words[160 + 256:] >> 16, length) and np.array_equal(words[160 + 256:] & 0xFFFF, code)
+    # and their layout and the modes' numbers are the ones the library's header declares
+    from ir2rgb_amd.jpeg_common import MODES
+    with open(os.path.join(os.path.dirname(HERE), "include", "ir2rgb_hip.h")) as f:
+        text = f.read()
+    assert f"#define IR2RGB_JPEG_TABLE_WORDS {J.TABLE_WORDS}\n" in text
+    for name, mode in (("444", "4:4:4"), ("420", "4:2:0"), ("L", "L"), ("422", "4:2:2")):
+        assert f"#define IR2RGB_JPEG_{name} {MODES.index(mode)}\n" in text
+    assert J.MODES == MODES[:3]
 
 
 @pytest.mark.parametrize("fault", ["quant_floor", "chroma_bias_2", "chroma_pad_output", "dummy_real_dct", "no_stuffing",
